@@ -2,7 +2,7 @@
 """Benchmark of the hot path: Mvoxels/s of compress + reconstruct (NDMPS.from_tensor with the bond cap applied in
 the sweep, then NDMPS.to_tensor), input and output resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--config metric|2|3|4|5] [--total-volumes V]
+    python bench.py --gpus N --steps K --warmup W [--config metric|2|3|4|5] [--total-volumes V] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -83,7 +83,12 @@ def parse(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo + --share-gpu rehearses N ranks on a 1-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy "
+                         "(rank 0's volumes; see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     # an explicit per-GPU batch without --total-volumes asks for weak scaling even on a strong-scaling config
     if args.batch is not None and args.total_volumes is None:
@@ -153,6 +158,40 @@ def throughput(job, n_vox, steps, elapsed):
     """Whole-job Mvoxels/s: all ranks together processed n_volumes volumes per step (weak scaling: world x
     batch_per_gpu; strong scaling: the fixed total)."""
     return job["n_volumes"] * n_vox * steps / elapsed / 1e6
+
+
+DUMP_SEED = 7  # fixes which voxels the reconstruction sample holds, so that two builds dump the same ones
+DUMP_RECON_BYTES = 32 << 20  # the sample of the reconstructions; the other arrays are a few KB
+
+
+def dump_outputs(out_dir, objs, recs):
+    """--dump-outputs: the NDMPS objects and reconstructions the last timed step returned, as float32 / float64 .npy files.
+    reconstruction.npy: (volumes, S) float32, the same S seeded voxel positions (flat C order) of every reconstruction,
+    all of them when they fit in DUMP_RECON_BYTES; bond_sizes.npy: (volumes, bonds) float64; sweep_spectra.npy:
+    (volumes, sum of bonds) float64, the singular values the sweep kept at every bond, one row per volume (NaN-padded),
+    written when the objects carry them.  Only gauge-invariant outputs: the cores themselves are fixed up to signs and
+    rotations that a different eigen-solver may legitimately change."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n_vox = int(recs[0].numel())
+    per = min(n_vox, DUMP_RECON_BYTES // (4 * len(recs)))
+    if per == n_vox:
+        idx = None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_vox, per, replace=False))
+        idx = torch.from_numpy(idx).to(recs[0].device)
+    sample = [r.reshape(-1) if idx is None else r.reshape(-1)[idx] for r in recs]
+    np.save(os.path.join(out_dir, "reconstruction.npy"), torch.stack(sample).to(torch.float32).cpu().numpy())
+    bonds = [list(o.bond_sizes()) for o in objs]
+    np.save(os.path.join(out_dir, "bond_sizes.npy"), np.array(bonds, dtype=np.float64))
+    spectra = [getattr(o, "sweep_spectra", None) for o in objs]
+    if all(s is not None for s in spectra):
+        rows = [np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in s if v is not None]) for s in spectra]
+        out = np.full((len(rows), max(len(r) for r in rows)), np.nan)
+        for i, r in enumerate(rows):
+            out[i, :len(r)] = r
+        np.save(os.path.join(out_dir, "sweep_spectra.npy"), out)
 
 
 # ------------------------------------------------------------------------------------------ data
@@ -420,6 +459,7 @@ def other_configs(ctx):
         # six timed steps: with batches issued as a stream the objects of the last `lanes` batches are built at the end of the
         # timed region, which three steps would over-weigh (config 5: 33 ms per step over three, 28 over ten)
         a2.steps, a2.warmup, a2.skip_single, a2.no_cpu_baseline = 6, 2, True, True
+        a2.dump_outputs = None  # the dump is the headline workload's
         c2 = dict(ctx, args=a2, job=job_descriptor(a2, 1))
         t0 = time.perf_counter()
         full = run_tensor(c2) if cfg["kind"] == "tensor" else run_cubes(c2)
@@ -530,6 +570,8 @@ def run_cubes(ctx):
     def collect(pending):
         objs, recs = pending.result()
         last["obj"], last["rec"] = objs[0], recs[0]
+        if args.dump_outputs:  # the whole batch is held only when asked for: it is 4 GB at the metric configuration
+            last["objs"], last["recs"] = objs, recs
 
     def step():
         # The step returns when everything is enqueued; the next step queues behind it on the same streams (like the
@@ -541,6 +583,8 @@ def run_cubes(ctx):
             objs, recs = batch_mod.encode_decode_concurrent(xs, groups=groups, mode=job["mode"], max_bond=job["chi"],
                                                              pool=pool, wait=False)
             last["obj"], last["rec"] = objs[0], recs[0]
+            if args.dump_outputs:
+                last["objs"], last["recs"] = objs, recs
             return
         in_flight.append(batch_mod.encode_decode_begin(xs, groups=groups, mode=job["mode"], max_bond=job["chi"], pool=pool,
                                                        lane=counter[0], lanes=lanes))
@@ -582,6 +626,8 @@ def run_cubes(ctx):
     ndmps_mod.set_stage_timer(None)
     _lib.check(lib.ndmps_profile_enable(0))
     obj, rec = last["obj"], last["rec"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last.pop("objs"), last.pop("recs"))
     stages = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps}
               for k, v in timer.totals_ms().items()}
     value = throughput(job, n_vox, args.steps, elapsed)
@@ -962,6 +1008,8 @@ def run_tensor(ctx):
     roofline["end_to_end_algorithmic_GBps"] = 2 * esize * n_vox / (ms_per_step * 1e-3) / 1e9
     roofline["end_to_end_frac"] = roofline["end_to_end_algorithmic_GBps"] / HBM_PEAK_GBPS
     obj = last["obj"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [obj], [last["rec"]])
     line = base_line(
         job, args, world, value, ms_per_step, dtype,
         f"ONE {'x'.join(str(v) for v in shape)} synthetic fMRI tensor per step, bond cap {chi}, {storage}; "

@@ -193,6 +193,12 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C img-compression-mps_amd/csrc`.  There is no CPU fallback."
         )
+    # torch first: its libraries ask for "libamdhip64.so", this one for "libamdhip64.so.7".  Loaded first, this library
+    # would bring in the system HIP runtime and torch then a second one of its own; the two do not share devices,
+    # streams or allocations (hipMalloc here failed with "no ROCm-capable device").  With torch's runtime already in
+    # the process, this library binds to it by SONAME.
+    import torch  # noqa: F401
+
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the ABI and the binding drift apart

@@ -1,13 +1,15 @@
 """Golden vectors for the quantise helpers from the REFERENCE's own filetools.py
-(/root/reference/src/imgcompressionmps/utils/filetools.py:7-39).  Build container only:
-    python tests/golden/make_golden_filetools.py   -> filetools.npz
+(src/imgcompressionmps/utils/filetools.py:7-39):
+    python tests/golden/make_golden_filetools.py REFERENCE_SRC   -> filetools.npz
 """
 import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, "/root/reference/src")
+if len(sys.argv) != 2:
+    raise SystemExit(f"usage: python {sys.argv[0]} REFERENCE_SRC  (the reference package's src/ directory)")
+sys.path.insert(0, sys.argv[1])
 from imgcompressionmps.utils.filetools import get_num_bits, scale_back, scale_to_dtype  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))

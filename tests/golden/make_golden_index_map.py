@@ -1,8 +1,8 @@
 """Generate golden vectors for the index map from the REFERENCE's own code.
 
-Run in the build container only (the reference does not travel to the GPU box):
-    python tests/golden/make_golden_index_map.py
-Imports /root/reference/src/imgcompressionmps/utils/core.py and stores
+Run where the reference is installed (the test suite itself only reads the stored fixtures):
+    python tests/golden/make_golden_index_map.py REFERENCE_SRC
+Imports REFERENCE_SRC/imgcompressionmps/utils/core.py and stores
   * factor_arr / prod / qubit_size / full enc_map for small shapes  -> index_map_small.npz
   * sha256 of the flat destination permutation for large shapes      -> index_map_hashes.json
 The flat destination of a voxel is ravel_multi_index(enc_map[:, voxel], qubit_size), i.e.
@@ -15,7 +15,9 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, "/root/reference/src")
+if len(sys.argv) != 2:
+    raise SystemExit(f"usage: python {sys.argv[0]} REFERENCE_SRC  (the reference package's src/ directory)")
+sys.path.insert(0, sys.argv[1])
 from imgcompressionmps.utils.core import gen_encoding_map, get_factorlist  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))

@@ -1,17 +1,18 @@
 """Golden SSIM / PSNR values from the REFERENCE's own metrics.py
-(/root/reference/src/imgcompressionmps/utils/metrics.py:11-146).
+(src/imgcompressionmps/utils/metrics.py:11-146).
 
-Needs scikit-image, which only /opt/conda/bin/python3.9 has in the build container
-(skimage 0.18.3; the reference pins 0.24.0 -- same uniform-window / sample-covariance
-algorithm for float inputs with explicit data_range).  Build container only:
-    /opt/conda/bin/python3.9 tests/golden/make_golden_metrics.py   -> metrics.npz
+Needs scikit-image (the stored fixtures were made with skimage 0.18.3; the reference pins 0.24.0 --
+same uniform-window / sample-covariance algorithm for float inputs with explicit data_range):
+    python tests/golden/make_golden_metrics.py REFERENCE_SRC   -> metrics.npz
 """
 import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, "/root/reference/src")
+if len(sys.argv) != 2:
+    raise SystemExit(f"usage: python {sys.argv[0]} REFERENCE_SRC  (the reference package's src/ directory)")
+sys.path.insert(0, sys.argv[1])
 import skimage  # noqa: E402
 from imgcompressionmps.utils.metrics import compute_psnr, compute_ssim_by_dim, ssim_3d_axis  # noqa: E402
 

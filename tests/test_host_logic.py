@@ -74,6 +74,22 @@ def test_library_exports_every_declared_symbol():
     assert lib.ndmps_version() >= 100
 
 
+def test_library_loaded_before_torch_shares_its_hip_runtime():
+    """build() loads the library before anything imports torch; smoke() in the same process then failed with "no
+    ROCm-capable device" because the process held two HIP runtimes (the system one, pulled in by the library, and
+    torch's own).  A fresh process in that order must map exactly one."""
+    import subprocess
+    import sys
+
+    code = (f"import sys; sys.path.insert(0, {ROOT!r})\n"
+            "from imgcompressionmps_amd import _lib\n_lib.load()\nimport torch\n"
+            "import json\nprint(json.dumps(sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l})))")
+    flags = ["-s"] if sys.flags.no_user_site else []
+    out = subprocess.run([sys.executable, *flags, "-c", code], capture_output=True, text=True, check=True).stdout
+    runtimes = json.loads(out.strip().splitlines()[-1])
+    assert len(runtimes) == 1, runtimes
+
+
 def test_resident_kernels_keep_their_state_in_registers():
     """The resident tridiagonalisation holds its share of the matrix in registers for the life of a launch and spins on
     agent-scope loads written in inline assembly; a build whose register allocation spills part of that state to
