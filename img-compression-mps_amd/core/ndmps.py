@@ -828,6 +828,12 @@ class NDMPS:
 
         ``cutoff == 0`` with no ``max_bond`` leaves every bond as it is (quimb only trims when
         cutoff > 0); the product of the cores is unchanged either way.
+
+        Each bond keeps the singular values s_j > max(cutoff, floor) * s_0 (at least one, at most
+        ``max_bond``), with the storage floor 1e-6 for fp32 and bf16 cores and 1e-8 for fp64 cores.
+        The floor applies with ``cutoff == 0`` too: ``compress(0, max_bond=chi)`` ("parity mode")
+        keeps min(#{s_j > floor * s_0}, chi) values per bond, where the reference keeps min(n, chi),
+        zeros included -- it equals the reference run at ``cutoff=floor``.
         """
         if cutoff < 0:
             raise ValueError("cutoff must be non-negative")

@@ -56,22 +56,25 @@ inline int grid1d(int64_t n) {
 // |A v_j|^2 for the eigenvectors v_j = V[:, i0 + j], j < t, of a Gram matrix of A: the singular values behind the SMALLEST
 // eigenvalues, which the eigenvalues themselves resolve only to ~1e-15 |G| (3e-8 of the largest singular value).
 // A(r, c) = A[r rs + c cs] (rs = n, cs = 1 for G = A^T A; the transposed strides for G = A A^T).  Thread (row, j):
-// 4 rows x 64 columns per workgroup; partial[blockIdx.x][j] = sum over the workgroup's rows; tail_norm_reduce_kernel
-// adds the row blocks in fixed order.
+// 4 rows x 64 columns per workgroup, row blocks strided by the grid (one row per thread when gridDim.x covers the
+// rows); partial[blockIdx.x][j] = sum over the workgroup's rows; tail_norm_reduce_kernel adds the row blocks in fixed
+// order.
 template <typename T>
 __global__ void __launch_bounds__(256)
 tail_norm_partial_kernel(const T* __restrict__ A, int64_t rs, int64_t cs, int rows, int cols, const double* __restrict__ V,
                          int ldv, int i0, int t, double* __restrict__ partial) {
   __shared__ double red[4][64];
   const int jl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int j = blockIdx.y * 64 + jl, r = blockIdx.x * 4 + rl;
-  double y = 0.0;
-  if (r < rows && j < t) {
+  const int j = blockIdx.y * 64 + jl;
+  double acc = 0.0;
+  for (int r = blockIdx.x * 4 + rl; r < rows && j < t; r += gridDim.x * 4) {
     const T* a = A + (int64_t)r * rs;
     const double* v = V + i0 + j;
+    double y = 0.0;
     for (int c = 0; c < cols; ++c) y = fma(ndmps::to_f64(a[(int64_t)c * cs]), v[(int64_t)c * ldv], y);
+    acc += y * y;
   }
-  red[rl][jl] = y * y;
+  red[rl][jl] = acc;
   __syncthreads();
   if (rl == 0 && j < t) partial[(int64_t)blockIdx.x * t + j] = (red[0][jl] + red[1][jl]) + (red[2][jl] + red[3][jl]);
 }
@@ -130,10 +133,15 @@ scale_rows_to_f32_kernel(const double* __restrict__ M, int64_t k, int64_t n, con
 
 // in-place: M (rows x cols fp64), column c scaled by sqrt(max(w[c], 0))
 __global__ void __launch_bounds__(256)
-scale_cols_sqrt_kernel(double* __restrict__ M, int64_t rows, int64_t cols, const double* __restrict__ w) {
+scale_cols_sqrt_kernel(double* __restrict__ M, int64_t rows, int64_t cols, const double* __restrict__ w,
+                       double rel_zero = 0.0) {
+  // eigenvalues at or below rel_zero * max(w) (sorted either way) are solver noise of a zero: a zero column
+  const double zero = rel_zero * fmax(fmax(w[0], w[cols - 1]), 0.0);
   const int64_t total = rows * cols;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
-    M[e] *= sqrt(fmax(w[e % cols], 0.0));
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const double we = w[e % cols];
+    M[e] *= we > zero ? sqrt(we) : 0.0;
+  }
 }
 
 __global__ void __launch_bounds__(256) sqrt_clamp_kernel(const double* __restrict__ w, int64_t n, double* s) {
@@ -853,9 +861,13 @@ int sweep_impl(int batch, T* const* h_dense, int L, const int64_t* h_dims, doubl
           const int64_t n = h_dims[i] * chi_r[b], m = cur_elems[b] / n;
           const bool right = n <= m;  // G = A^T A: vectors in R^n, |A v|; else G = A A^T: |A^T u|
           const int rows = (int)(right ? m : n), cols = (int)(right ? n : m);
-          const int nblk = (int)ceil_div(rows, 4);
+          // partials (nblk x t) and sums (t) live in this volume's G (sq doubles): a tall unfolding (rows / 4 row blocks
+          // beyond what fits, e.g. 4096 rows of order 8 in an order-64 layout) takes fewer blocks of more rows each
+          int nblk = (int)ceil_div(rows, 4);
+          if ((int64_t)nblk * t + t > sq) nblk = (int)((sq - t) / t);
           double* partial = G + (int64_t)b * sq;
-          NDMPS_REQUIRE((int64_t)nblk * t + t <= sq, "internal: no room for the tail norms (%lld x %lld)", (long long)nblk, (long long)t);
+          NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= sq, "internal: no room for the tail norms (%lld x %lld)",
+                        (long long)nblk, (long long)t);
           double* out = partial + (int64_t)nblk * t;
           hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
                              (const T*)cur[b], right ? n : (int64_t)1, right ? (int64_t)1 : n, rows, cols,
@@ -1479,7 +1491,9 @@ int compress_bond_impl(const T* d_t1, const T* d_t2, int64_t chi_l, int64_t d1, 
       NDMPS_TRY(direct_vectors(chi, g2_direct));
     }
     if (!g2_direct) NDMPS_TRY(ndmps_syevj_f64(G2, chi, Lt, w2, ev_ws, ev_bytes, &sweeps, s));
-    hipLaunchKernelGGL(scale_cols_sqrt_kernel, dim3(grid1d(c2)), dim3(256), 0, s, Lt, chi, chi, w2);
+    // a singular G2 (rank-deficient T2) has eigenvalues of ~kDirectDoubt |G2| where it has zeros: their square roots
+    // would be columns of ~3e-7 |T2| pointing anywhere, spurious singular values of T1 Lt
+    hipLaunchKernelGGL(scale_cols_sqrt_kernel, dim3(grid1d(c2)), dim3(256), 0, s, Lt, chi, chi, w2, kDirectDoubt);
     NDMPS_LAUNCH_CHECK();
   }
   NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, G1, chi, Lt, chi, tmp, chi, s));
@@ -1497,7 +1511,38 @@ int compress_bond_impl(const T* d_t1, const T* d_t2, int64_t chi_l, int64_t d1, 
     NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
     NDMPS_CHECK_HIP(hipStreamSynchronize(s));
   }
-  for (auto& x : sv) x = sqrt(std::max(x, 0.0));  // eigenvalues of H are s^2
+  // fp64 cores: H carries s^2, so a zero comes back at ~sqrt(n u) s_0 -- on kCutoffFloorF64 itself -- and the eigenvalues
+  // in doubt (direct_doubt_from) cannot decide the rank.  Those below the cap are measured directly, s_j = |T1 Lt v_j|
+  // (H = (T1 Lt)^T (T1 Lt)), whose noise is ~u |T1| |Lt|, as sweep_impl measures its tail norms; they replace the squared
+  // values in the rank and in the s^-1/2, s^-3/2 scalings.  fp32 and bf16 cores: the floor (1e-6) is far above the noise.
+  // (k is 1 whatever the values when at most one may be kept; from chi = 2 on, one row block fits H: 2 t <= chi^2)
+  const int64_t limit = max_bond > 0 ? std::min(max_bond, chi) : chi;
+  if (sizeof(T) == 8 && limit > 1 && direct_doubt_from(sv.data(), chi, std::max(cutoff, cutoff_floor<T>())) < limit) {
+    if (h_direct) {  // every vector is needed: the Jacobi computes them all (same spectrum)
+      NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));
+      NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
+      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+      h_direct = false;
+    }
+    const int64_t i0 = direct_doubt_from(sv.data(), chi, std::max(cutoff, cutoff_floor<T>())), t = chi - i0;
+    if (i0 < limit) {
+      NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, Lt, chi, V, chi, P1, chi, s));  // Lt V; P1 is rewritten below
+      // partials (nblk x t) and sums (t) in H, free now: fewer blocks of more rows when ceil(m1 / 4) do not fit
+      int nblk = (int)ceil_div(m1, 4);
+      if ((int64_t)nblk * t + t > c2) nblk = (int)((c2 - t) / t);
+      NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= c2, "internal: no room for the tail norms (%lld x %lld)",
+                    (long long)nblk, (long long)t);
+      double* out = H + (int64_t)nblk * t;
+      hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
+                         d_t1, chi, (int64_t)1, (int)m1, (int)chi, (const double*)P1, (int)chi, (int)i0, (int)t, H);
+      hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, H, nblk, (int)t, out);
+      NDMPS_LAUNCH_CHECK();
+      NDMPS_CHECK_HIP(hipMemcpyAsync(wh + i0, out, t * sizeof(double), hipMemcpyDeviceToDevice, s));
+      NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data() + i0, out, t * sizeof(double), hipMemcpyDeviceToHost, s));
+      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+    }
+  }
+  for (auto& x : sv) x = sqrt(std::max(x, 0.0));  // eigenvalues of H are s^2 (measured |T1 Lt v_j|^2 in doubt)
   const int64_t k = kept_rank(sv, cutoff, max_bond, cutoff_floor<T>());
   if (h_direct) {
     NDMPS_TRY(direct_vectors(k, h_direct));
