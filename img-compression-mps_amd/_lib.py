@@ -80,6 +80,11 @@ SIGNATURES = {
                                               C.POINTER(vp), p_i64, p_i64, p_f64, p_i64, vp, i64, vp]),
     "ndmps_chain_tail_columns": (i64, [C.c_int, p_i64]),
     "ndmps_plan_split_offsets": (C.c_int, [vp, i64, p_i64, p_i64]),
+    "ndmps_region_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, i64]),
+    "ndmps_region_contract_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), p_i64, p_i64, vp, i64, i64, vp, vp,
+                                            i64, vp]),
+    "ndmps_region_contract_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), p_i64, p_i64, vp, i64, i64, vp, vp,
+                                            i64, vp]),
     "ndmps_chain_contract_scatter_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, vp, i64, vp]),
     "ndmps_chain_batched_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,

@@ -986,6 +986,130 @@ class NDMPS:
             return recs
         return [r.cpu().numpy() for r in recs]
 
+    # ---------------------------------------------------------------- region decode
+    def _region_values(self, plan):
+        """The plan's output elements (core/region.py) contracted from the cores (ndmps_region_contract_*): a flat
+        device tensor, fp64 for fp64 cores, fp32 otherwise (bf16 cores are upcast as for the overlap)."""
+        torch = _torch()
+        lib = _lib.load()
+        mps = self.mps
+        f64 = mps.dtype == torch.float64
+        keep, ptrs = mps._f64_ptrs() if f64 else mps._f32_ptrs()
+        L = len(mps.cores)
+        dims, bonds = _lib.i64_array(mps.dims), _lib.i64_array(mps.bonds)
+        nodes, tiles = _lib.i64_array(plan.nodes), _lib.i64_array(plan.n_tiles)
+        device = mps.device
+        tables = torch.from_numpy(plan.tables()).to(device)  # every table in one upload
+        ws_bytes = int(lib.ndmps_region_workspace_bytes(L, bonds, nodes, 8 if f64 else 4))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+        out = torch.empty(plan.n_out, dtype=torch.float64 if f64 else torch.float32, device=device)
+        fn = lib.ndmps_region_contract_f64 if f64 else lib.ndmps_region_contract_f32
+        with _span("region"):
+            _lib.check(fn(L, dims, bonds, ptrs, nodes, tiles, tables.data_ptr(), tables.numel(), plan.n_out,
+                          out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()))
+        del keep
+        return out
+
+    def _idct_rows(self, rows, n):
+        """Inverse DCT of the last axis on rows of length n (the region's rows in DCT mode)."""
+        torch = _torch()
+        lib = _lib.load()
+        f64 = rows.dtype == torch.float64
+        rec = torch.empty_like(rows)
+        idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
+        _lib.check(idct(rows.data_ptr(), rec.data_ptr(), rows.numel() // n, n,
+                        _dct_basis(n, rows.device, f64).data_ptr(), _lib.stream_ptr()))
+        return rec
+
+    def _region_result(self, res, as_torch, dtype):
+        """to_tensor's result types: float64 for fp64 cores, float32 otherwise; as_torch with bf16 cores in Std mode
+        gives bf16 like to_tensor's bf16 chain (the NumPy result keeps the fp32 contraction unrounded)."""
+        torch = _torch()
+        if as_torch:
+            if dtype is None and self.mps.dtype == torch.bfloat16 and self.mode == "Std":
+                dtype = torch.bfloat16
+            return res if dtype is None else res.to(dtype)
+        arr = (res if res.dtype == torch.float64 else res.to(torch.float32)).cpu().numpy()
+        return arr[()] if arr.ndim == 0 else arr  # all-int keys give a NumPy scalar, as to_tensor()[i, j, k]
+
+    def decode_region(self, key, as_torch: bool = False, dtype=None):
+        """
+        ``to_tensor(as_torch, dtype)[key]`` without decoding the whole volume.
+
+        ``key`` is a NumPy OUTER index, one entry per axis: an int (negative allowed; drops its axis), a slice (any
+        start / stop / step) or a 1-D integer array or list (unsorted, repeats allowed); one ``Ellipsis`` and missing
+        trailing entries are full slices.  The result, its shape and its dtype are those of ``to_tensor`` indexed with
+        ``np.ix_`` of the per-axis indices.  Only the prefixes of the chain that the region reaches are contracted
+        (core/region.py), so time and memory follow the region, not the volume.
+
+        Raises IndexError (index out of range, too many entries), TypeError (non-integer entries) or ValueError (no
+        known shape) before anything runs on the device; returns None for modes other than Std / DCT, like to_tensor.
+
+        DCT mode stores the last axis in the DCT domain: the last axis is decoded in full for every selected row,
+        transformed back, then indexed.  A region restricted only on the last axis costs a full decode there.
+        """
+        torch = _torch()
+        if self._shape is None:
+            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        from . import region as _region
+
+        shape = tuple(self._shape)
+        idx, keep = _region.normalize_key(key, shape)
+        if self.mode not in ("Std", "DCT"):
+            return None
+        out_shape = [i.size for i, k in zip(idx, keep) if k]
+        device = self.mps.device
+        with torch.cuda.device(device):
+            f64 = self.mps.dtype == torch.float64
+            if any(i.size == 0 for i in idx):
+                res = torch.empty(out_shape, dtype=torch.float64 if f64 else torch.float32, device=device)
+            elif self.mode == "Std":
+                res = self._region_values(_region.plan_outer(shape, idx)).view(out_shape)
+            else:
+                n = shape[-1]
+                rows = self._region_values(_region.plan_outer(shape, idx[:-1] + [np.arange(n, dtype=np.int64)]))
+                rec = self._idct_rows(rows, n).view(-1, n)
+                res = rec.index_select(1, torch.from_numpy(idx[-1]).to(device)).reshape(out_shape)
+        return self._region_result(res, as_torch, dtype)
+
+    def values_at(self, coords, as_torch: bool = False, dtype=None):
+        """
+        ``to_tensor()[tuple(coords.T)]`` for an (N, ndim) integer array of points (negative indices allowed), without
+        decoding the whole volume: an (N,) result of to_tensor's dtype.  Errors as ``decode_region``; in DCT mode every
+        distinct row of the last axis that the points touch is decoded in full.
+        """
+        torch = _torch()
+        if self._shape is None:
+            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        from . import region as _region
+
+        shape = tuple(self._shape)
+        pts = _region.normalize_points(coords, shape)
+        if self.mode not in ("Std", "DCT"):
+            return None
+        N = pts.shape[1]
+        device = self.mps.device
+        with torch.cuda.device(device):
+            f64 = self.mps.dtype == torch.float64
+            if N == 0:
+                res = torch.empty(0, dtype=torch.float64 if f64 else torch.float32, device=device)
+            elif self.mode == "Std":
+                res = self._region_values(_region.plan_points(shape, pts))
+            else:
+                n = shape[-1]
+                if len(shape) > 1:
+                    row_key = np.ravel_multi_index(tuple(pts[:-1]), shape[:-1])
+                    uniq, inv = np.unique(row_key, return_inverse=True)
+                    lead = np.stack(np.unravel_index(uniq, shape[:-1])).astype(np.int64)
+                else:
+                    uniq, inv, lead = np.zeros(1, np.int64), np.zeros(N, np.int64), np.zeros((0, 1), np.int64)
+                full = np.concatenate([np.repeat(lead, n, axis=1), np.tile(np.arange(n, dtype=np.int64), uniq.size)[None]])
+                rows = self._region_values(_region.plan_points(shape, full))
+                rec = self._idct_rows(rows, n).view(-1, n)
+                sel = torch.from_numpy(inv.ravel() * n + pts[-1]).to(device)
+                res = rec.reshape(-1).index_select(0, sel)
+        return self._region_result(res, as_torch, dtype)
+
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):
         """Integer-truncate each MPS tensor to the given unsigned dtype (ndmps.py:182-207)."""

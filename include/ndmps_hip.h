@@ -488,6 +488,25 @@ int ndmps_chain_contract_bf16(int L, const int64_t* h_dims, const int64_t* h_bon
                               int64_t ws_bytes, ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Region decode: replaces to_tensor()[key] (core/ndmps.py:131-153 decodes the whole volume, then indexes).
+ * Left-to-right contraction over the live prefixes of a voxel set only (tables from core/region.py): for each
+ * site s < L-1, h_nodes[s] nodes (a parent index and, through h_tiles[s] tiles (phys, row0, count <= 32) of nodes
+ * that share their physical index, a gathered product with core s); the last site writes d_out[e] for e < n_out.
+ * d_tables (int32, table_len = 2 n_out + sum_s (h_nodes[s] + 3 h_tiles[s])): per level parent[h_nodes[s]] then
+ * the tiles; then leaf_parent[n_out], leaf_phys[n_out].  Entries out of range read zeros, never outside a buffer.
+ * d_ws >= ndmps_region_workspace_bytes(L, bonds, nodes, sizeof element) (0 for L == 1).
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_region_workspace_bytes(int L, const int64_t* h_bonds, const int64_t* h_nodes, int64_t elem_bytes);
+int ndmps_region_contract_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                              const int64_t* h_nodes, const int64_t* h_tiles, const int32_t* d_tables,
+                              int64_t table_len, int64_t n_out, float* d_out, void* d_ws, int64_t ws_bytes,
+                              ndmps_stream_t stream);
+int ndmps_region_contract_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                              const int64_t* h_nodes, const int64_t* h_tiles, const int32_t* d_tables,
+                              int64_t table_len, int64_t n_out, double* d_out, void* d_ws, int64_t ws_bytes,
+                              ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
