@@ -85,6 +85,11 @@ SIGNATURES = {
                                             i64, vp]),
     "ndmps_region_contract_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), p_i64, p_i64, vp, i64, i64, vp, vp,
                                             i64, vp]),
+    "ndmps_pool_workspace_bytes": (i64, [C.c_int, p_i64]),
+    "ndmps_pool_cores": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, p_i64, p_f64, vp, i64,
+                                   C.POINTER(vp), vp, i64, vp]),
+    "ndmps_pool_dct_basis_f32": (C.c_int, [vp, i64, i64, C.c_double, vp]),
+    "ndmps_pool_dct_basis_f64": (C.c_int, [vp, i64, i64, C.c_double, vp]),
     "ndmps_chain_contract_scatter_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, vp, i64, vp]),
     "ndmps_chain_batched_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,

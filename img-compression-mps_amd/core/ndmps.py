@@ -89,12 +89,16 @@ def _torch():
 
 
 class _Plan:
-    """Permutation plan (device offset tables) for one tensor shape."""
+    """Permutation plan (device offset tables) for one tensor shape.  ``factor_arr`` (L, ndim): an explicit factor
+    array whose columns multiply to the shape (the coarse chains of core/pool.py); ``get_factorlist(shape)`` if None."""
 
-    def __init__(self, shape, reverse_sites=False):
+    def __init__(self, shape, reverse_sites=False, factor_arr=None):
         lib = _lib.load()
         self.shape = tuple(int(s) for s in shape)
-        self.factor_arr, _ = _core.get_factorlist(self.shape)
+        if factor_arr is None:
+            self.factor_arr, _ = _core.get_factorlist(self.shape)
+        else:
+            self.factor_arr = np.array(factor_arr, dtype=np.int64)
         self.qubit_size = np.prod(self.factor_arr, axis=1)
         handle = C.c_void_p()
         fa = np.ascontiguousarray(self.factor_arr, dtype=np.int64)
@@ -168,11 +172,14 @@ class _Plan:
 _CACHE_LOCK = threading.Lock()  # concurrent groups (core/batch.py) reach the caches from several host threads
 
 
-def _plan_for(shape, device_index, reverse_sites=False):
+def _plan_for(shape, device_index, reverse_sites=False, factor_arr=None):
     key = (tuple(int(s) for s in shape), device_index) + (("reversed",) if reverse_sites else ())
+    if factor_arr is not None:
+        fa = np.asarray(factor_arr, dtype=np.int64)
+        key = key + (("factors", fa.shape, tuple(int(v) for v in fa.ravel())),)
     with _CACHE_LOCK:
         if key not in _PLAN_CACHE:
-            _PLAN_CACHE[key] = _Plan(shape, reverse_sites)  # plan tables are uploaded with synchronous copies
+            _PLAN_CACHE[key] = _Plan(shape, reverse_sites, factor_arr)  # plan tables are uploaded with synchronous copies
         return _PLAN_CACHE[key]
 
 
@@ -193,6 +200,23 @@ def _dct_basis(n, device, f64=False):
             torch.cuda.current_stream().synchronize()
             _DCT_CACHE[key] = basis
         return _DCT_CACHE[key]
+
+
+_POOL_DCT_CACHE = {}
+
+
+def _pooled_dct_basis(n, block, op, device, f64=False):
+    """(n / block, n) basis that turns DCT coefficient rows into block means (sums) of the voxels: y W^T."""
+    torch = _torch()
+    key = (int(n), int(block), op, str(device), bool(f64))
+    with _CACHE_LOCK:
+        if key not in _POOL_DCT_CACHE:
+            basis = torch.empty((n // block, n), dtype=torch.float64 if f64 else torch.float32, device=device)
+            fill = _lib.load().ndmps_pool_dct_basis_f64 if f64 else _lib.load().ndmps_pool_dct_basis_f32
+            _lib.check(fill(basis.data_ptr(), n, block, 1.0 / block if op == "mean" else 1.0, _lib.stream_ptr()))
+            torch.cuda.current_stream().synchronize()  # shared by every stream from now on
+            _POOL_DCT_CACHE[key] = basis
+        return _POOL_DCT_CACHE[key]
 
 
 class _GroupState:
@@ -1109,6 +1133,179 @@ class NDMPS:
                 sel = torch.from_numpy(inv.ravel() * n + pts[-1]).to(device)
                 res = rec.reshape(-1).index_select(0, sel)
         return self._region_result(res, as_torch, dtype)
+
+    # ------------------------------------------------------------ block-averaged decode
+    def _pool_levels(self, levels):
+        """(factor_arr, normalised levels) for this object's shape; ValueError without one."""
+        if self._shape is None:
+            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        from . import pool as _pool
+
+        fa = _core.get_factorlist(tuple(self._shape))[0]
+        return fa, _pool.normalize_levels(levels, len(self._shape), fa.shape[0])
+
+    def block_shape(self, levels):
+        """Block size ``B_a = prod(factor_arr[L - levels[a]:, a])`` per axis: the voxels that ``downsample(levels)``
+        averages into one value.  ``levels`` is an int in ``[0, L]`` (L = number of sites) or one int per axis.
+        Host only."""
+        from . import pool as _pool
+
+        fa, lev = self._pool_levels(levels)
+        return _pool.block_shape(fa, lev)
+
+    @staticmethod
+    def _rank_safe(cores):
+        """The chain with every bond at most the product of the site dims on either side of it (what ndmps_chain_*
+        require; a reduced chain can have wider bonds): the two sites around a wider bond are contracted into one.
+        The site-order tensor is unchanged."""
+        torch = _torch()
+        lib = _lib.load()
+        dims = [int(c.shape[1]) for c in cores]
+        numel = int(np.prod(dims, dtype=np.int64))
+        out, left = [cores[0]], dims[0]
+        for c in cores[1:]:
+            chi = int(c.shape[0])
+            if chi > left or chi > numel // left:
+                prev = out.pop()
+                m, n = int(prev.shape[0]) * int(prev.shape[1]), int(c.shape[1]) * int(c.shape[2])
+                merged = torch.empty((int(prev.shape[0]), int(prev.shape[1]) * int(c.shape[1]), int(c.shape[2])),
+                                     dtype=c.dtype, device=c.device)
+                gemm = lib.ndmps_dgemm if c.dtype == torch.float64 else lib.ndmps_sgemm
+                _lib.check(gemm(0, 0, m, n, chi, prev.data_ptr(), chi, c.data_ptr(), n, merged.data_ptr(), n,
+                                _lib.stream_ptr()))
+                out.append(merged)
+            else:
+                out.append(c)
+            left *= int(c.shape[1])
+        return out
+
+    def _pooled(self, fa, lev, op):
+        """The volume reduced over the blocks of ``lev`` (core/pool.py) as a device tensor of the plan's out_shape,
+        fp64 for fp64 cores, fp32 otherwise (bf16 cores are reduced and contracted in fp32)."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import pool as _pool
+
+        mps = self.mps
+        plan = _pool.PoolPlan(fa, lev, op, dct=self.mode == "DCT")
+        device = mps.device
+        f64 = mps.dtype == torch.float64
+        work = torch.float64 if f64 else torch.float32
+        code = 2 if f64 else 1 if mps.dtype == torch.bfloat16 else 0
+        L, Lk = plan.L, plan.L_keep
+        bonds = mps.bonds
+        outs = []
+        for l in range(max(Lk, 1)):
+            if Lk == 0:
+                outs.append(torch.empty((1, 1, 1), dtype=work, device=device))
+            elif l == Lk - 1 and Lk < L:
+                outs.append(torch.empty((bonds[l], int(plan.dprime[l]), 1), dtype=work, device=device))
+            elif plan.passthrough[l] and mps.cores[l].dtype == work:
+                outs.append(None)  # nothing reduced: the core itself
+            else:
+                outs.append(torch.empty((bonds[l], int(plan.dprime[l]), bonds[l + 1]), dtype=work, device=device))
+        ptrs = mps._core_ptrs()
+        with torch.cuda.device(device):
+            stream = _lib.stream_ptr()
+            offs = torch.from_numpy(plan.offsets).to(device)  # every site's offsets in one upload
+            ws_bytes = int(lib.ndmps_pool_workspace_bytes(L, _lib.i64_array(bonds))) if Lk < L else 0
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+            out_ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() if o is not None else None for o in outs])
+            with _span("pool"):
+                _lib.check(lib.ndmps_pool_cores(code, L, _lib.i64_array(mps.dims), _lib.i64_array(bonds), ptrs, Lk,
+                                                _lib.i64_array(plan.sites.ravel()), _lib.f64_array(plan.weight),
+                                                offs.data_ptr(), offs.numel(), out_ptrs, ws.data_ptr(), ws_bytes,
+                                                stream))
+            if Lk == 0:
+                res = outs[0].view(plan.coarse_shape)
+            else:
+                cores = self._rank_safe([o if o is not None else mps.cores[l] for l, o in enumerate(outs)])
+                chain = DeviceMPS(cores, _trusted=True)
+                cplan = _plan_for(plan.coarse_shape, device.index or 0, factor_arr=plan.out_factor)
+                cdims = _lib.i64_array(chain.dims)
+                n_tail = int(lib.ndmps_chain_tail_columns(len(cores), cdims)) if not f64 else 0
+                if n_tail > 0:
+                    res = torch.empty(plan.coarse_shape, dtype=torch.float32, device=device)
+                    with _span("chain"):
+                        chain.to_volume(res, n_tail, cplan.split_tables(n_tail, device))
+                else:
+                    with _span("chain"):
+                        dense = chain.to_dense()
+                    res = torch.empty(plan.coarse_shape, dtype=work, device=device)
+                    with _span("decode_permute"):
+                        _lib.check(lib.ndmps_decode_permute(cplan.handle, dense.data_ptr(), res.data_ptr(),
+                                                            dense.element_size(), stream))
+                    del dense
+            if self.mode == "DCT" and lev[-1] < L:
+                n = int(self._shape[-1])
+                rows = res.numel() // n
+                if plan.dct_pool > 1:
+                    # coefficient rows times the pooled basis (n / B, n): about 1 / prod_{a < last} B_a of the
+                    # full decode's transform
+                    nb = n // plan.dct_pool
+                    basis = _pooled_dct_basis(n, plan.dct_pool, op, device, f64)
+                    rec = torch.empty(rows * nb, dtype=work, device=device)
+                    gemm = lib.ndmps_dgemm if f64 else lib.ndmps_sgemm
+                    _lib.check(gemm(0, 1, rows, nb, n, res.data_ptr(), n, basis.data_ptr(), n, rec.data_ptr(), nb,
+                                    stream))
+                    res = rec
+                else:
+                    res = self._idct_rows(res, n)
+        return res.view(plan.out_shape)
+
+    def downsample(self, levels=1, op: str = "mean", as_torch: bool = False, dtype=None):
+        """
+        The volume averaged (``op="mean"``) or summed (``op="sum"``) over blocks of ``block_shape(levels)`` voxels:
+        ``to_tensor()`` reshaped to ``(n0 / B0, B0, n1 / B1, B1, ...)`` and reduced over the odd axes, without
+        decoding the whole volume.  ``levels`` is an int in ``[0, L]`` or one per axis; axis ``a`` is reduced over
+        the digits of its last ``levels[a]`` sites.  ``levels = 0`` equals ``to_tensor()``; ``levels = L`` gives a
+        ``(1, ..., 1)`` array.
+
+        The last sites of the chain carry the finest digits, so the reduction is a site-local sum over the cores
+        (core/pool.py, csrc/pool.hip); only the coarse volume is contracted.  In DCT mode a full reduction of the
+        last axis picks its DC coefficient on the sites; a partial one decodes the coefficient rows of the coarse
+        volume and pools them with one GEMM.
+
+        Result types as ``decode_region``.  Raises TypeError (non-integer levels) or ValueError (levels outside
+        [0, L], wrong count, unknown ``op``, no known shape) before anything runs on the device; returns None for
+        modes other than Std / DCT, like to_tensor.
+        """
+        if op not in ("mean", "sum"):
+            raise ValueError(f"op must be 'mean' or 'sum', got {op!r}")
+        fa, lev = self._pool_levels(levels)
+        if self.mode not in ("Std", "DCT"):
+            return None
+        with _torch().cuda.device(self.mps.device):
+            res = self._pooled(fa, lev, op)
+        return self._region_result(res, as_torch, dtype)
+
+    def _axis_reduce(self, axis, keepdims, op, as_torch, dtype):
+        from . import pool as _pool
+
+        if self._shape is None:
+            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        ndim = len(self._shape)
+        axes = _pool.normalize_axes(axis, ndim)
+        fa = _core.get_factorlist(tuple(self._shape))[0]
+        lev = np.array([fa.shape[0] if a in axes else 0 for a in range(ndim)], dtype=np.int64)
+        if self.mode not in ("Std", "DCT"):
+            return None
+        with _torch().cuda.device(self.mps.device):
+            res = self._pooled(fa, lev, op)
+            if not keepdims:
+                res = res.reshape([n for a, n in enumerate(res.shape) if a not in axes])
+        return self._region_result(res, as_torch, dtype)
+
+    def sum(self, axis=None, keepdims: bool = False, as_torch: bool = False, dtype=None):
+        """``to_tensor().sum(axis=axis, keepdims=keepdims)`` without decoding the whole volume (``downsample`` with
+        every level on the reduced axes).  ``axis``: None, an int or a tuple (negative allowed).  ``axis=None``
+        without keepdims gives a NumPy scalar.  TypeError for non-integer axes, numpy's AxisError out of range,
+        ValueError for a repeated axis or no known shape; None for modes other than Std / DCT."""
+        return self._axis_reduce(axis, keepdims, "sum", as_torch, dtype)
+
+    def mean(self, axis=None, keepdims: bool = False, as_torch: bool = False, dtype=None):
+        """``to_tensor().mean(axis=axis, keepdims=keepdims)`` without decoding the whole volume; as ``sum``."""
+        return self._axis_reduce(axis, keepdims, "mean", as_torch, dtype)
 
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):

@@ -507,6 +507,26 @@ int ndmps_region_contract_f64(int L, const int64_t* h_dims, const int64_t* h_bon
                               ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Block-averaged decode (NDMPS.downsample / sum / mean): no reference counterpart (there: to_tensor(), core/ndmps.py:
+ * 131-153, then a reshape and a mean).  Reduces every site of the chain (tables from core/pool.py):
+ *     out_l[x, q, y] = h_weight[l] * sum_r A_l[x, qoff_l[q] + roff_l[r], y]
+ * h_sites (L x 4): d'_l, n_red_l, start of qoff_l and of roff_l in d_offs (int32, offs_len entries).  Sites l < L_keep
+ * are kept: out_l is a (chi_l, d'_l, chi_{l+1}) core at h_out[l] (NULL: the site is used as it is, nothing written).
+ * Sites l >= L_keep must have d'_l = 1: they are collapsed right to left into a vector that site L_keep - 1 absorbs,
+ * h_out[L_keep - 1] receiving its (chi, d', 1) core; with L_keep == 0, h_out[0] receives the scalar.
+ * dtype: 0 fp32, 1 bf16 (outputs fp32), 2 fp64 (outputs fp64); sums in fp64.  d_ws >= ndmps_pool_workspace_bytes(L,
+ * bonds) when L_keep < L.  Table entries outside a core read nothing.
+ * ndmps_pool_dct_basis_*: d_W (n / block, n) = weight * the orthonormal DCT-II basis (ndmps_dct_basis_*) summed over
+ * blocks of `block` rows; DCT coefficient rows y give the block-pooled voxels y W^T (ndmps_sgemm(0, 1, ...)).
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_pool_workspace_bytes(int L, const int64_t* h_bonds);
+int ndmps_pool_cores(int dtype, int L, const int64_t* h_dims, const int64_t* h_bonds, const void* const* h_cores,
+                     int L_keep, const int64_t* h_sites, const double* h_weight, const int32_t* d_offs,
+                     int64_t offs_len, void* const* h_out, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_pool_dct_basis_f32(float* d_W, int64_t n, int64_t block, double weight, ndmps_stream_t stream);
+int ndmps_pool_dct_basis_f64(double* d_W, int64_t n, int64_t block, double weight, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
