@@ -24,6 +24,8 @@ import contextlib
 import ctypes as C
 import gzip
 import io
+import math
+import numbers
 import os
 import threading
 
@@ -866,6 +868,136 @@ class NDMPS:
                 self.mps.compress_bond_(i, cutoff, max_bond)
         self.update_boundary_list()
         self.update_norm()
+
+    # ------------------------------------------------------- linear combination / rounding (core/lincomb.py)
+    @staticmethod
+    def linear_combination(objs, weights, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
+        """
+        The TT rounding of ``sum_a weights[a] * objs[a]`` as a new object, computed on the cores (csrc/lincomb.hip):
+        its ``to_tensor()`` is ``sum_a w_a * objs[a].to_tensor()`` up to the truncation, and no volume is formed.  In DCT
+        mode the combination is taken on the coefficients (the orthonormal DCT is linear).  No counterpart in the
+        reference.
+
+        Right-to-left TT-SVD of the formal sum chain, the truncation ``from_tensor`` makes: at each bond keep the
+        singular values ``s_j > max(cutoff * s_0, floor * scale)``, ``scale = sum_a |w_a| * objs[a].norm_value`` and
+        the storage floor 1e-6 (fp32 / bf16 work) or 1e-8 (fp64), at most ``max_bond``.  When nothing survives at
+        some bond (or the scale is 0) the result is the zero MPS: every bond 1, zero cores, ``sweep_spectra`` [0.0] per
+        bond.  Sites 1..L-1 of the result are
+        right-isometric and site 0 carries the norm; ``norm=False``; ``sweep_spectra`` holds the kept values.
+
+        dtype: storage of the result; None gives fp64 if any input is fp64 and fp32 otherwise (bf16 inputs are
+        widened in the kernels); torch.bfloat16 rounds the finished fp32 cores once, as ``astype`` does.
+        Raises ValueError for empty or mismatched inputs, a non-finite weight, ``cutoff < 0``, ``max_bond < 1``,
+        objects that differ in qubit_size, shape, mode or device, or a summed bond above 4096.
+        """
+        torch = _torch()
+        lib = _lib.load()
+        from . import lincomb as _lc
+
+        objs = list(objs)
+        for o in objs:
+            if not isinstance(o, NDMPS):
+                raise TypeError(f"linear_combination combines NDMPS objects, not {type(o).__name__}")
+        w = _lc.check_args(len(objs), weights, cutoff, max_bond)
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
+            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
+        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
+                                   dims=o.mps.dims) for o in objs])
+        bond_lists = [o.mps.bonds for o in objs]
+        _lc.check_summed_bonds(bond_lists)
+        codes = [_lc.dtype_code(o.mps.dtype) for o in objs]
+        f64 = dtype == torch.float64 or (dtype != torch.float32 and _lc.work_is_f64(codes))
+        work = torch.float64 if f64 else torch.float32
+        scale = _lc.scale_of(w, [o.norm_value for o in objs])
+        first = objs[0]
+        device = first.mps.device
+        K, L = len(objs), first.mps.L
+        dims = first.mps.dims
+        mb = int(max_bond) if max_bond is not None else 0
+        c_dims = _lib.i64_array(dims)
+        c_bonds = _lib.i64_array([b for bl in bond_lists for b in bl])
+        out_off = (C.c_int64 * (L + 1))()
+        ws_bytes, stride = C.c_int64(0), C.c_int64(0)
+        total = _lib.check(lib.ndmps_lincomb_layout(K, L, c_dims, c_bonds, mb, out_off, C.byref(ws_bytes),
+                                                    C.byref(stride)))
+        ptrs = (C.c_void_p * (K * L))(*[c.data_ptr() for o in objs for c in o.mps.cores])
+        out_bonds = (C.c_int64 * (L + 1))()
+        spectra = np.zeros(L * max(int(stride.value), 1), dtype=np.float64)
+        with torch.cuda.device(device):
+            arena = torch.empty(max(int(total), 1), dtype=work, device=device)
+            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
+            with _span("lincomb"):
+                rc = _lib.check(lib.ndmps_lincomb_round(
+                    K, L, c_dims, c_bonds, (C.c_int * K)(*codes), ptrs, _lib.f64_array(w), float(cutoff), mb,
+                    2 if f64 else 0, scale, arena.data_ptr(), arena.numel(), out_bonds,
+                    spectra.ctypes.data_as(_lib.p_f64), int(stride.value), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            del ws
+        r = [int(v) for v in out_bonds]
+        cores = [arena[out_off[j]: out_off[j] + r[j] * dims[j] * r[j + 1]].view(r[j], dims[j], r[j + 1])
+                 for j in range(L)]
+        if dtype == torch.bfloat16:
+            cores = [c.to(torch.bfloat16) for c in cores]
+        out = NDMPS(DeviceMPS(cores, _trusted=True), first.qubit_size, None, None, False, None, first.mode, first.dim)
+        out._shape = first._shape
+        out._encoding_map = first._encoding_map
+        out.update_boundary_list()
+        out.update_norm()
+        st = int(stride.value)
+        if rc > 0:  # the zero MPS: every bond 1 with the singular value 0
+            out.sweep_spectra = [None] + [np.zeros(1) for _ in range(1, L)]
+        else:
+            out.sweep_spectra = [None] + [spectra[k * st: k * st + r[k]].copy() for k in range(1, L)]
+        return out
+
+    def recompress(self, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
+        """The TT-SVD truncation of this object's own chain as a new object: ``linear_combination([self], [1.0],
+        cutoff, max_bond, dtype)``.  On an exact object ``recompress(max_bond=chi)`` is the truncation
+        ``from_tensor(x, max_bond=chi)`` makes.  ``compress()`` (the reference's left-to-right two-site truncation)
+        is unchanged."""
+        return NDMPS.linear_combination([self], [1.0], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
+
+    def _scaled(self, c: float) -> "NDMPS":
+        """A copy with site 0 multiplied by ``c`` (no rounding; bonds unchanged)."""
+        cores = [t.clone() for t in self.mps.cores]
+        cores[0].mul_(c)
+        out = NDMPS(DeviceMPS(cores, _trusted=True), self.qubit_size, None, None, self.norm, None, self.mode, self.dim)
+        out._shape = self._shape
+        out._encoding_map = self._encoding_map
+        out.update_boundary_list()
+        out.norm_value = abs(c) * float(self.norm_value)
+        spec = self.sweep_spectra
+        if spec is not None:
+            out.sweep_spectra = [None if s is None else abs(c) * np.asarray(s) for s in spec]
+        return out
+
+    @staticmethod
+    def _real_scalar(c):
+        return isinstance(c, numbers.Real) and not isinstance(c, bool) and math.isfinite(float(c))
+
+    def __add__(self, other):
+        if not isinstance(other, NDMPS):
+            return NotImplemented
+        return NDMPS.linear_combination([self, other], [1.0, 1.0])
+
+    def __sub__(self, other):
+        if not isinstance(other, NDMPS):
+            return NotImplemented
+        return NDMPS.linear_combination([self, other], [1.0, -1.0])
+
+    def __neg__(self):
+        return self._scaled(-1.0)
+
+    def __mul__(self, c):
+        if not self._real_scalar(c):
+            return NotImplemented
+        return self._scaled(float(c))
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, c):
+        if not self._real_scalar(c):
+            return NotImplemented
+        return self._scaled(1.0 / float(c))
 
     def continuous_compress(self, cutoff: float, print_ratio: bool = True):
         """Apply compression across a range of 20 cutoff values up to ``cutoff``."""

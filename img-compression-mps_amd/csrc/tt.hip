@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "trunc.h"
 
 namespace {
 
@@ -1384,6 +1385,142 @@ inline int64_t bond_eig_bytes(int64_t chi) {
 }
 }  // namespace
 
+// ------------------------------------------------------------- truncation from two Gram matrices (trunc.h)
+int64_t ndmps::gram_trunc_eig_bytes(int64_t chi) { return bond_eig_bytes(chi); }
+
+template <typename T>
+int ndmps::gram_truncate(const GramTrunc& g, double* Gf, const double* Gd, const T* data, int64_t rows, int64_t rs,
+                         int64_t cs, double cutoff, double floor, double abs_thr, int64_t max_bond, bool f64_tails,
+                         bool cap_decides, int64_t* k_out, double* h_s, hipStream_t s) {
+  const int64_t chi = g.chi, c2 = chi * chi;
+  double *Lt = g.Lt, *tmp = g.tmp, *H = g.H, *V = g.V, *P1 = g.P1, *w2 = g.w2, *wh = g.wh;
+  char* ev_ws = g.ev_ws;
+  const int64_t ev_bytes = g.ev_bytes;
+  int sweeps = 0;
+  // Both decompositions on the direct solver where it applies (every eigenpair of Gf for its square root; of H the
+  // eigenvalues, then only the kept vectors), the block Jacobi otherwise -- and for H whenever the solver's own noise
+  // could move the rank (direct_rank_is_safe).
+  const bool direct = use_direct_full(chi, 1, 0);
+  const int64_t n1[1] = {chi};
+  auto direct_values = [&](const double* M, double* vecs, double* vals) -> int {
+    NDMPS_TRY(ndmps_syevd_topk_values_f64(1, M, c2, n1, vecs, c2, vals, chi, chi, ev_ws, ev_bytes, s));
+    return ndmps_syevd_topk_recover_f64(1, n1, chi, ev_ws, ev_bytes, nullptr, s);
+  };
+  auto direct_vectors = [&](int64_t kv, bool& ok) -> int {  // ok = false: the block lost rank, the caller takes the Jacobi
+    const int64_t k1[1] = {kv};
+    int status = 0;
+    NDMPS_TRY(ndmps_syevd_topk_vectors_f64(1, n1, k1, chi, ev_ws, ev_bytes, &status, s));
+    if (status == 2) return solver_failed(-1, 0, status);
+    ok = status == 0;
+    return NDMPS_OK;
+  };
+  // Square root of Gf: any Lt with Lt Lt^T = Gf serves (H = Lt^T Gd Lt has the singular values squared whatever the
+  // factor, and Lt V_k, Gd Lt V_k do not depend on it).  The Cholesky factor where Gf is numerically positive definite
+  // -- in compress_bond the cores to the right of the bond are isometries until compress() reaches them: Gf = I +
+  // rounding, a chi-fold eigenvalue, the worst case of an eigen-solver and the best of a Cholesky --, else W D^(1/2)
+  // from the eigen-decomposition (zero eigenvalues give zero columns).
+  bool g2_chol = direct && !getenv("NDMPS_COMPRESS_EIG") && ndmps_potrf_scratch_elems(chi) <= 2 * c2;
+  if (g2_chol) {
+    NDMPS_CHECK_HIP(hipMemcpyAsync(Lt, Gf, sizeof(double) * c2, hipMemcpyDeviceToDevice, s));
+    int bad = 0;
+    NDMPS_TRY(ndmps_potrf_lower_f64(Lt, chi, tmp, &bad, s));  // tmp and H (adjacent, 2 c2 doubles) are free until Lt is known
+    g2_chol = bad == 0;
+  }
+  if (!g2_chol) {
+    bool g2_direct = direct;
+    if (g2_direct) {
+      NDMPS_TRY(direct_values(Gf, Lt, w2));
+      NDMPS_TRY(direct_vectors(chi, g2_direct));
+    }
+    if (!g2_direct) NDMPS_TRY(ndmps_syevj_f64(Gf, chi, Lt, w2, ev_ws, ev_bytes, &sweeps, s));
+    // a singular Gf (rank-deficient factor) has eigenvalues of ~kDirectDoubt |Gf| where it has zeros: their square
+    // roots would be columns of ~3e-7 |F| pointing anywhere, spurious singular values
+    hipLaunchKernelGGL(scale_cols_sqrt_kernel, dim3(grid1d(c2)), dim3(256), 0, s, Lt, chi, chi, w2, kDirectDoubt);
+    NDMPS_LAUNCH_CHECK();
+  }
+  NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, Gd, chi, Lt, chi, tmp, chi, s));
+  NDMPS_TRY(ndmps_dgemm(1, 0, chi, chi, chi, Lt, chi, tmp, chi, H, chi, s));
+  std::vector<double> sv(chi);
+  auto fetch = [&]() -> int {
+    NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
+    NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+    return NDMPS_OK;
+  };
+  bool h_direct = direct;
+  if (h_direct) NDMPS_TRY(direct_values(H, V, wh));  // the solver symmetrises its copy of H
+  else NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));  // symmetrises H on entry
+  NDMPS_TRY(fetch());
+  // the relative threshold; an absolute one (abs_thr >= 0, 0 included) raises it, or leaves nothing to keep
+  double c = std::max(cutoff, floor);
+  if (abs_thr >= 0.0) {
+    const double s0 = sqrt(std::max(sv[0], 0.0));
+    if (!(s0 > abs_thr)) {
+      for (auto& x : sv) x = sqrt(std::max(x, 0.0));
+      if (h_s) memcpy(h_s, sv.data(), chi * sizeof(double));
+      *k_out = 0;
+      return NDMPS_OK;
+    }
+    c = std::max(c, abs_thr / s0);
+  }
+  const int64_t limit = max_bond > 0 ? std::min(max_bond, chi) : chi;
+  // cap_decides: a rank fixed by the cap -- `limit` eigenvalues clearly above the threshold -- needs no decision there
+  bool safe = direct_rank_is_safe(sv.data(), chi, c);
+  if (!safe && cap_decides && limit < chi) {
+    const double clear = c * c * sv[0] + kDirectDoubt * fabs(sv[0]);
+    safe = sv[limit - 1] > clear;
+  }
+  if (h_direct && !safe) {
+    h_direct = false;
+    NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));
+    NDMPS_TRY(fetch());
+  }
+  // fp64 cores: H carries s^2, so a zero comes back at ~sqrt(n u) s_0 -- on kCutoffFloorF64 itself -- and the eigenvalues
+  // in doubt (direct_doubt_from) cannot decide the rank.  Those below the cap are measured directly, s_j = |data Lt v_j|
+  // (H = (data Lt)^T (data Lt)), whose noise is ~u |data| |Lt|, as sweep_impl measures its tail norms; they replace the
+  // squared values in the rank and in the caller's scalings.  fp32 and bf16 cores: the floor (1e-6) is far above the noise.
+  // (k is 1 whatever the values when at most one may be kept; from chi = 2 on, one row block fits H: 2 t <= chi^2)
+  if (f64_tails && limit > 1 && direct_doubt_from(sv.data(), chi, c) < limit) {
+    if (h_direct) {  // every vector is needed: the Jacobi computes them all (same spectrum)
+      NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));
+      NDMPS_TRY(fetch());
+      h_direct = false;
+    }
+    const int64_t i0 = direct_doubt_from(sv.data(), chi, c), t = chi - i0;
+    if (i0 < limit) {
+      NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, Lt, chi, V, chi, P1, chi, s));  // Lt V
+      // partials (nblk x t) and sums (t) in H, free now: fewer blocks of more rows when ceil(rows / 4) do not fit
+      int nblk = (int)ceil_div(rows, 4);
+      if ((int64_t)nblk * t + t > c2) nblk = (int)((c2 - t) / t);
+      NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= c2, "internal: no room for the tail norms (%lld x %lld)",
+                    (long long)nblk, (long long)t);
+      double* out = H + (int64_t)nblk * t;
+      hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
+                         data, rs, cs, (int)rows, (int)chi, (const double*)P1, (int)chi, (int)i0, (int)t, H);
+      hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, H, nblk, (int)t, out);
+      NDMPS_LAUNCH_CHECK();
+      NDMPS_CHECK_HIP(hipMemcpyAsync(wh + i0, out, t * sizeof(double), hipMemcpyDeviceToDevice, s));
+      NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data() + i0, out, t * sizeof(double), hipMemcpyDeviceToHost, s));
+      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+    }
+  }
+  for (auto& x : sv) x = sqrt(std::max(x, 0.0));  // eigenvalues of H are s^2 (measured |data Lt v_j|^2 in doubt)
+  const int64_t k = kept_rank(sv, c, max_bond, floor);
+  if (h_direct) {
+    NDMPS_TRY(direct_vectors(k, h_direct));
+    if (!h_direct) NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));  // same spectrum, same k
+  }
+  if (h_s) memcpy(h_s, sv.data(), chi * sizeof(double));
+  *k_out = k;
+  hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(grid1d(chi)), dim3(256), 0, s, wh, chi, g.sig);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
+template int ndmps::gram_truncate<float>(const GramTrunc&, double*, const double*, const float*, int64_t, int64_t,
+                                         int64_t, double, double, double, int64_t, bool, bool, int64_t*, double*, hipStream_t);
+template int ndmps::gram_truncate<double>(const GramTrunc&, double*, const double*, const double*, int64_t, int64_t,
+                                          int64_t, double, double, double, int64_t, bool, bool, int64_t*, double*, hipStream_t);
+
+
 extern "C" int64_t ndmps_compress_bond_workspace_bytes(int64_t chi_l, int64_t d1, int64_t chi, int64_t d2,
                                                        int64_t chi_r) {
   if (chi_l <= 0 || d1 <= 0 || chi <= 0 || d2 <= 0 || chi_r <= 0) return 0;
@@ -1450,109 +1587,16 @@ int compress_bond_impl(const T* d_t1, const T* d_t2, int64_t chi_l, int64_t d1, 
                     gram_ws,
                 "workspace carve failed");
 
-  int sweeps = 0;
   NDMPS_TRY(gram_T(d_t1, m1, chi, chi, G1, gram_ws, gram_bytes, s));
   hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(chi * n2)), dim3(256), 0, s, d_t2, chi * n2, t2d);
   NDMPS_LAUNCH_CHECK();
   NDMPS_TRY(ndmps_dgemm(0, 1, chi, chi, n2, t2d, n2, t2d, n2, G2, chi, s));
-  // Both decompositions on the direct solver where it applies (every eigenpair of G2 for its square root; of H the
-  // eigenvalues, then only the kept vectors), the block Jacobi otherwise -- and for H whenever the solver's own noise
-  // could move the rank (direct_rank_is_safe).
-  const bool direct = use_direct_full(chi, 1, 0);
-  const int64_t n1[1] = {chi};
-  auto direct_values = [&](const double* M, double* vecs, double* vals) -> int {
-    NDMPS_TRY(ndmps_syevd_topk_values_f64(1, M, c2, n1, vecs, c2, vals, chi, chi, ev_ws, ev_bytes, s));
-    return ndmps_syevd_topk_recover_f64(1, n1, chi, ev_ws, ev_bytes, nullptr, s);
-  };
-  auto direct_vectors = [&](int64_t kv, bool& ok) -> int {  // ok = false: the block lost rank, the caller takes the Jacobi
-    const int64_t k1[1] = {kv};
-    int status = 0;
-    NDMPS_TRY(ndmps_syevd_topk_vectors_f64(1, n1, k1, chi, ev_ws, ev_bytes, &status, s));
-    if (status == 2) return solver_failed(-1, 0, status);
-    ok = status == 0;
-    return NDMPS_OK;
-  };
-  // Square root of G2: any Lt with Lt Lt^T = G2 serves (H = Lt^T G1 Lt has the singular values squared whatever the
-  // factor, and Lt V_k, G1 Lt V_k do not depend on it).  The Cholesky factor where G2 is numerically positive definite
-  // -- the cores to the right of the bond are isometries until compress() reaches them: G2 = I + rounding, a
-  // chi-fold eigenvalue, the worst case of an eigen-solver and the best of a Cholesky --, else W D^(1/2) from the
-  // eigen-decomposition (zero eigenvalues give zero columns).
-  bool g2_chol = direct && !getenv("NDMPS_COMPRESS_EIG") && ndmps_potrf_scratch_elems(chi) <= 2 * c2;
-  if (g2_chol) {
-    NDMPS_CHECK_HIP(hipMemcpyAsync(Lt, G2, sizeof(double) * c2, hipMemcpyDeviceToDevice, s));
-    int bad = 0;
-    NDMPS_TRY(ndmps_potrf_lower_f64(Lt, chi, tmp, &bad, s));  // tmp and H (adjacent, 2 c2 doubles) are free until Lt is known
-    g2_chol = bad == 0;
-  }
-  if (!g2_chol) {
-    bool g2_direct = direct;
-    if (g2_direct) {
-      NDMPS_TRY(direct_values(G2, Lt, w2));
-      NDMPS_TRY(direct_vectors(chi, g2_direct));
-    }
-    if (!g2_direct) NDMPS_TRY(ndmps_syevj_f64(G2, chi, Lt, w2, ev_ws, ev_bytes, &sweeps, s));
-    // a singular G2 (rank-deficient T2) has eigenvalues of ~kDirectDoubt |G2| where it has zeros: their square roots
-    // would be columns of ~3e-7 |T2| pointing anywhere, spurious singular values of T1 Lt
-    hipLaunchKernelGGL(scale_cols_sqrt_kernel, dim3(grid1d(c2)), dim3(256), 0, s, Lt, chi, chi, w2, kDirectDoubt);
-    NDMPS_LAUNCH_CHECK();
-  }
-  NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, G1, chi, Lt, chi, tmp, chi, s));
-  NDMPS_TRY(ndmps_dgemm(1, 0, chi, chi, chi, Lt, chi, tmp, chi, H, chi, s));
-  std::vector<double> sv(chi);
-  bool h_direct = direct;
-  if (h_direct) {
-    NDMPS_TRY(direct_values(H, V, wh));  // the solver symmetrises its copy of H
-    NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
-    NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-    h_direct = direct_rank_is_safe(sv.data(), chi, std::max(cutoff, cutoff_floor<T>()));
-  }
-  if (!h_direct) {
-    NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));  // symmetrises H on entry
-    NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
-    NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-  }
-  // fp64 cores: H carries s^2, so a zero comes back at ~sqrt(n u) s_0 -- on kCutoffFloorF64 itself -- and the eigenvalues
-  // in doubt (direct_doubt_from) cannot decide the rank.  Those below the cap are measured directly, s_j = |T1 Lt v_j|
-  // (H = (T1 Lt)^T (T1 Lt)), whose noise is ~u |T1| |Lt|, as sweep_impl measures its tail norms; they replace the squared
-  // values in the rank and in the s^-1/2, s^-3/2 scalings.  fp32 and bf16 cores: the floor (1e-6) is far above the noise.
-  // (k is 1 whatever the values when at most one may be kept; from chi = 2 on, one row block fits H: 2 t <= chi^2)
-  const int64_t limit = max_bond > 0 ? std::min(max_bond, chi) : chi;
-  if (sizeof(T) == 8 && limit > 1 && direct_doubt_from(sv.data(), chi, std::max(cutoff, cutoff_floor<T>())) < limit) {
-    if (h_direct) {  // every vector is needed: the Jacobi computes them all (same spectrum)
-      NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));
-      NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data(), wh, chi * sizeof(double), hipMemcpyDeviceToHost, s));
-      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-      h_direct = false;
-    }
-    const int64_t i0 = direct_doubt_from(sv.data(), chi, std::max(cutoff, cutoff_floor<T>())), t = chi - i0;
-    if (i0 < limit) {
-      NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, Lt, chi, V, chi, P1, chi, s));  // Lt V; P1 is rewritten below
-      // partials (nblk x t) and sums (t) in H, free now: fewer blocks of more rows when ceil(m1 / 4) do not fit
-      int nblk = (int)ceil_div(m1, 4);
-      if ((int64_t)nblk * t + t > c2) nblk = (int)((c2 - t) / t);
-      NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= c2, "internal: no room for the tail norms (%lld x %lld)",
-                    (long long)nblk, (long long)t);
-      double* out = H + (int64_t)nblk * t;
-      hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
-                         d_t1, chi, (int64_t)1, (int)m1, (int)chi, (const double*)P1, (int)chi, (int)i0, (int)t, H);
-      hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, H, nblk, (int)t, out);
-      NDMPS_LAUNCH_CHECK();
-      NDMPS_CHECK_HIP(hipMemcpyAsync(wh + i0, out, t * sizeof(double), hipMemcpyDeviceToDevice, s));
-      NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data() + i0, out, t * sizeof(double), hipMemcpyDeviceToHost, s));
-      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-    }
-  }
-  for (auto& x : sv) x = sqrt(std::max(x, 0.0));  // eigenvalues of H are s^2 (measured |T1 Lt v_j|^2 in doubt)
-  const int64_t k = kept_rank(sv, cutoff, max_bond, cutoff_floor<T>());
-  if (h_direct) {
-    NDMPS_TRY(direct_vectors(k, h_direct));
-    if (!h_direct) NDMPS_TRY(ndmps_syevj_f64(H, chi, V, wh, ev_ws, ev_bytes, &sweeps, s));  // same spectrum, same k
-  }
-  if (h_s) memcpy(h_s, sv.data(), chi * sizeof(double));
+  // G2 = T2 T2^T is the square-rooted metric, G1 = T1^T T1 the data Gram; tail norms measured on the rows of T1
+  const ndmps::GramTrunc g{chi, Lt, tmp, H, V, P1, w2, wh, sig, ev_ws, ev_bytes};
+  int64_t k = 0;
+  NDMPS_TRY(ndmps::gram_truncate<T>(g, G2, G1, d_t1, m1, chi, 1, cutoff, cutoff_floor<T>(), -1.0, max_bond, sizeof(T) == 8,
+                                    false, &k, h_s, s));
   *h_new_chi = k;
-
-  hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(grid1d(chi)), dim3(256), 0, s, wh, chi, sig);
-  NDMPS_LAUNCH_CHECK();
   NDMPS_TRY(ndmps_dgemm(0, 0, chi, k, chi, Lt, chi, V, chi, P1, k, s));
   NDMPS_TRY(ndmps_dgemm(0, 0, chi, k, chi, tmp, chi, V, chi, P2, k, s));
   hipLaunchKernelGGL(scale_cols_to_f32_kernel<T>, dim3(grid1d(chi * k)), dim3(256), 0, s, P1, chi, k, k, sig, -0.5, A1);

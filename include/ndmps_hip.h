@@ -527,6 +527,26 @@ int ndmps_pool_dct_basis_f32(float* d_W, int64_t n, int64_t block, double weight
 int ndmps_pool_dct_basis_f64(double* d_W, int64_t n, int64_t block, double weight, ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Linear combination (no reference counterpart; core/lincomb.py): the TT-SVD rounding of sum_a w_a X^a for K
+ * chains with the same L site dims, right to left, from pair-batched left Gram matrices (csrc/lincomb.hip).
+ * h_bonds: K x (L + 1) (row a = input a's bonds, outer bonds 1); h_codes: K storage codes (0 fp32, 1 bf16, 2 fp64);
+ * h_cores: K x L device pointers (row a = input a's cores).  Every summed bond sum_a chi_{a,k} must be <= 4096.
+ * ndmps_lincomb_layout: returns the output arena's element count; h_out_off (L + 1): site j's core starts at element
+ * h_out_off[j] (a prefix of its slot is used); *h_ws_bytes: workspace; *h_spec_stride: row stride of h_spectra.
+ * ndmps_lincomb_round: out_code 0 fp32 or 2 fp64 cores into d_out; h_out_bonds (L + 1) the new bonds; h_spectra
+ * (L x spec_stride doubles) row k = the kept singular values at bond k.  Keeps s_j > max(cutoff s_0, floor scale)
+ * (floor 1e-6 for fp32 output, 1e-8 for fp64), at most max_bond (<= 0: none).  Returns 1 when nothing survives at
+ * some bond, or scale is 0: the zero MPS (every bond 1, zero cores, a kept value of 0 per bond).  Synchronises the
+ * stream.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_lincomb_layout(int K, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t max_bond,
+                             int64_t* h_out_off, int64_t* h_ws_bytes, int64_t* h_spec_stride);
+int ndmps_lincomb_round(int K, int L, const int64_t* h_dims, const int64_t* h_bonds, const int* h_codes,
+                        const void* const* h_cores, const double* h_weights, double cutoff, int64_t max_bond, int out_code,
+                        double scale, void* d_out, int64_t out_elems, int64_t* h_out_bonds, double* h_spectra,
+                        int64_t spec_stride, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
