@@ -259,22 +259,28 @@ void carve(const Plan& p, Arena& ar, Buffers& b) {
   b.g.ev_ws = ar.take<char>(b.g.ev_bytes);
 }
 
+// tasks [first, first + count) of the table, one per blockIdx.y, in launches of at most kMaxTasksPerLaunch tasks
+// (gridDim.y <= 65535): K inputs give K (K + 1) / 2 pair tasks, above 65535 from K = 362 on
+constexpr int64_t kMaxTasksPerLaunch = 65535;
+
 int launch_tasks(const Task* d_tasks, const std::vector<Task>& h, int64_t first, int64_t count, bool proj,
                  const double* Pbase, double* Cbase, int64_t r, hipStream_t s) {
-  if (count <= 0) return NDMPS_OK;
-  int64_t tiles = 1;
-  for (int64_t i = first; i < first + count; ++i) {
-    const int64_t n = proj ? r : h[i].N;
-    tiles = std::max(tiles, ceil_div(h[i].M, kTile) * ceil_div(n, kTile));
+  for (int64_t c0 = first; c0 < first + count; c0 += kMaxTasksPerLaunch) {
+    const int64_t n_tasks = std::min(kMaxTasksPerLaunch, first + count - c0);
+    int64_t tiles = 1;
+    for (int64_t i = c0; i < c0 + n_tasks; ++i) {
+      const int64_t n = proj ? r : h[i].N;
+      tiles = std::max(tiles, ceil_div(h[i].M, kTile) * ceil_div(n, kTile));
+    }
+    NDMPS_REQUIRE(tiles <= INT32_MAX, "internal: ragged launch too large");
+    if (proj)
+      hipLaunchKernelGGL(ragged_gemm_kernel<true>, dim3((unsigned)tiles, (unsigned)n_tasks), dim3(256), 0, s,
+                         d_tasks + c0, (int)n_tasks, Pbase, Cbase, r);
+    else
+      hipLaunchKernelGGL(ragged_gemm_kernel<false>, dim3((unsigned)tiles, (unsigned)n_tasks), dim3(256), 0, s,
+                         d_tasks + c0, (int)n_tasks, (const double*)nullptr, (double*)nullptr, (int64_t)0);
+    NDMPS_LAUNCH_CHECK();
   }
-  NDMPS_REQUIRE(count <= 65535 && tiles <= INT32_MAX, "internal: ragged launch too large");
-  if (proj)
-    hipLaunchKernelGGL(ragged_gemm_kernel<true>, dim3((unsigned)tiles, (unsigned)count), dim3(256), 0, s, d_tasks + first,
-                       (int)count, Pbase, Cbase, r);
-  else
-    hipLaunchKernelGGL(ragged_gemm_kernel<false>, dim3((unsigned)tiles, (unsigned)count), dim3(256), 0, s,
-                       d_tasks + first, (int)count, (const double*)nullptr, (double*)nullptr, (int64_t)0);
-  NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
 

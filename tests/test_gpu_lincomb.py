@@ -130,6 +130,8 @@ def _check_tt_svd(r, objs, w, cutoff, max_bond, storage):
     err = np.linalg.norm(_site_dense(r) - S)
     ref_err = np.linalg.norm(mps_to_dense(ref) - S)
     assert err <= (1 + 1e-3) * ref_err + _tol(storage) * _scale(objs, w)
+    # what was measured, for callers that add bars of their own (tests/test_gpu_lincomb_scale.py)
+    return dict(S=S, spec=spec, ref_bonds=ref_b, err=err, ref_err=ref_err, slack=_tol(storage) * _scale(objs, w))
 
 
 @pytest.mark.parametrize("kw", [dict(cutoff=1e-3), dict(cutoff=1e-2), dict(max_bond=4), dict(max_bond=12)],

@@ -179,3 +179,15 @@ def test_rank_rule():
     assert lc.floor_for(True) == 1e-8 and lc.floor_for(False) == 1e-6
     assert lc.dtype_code("torch.bfloat16") == 1
     assert lc.work_is_f64([0, 1, 2]) and not lc.work_is_f64([0, 1])
+
+
+@pytest.mark.parametrize("K", [361, 362, 400, 4096])
+def test_many_inputs_pass_validation(K):
+    """K (K + 1) / 2 pair tasks exceed one launch's 65535 from K = 362 on; the host accepts such K whenever the summed
+    bond stays within MAX_SUMMED_BOND (csrc/lincomb.hip issues the pair tasks in launches of at most 65535)."""
+    assert K * (K + 1) // 2 > 65535 or K == 361
+    w = lc.check_args(K, [1.0 / K] * K, 0.0, None)
+    assert len(w) == K
+    bonds = [[1] + [1 + a % 2 if K <= 2048 else 1] * 4 + [1] for a in range(K)]
+    lc.check_summed_bonds(bonds)
+    assert max(lc.summed_bonds(bonds)) <= lc.MAX_SUMMED_BOND
