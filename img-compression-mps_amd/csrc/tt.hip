@@ -1747,6 +1747,14 @@ int chain_impl(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* co
     return NDMPS_OK;
   }
   const ChainPlan p = chain_plan(L, h_dims, h_bonds);
+  if (scatter) {
+    // refused before the first launch: the cumulative products below may already write d_dense
+    int64_t tail_cols = 1;
+    for (int i = p.j0; i < L; ++i) tail_cols *= h_dims[i];
+    NDMPS_REQUIRE(p.j0 < L && scatter->n_cols == tail_cols,
+                  "scatter tables are for %lld tail columns, the chain's tail has %lld", (long long)scatter->n_cols,
+                  (long long)(p.j0 < L ? tail_cols : 0));
+  }
   T* ws_left = (T*)d_ws;
   T* ws_tail[2] = {ws_left + ndmps::round_up(p.left_elems, 64),
                    ws_left + ndmps::round_up(p.left_elems, 64) + ndmps::round_up(p.tail_elems, 64)};
@@ -1784,10 +1792,6 @@ int chain_impl(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* co
     left = out;
     rows *= h_dims[i];
   }
-  if (scatter)
-    NDMPS_REQUIRE(j0 < L && L >= 2 && scatter->n_cols == n_tail,
-                  "scatter tables are for %lld tail columns, the chain's tail has %lld", (long long)scatter->n_cols,
-                  (long long)(j0 < L ? n_tail : 0));
   if (j0 < L) {
     // R sits in one tail buffer (or is the last core itself); the other one is free for its reordered copy
     T* spare = (R == ws_tail[0]) ? ws_tail[1] : ws_tail[0];
@@ -1856,6 +1860,13 @@ int chain_batched_same_bonds(int count, int L, const int64_t* h_dims, const int6
   const ChainPlan p = chain_plan(L, h_dims, h_bonds);
   const int j0 = p.j0;
   NDMPS_REQUIRE(L >= 2 && j0 < L, "internal: batched chain needs a pre-contracted tail");
+  {
+    // refused before the first launch: the cumulative products below may already write h_out
+    int64_t tail_cols = 1;
+    for (int i = j0; i < L; ++i) tail_cols *= h_dims[i];
+    NDMPS_REQUIRE(sc.n_cols == tail_cols, "scatter tables are for %lld tail columns, the chain's tail has %lld",
+                  (long long)sc.n_cols, (long long)tail_cols);
+  }
   std::vector<const float*> A(count), B(count);
   std::vector<float*> Cc(count);
   std::vector<float*> ws_left(count), ws_tail0(count), ws_tail1(count);
@@ -1898,8 +1909,6 @@ int chain_batched_same_bonds(int count, int L, const int64_t* h_dims, const int6
     for (int b = 0; b < count; ++b) left[b] = Cc[b];
     rows *= h_dims[i];
   }
-  NDMPS_REQUIRE(sc.n_cols == n_tail, "scatter tables are for %lld tail columns, the chain's tail has %lld",
-                (long long)sc.n_cols, (long long)n_tail);
   // ---- final product: columns of R in memory order, every element straight to its voxel
   PtrPairs pp;
   for (int b = 0; b < count; ++b) {
