@@ -16,6 +16,7 @@ reference switches over); their bodies are this repo's own.  The reference's dat
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Sequence
 
@@ -39,11 +40,10 @@ def conv_to_mps(tensor_list: Sequence, mode: str = "DCT", norm: bool = False, ma
     chunk as a stream (``NDMPS.from_tensors_begin`` on three alternating streams: the objects of a chunk are built while the
     next ones run) -- results equal ``from_tensor`` on each up to the rounding of the fp64 eigen-solver, the order of the
     list is kept.  Lists of mixed shapes keep the loop."""
-    import numpy as np
-
-    from .ndmps import NDMPS
+    import torch
 
     from .. import _lib
+    from .ndmps import NDMPS, _plan_for
 
     _lib.require_device()  # the product never computes on the CPU: the same loud failure as from_tensor
     tensor_list = list(tensor_list)
@@ -51,15 +51,11 @@ def conv_to_mps(tensor_list: Sequence, mode: str = "DCT", norm: bool = False, ma
     if len(tensor_list) < 2 or len(shapes) != 1 or () in shapes:
         return [NDMPS.from_tensor(t, norm=norm, mode=mode, max_bond=max_bond, cutoff=cutoff, device=device)
                 for t in tensor_list]
-    import torch
-
     shape = next(iter(shapes))
     numel = int(np.prod(shape))
     chunk = int(max(1, min(64, (8 << 30) // (4 * numel))))  # at most 8 GiB of fp32 volumes in a chunk
     # ... and a sweep workspace of at most 24 GiB: an exact sweep (no bond cap, the reference's default) solves eigenproblems
     # of the full bond dimensions -- order 4096 in the middle of a 256^3 volume -- and asks for gigabytes per volume
-    from .ndmps import _plan_for
-
     lib = _lib.load()
     dims = [int(q) for q in _plan_for(tuple(int(v) for v in shape), torch.cuda.current_device()).qubit_size]
     per_volume = int(lib.ndmps_tt_sweep_batched_workspace_bytes(1, len(dims), _lib.i64_array(dims), int(max_bond or 0)))
@@ -67,14 +63,11 @@ def conv_to_mps(tensor_list: Sequence, mode: str = "DCT", norm: bool = False, ma
         chunk = int(max(1, min(chunk, (24 << 30) // per_volume)))
     _, lanes = default_stream_shape(chunk)
     streams = group_streams(lanes)
-    main = torch.cuda.current_stream()
-    ready = torch.cuda.Event()
-    ready.record(main)
+    fork = _Fork()
     out, in_flight = [], []
     for k, i0 in enumerate(range(0, len(tensor_list), chunk)):
         stream = streams[k % lanes]
-        with torch.cuda.stream(stream):
-            stream.wait_event(ready)  # inputs produced on the caller's stream
+        with fork.on(stream):
             in_flight.append((NDMPS.from_tensors_begin(tensor_list[i0:i0 + chunk], norm=norm, mode=mode, max_bond=max_bond,
                                                        cutoff=cutoff, device=device), stream))
         while len(in_flight) > lanes:
@@ -149,6 +142,38 @@ def group_streams(n: int):
     return _group_streams[key]
 
 
+def _group_pool(n: int):
+    """The long-lived pool of ``n`` host threads: the solver keeps per-thread pinned flags and events
+    (csrc/eig_block.hip), a fresh pool per call would allocate them again every time."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    pool = _group_pools.get(n)
+    if pool is None:
+        pool = _group_pools.setdefault(n, ThreadPoolExecutor(n, thread_name_prefix="ndmps-group"))
+    return pool
+
+
+class _Fork:
+    """Work forked from the caller's stream onto other streams (and host threads): an event is recorded on the caller's
+    stream here, and ``on(stream)`` makes ``stream`` current on the calling thread, on the caller's device, behind it."""
+
+    def __init__(self):
+        import torch
+
+        self.device_index = torch.cuda.current_device()
+        self.ready = torch.cuda.Event()
+        self.ready.record(torch.cuda.current_stream())
+
+    @contextlib.contextmanager
+    def on(self, stream):
+        import torch
+
+        torch.cuda.set_device(self.device_index)  # pool threads start on device 0
+        with torch.cuda.stream(stream):
+            stream.wait_event(self.ready)  # inputs produced on the caller's stream
+            yield
+
+
 def encode_decode_concurrent(tensor_list: Sequence, groups: int = None, mode: str = "Std", norm: bool = False,
                              max_bond=None, cutoff: float = 1e-10, reconstruct: bool = True, pool=None,
                              wait: bool = True):
@@ -162,34 +187,22 @@ def encode_decode_concurrent(tensor_list: Sequence, groups: int = None, mode: st
     still being written on the groups' streams when the call returns (the NDMPS objects are complete) and the
     caller synchronises the device before reading them; a following call queues behind them on the same
     streams, so consecutive batches run back to back without the host in between."""
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-
     from .ndmps import NDMPS
 
     tensor_list = list(tensor_list)
     if groups is None:
         groups = default_groups(len(tensor_list))
     parts = _split(len(tensor_list), groups)
-    main = torch.cuda.current_stream()
-    ready = torch.cuda.Event()
-    ready.record(main)
-
-    device_index = torch.cuda.current_device()
+    fork = _Fork()
     streams = group_streams(len(parts))
 
     def work(slot):
         idx = parts[slot]
-        torch.cuda.set_device(device_index)  # pool threads start on device 0
         stream = streams[slot]
-        with torch.cuda.stream(stream):
-            stream.wait_event(ready)  # inputs produced on the caller's stream
-            if reconstruct:
-                objs, recs = NDMPS.from_tensors([tensor_list[i] for i in idx], norm=norm, mode=mode, max_bond=max_bond,
-                                                cutoff=cutoff, reconstruct=True)
-            else:
-                objs, recs = NDMPS.from_tensors([tensor_list[i] for i in idx], norm=norm, mode=mode,
-                                                max_bond=max_bond, cutoff=cutoff), None
+        with fork.on(stream):
+            res = NDMPS.from_tensors([tensor_list[i] for i in idx], norm=norm, mode=mode, max_bond=max_bond,
+                                     cutoff=cutoff, reconstruct=reconstruct)
+            objs, recs = res if reconstruct else (res, None)
         # host-side completion: a device-side wait on the caller's stream would sit in whichever
         # hardware queue that stream shares with a group and hold that group's next launches behind it
         if wait:
@@ -197,11 +210,7 @@ def encode_decode_concurrent(tensor_list: Sequence, groups: int = None, mode: st
         return objs, recs
 
     if pool is None:
-        # long-lived workers: the solver keeps per-thread pinned flags and events (csrc/eig_block.hip),
-        # a fresh pool per call would allocate them again every time
-        pool = _group_pools.get(len(parts))
-        if pool is None:
-            pool = _group_pools.setdefault(len(parts), ThreadPoolExecutor(len(parts), thread_name_prefix="ndmps-group"))
+        pool = _group_pool(len(parts))
     results = list(pool.map(work, range(len(parts))))
     objs, recs = [], []
     for o, r in results:
@@ -246,9 +255,6 @@ def encode_decode_begin(tensor_list: Sequence, groups: int = None, mode: str = "
     take 32-column blocks then (ndmps_syevd_topk_set_streamed): equal up to the last bits of the fp64 eigen-solver.
     ``lane`` / ``lanes``: a stream of SMALL batches (one group each) may alternate between ``lanes`` sets of streams --
     batch k on lane k mod lanes -- so that consecutive batches overlap on the GPU the way two groups of one batch do."""
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-
     from .. import _lib
     from .ndmps import NDMPS
 
@@ -256,32 +262,25 @@ def encode_decode_begin(tensor_list: Sequence, groups: int = None, mode: str = "
     if groups is None:
         groups = default_groups(len(tensor_list))
     parts = _split(len(tensor_list), groups)
-    main = torch.cuda.current_stream()
-    ready = torch.cuda.Event()
-    ready.record(main)
-    device_index = torch.cuda.current_device()
+    fork = _Fork()
     lanes = max(1, int(lanes))
     streams = group_streams(len(parts) * lanes)[(int(lane) % lanes) * len(parts):]
 
     def work(slot):
         idx = parts[slot]
-        torch.cuda.set_device(device_index)  # pool threads start on device 0
         lib = _lib.load()
-        # several lanes: this batch shares the GPU with its neighbours -- the solver then sizes small batches' resident
-        # launches for overlap, not for the latency of one batch (per host thread; restored behind the call)
-        was = lib.ndmps_syevd_topk_set_streamed(1 if lanes > 1 else 0)
-        try:
-            with torch.cuda.stream(streams[slot]):
-                streams[slot].wait_event(ready)  # inputs produced on the caller's stream
+        with fork.on(streams[slot]):
+            # several lanes: this batch shares the GPU with its neighbours -- the solver then sizes small batches' resident
+            # launches for overlap, not for the latency of one batch (per host thread; restored behind the call)
+            was = lib.ndmps_syevd_topk_set_streamed(1 if lanes > 1 else 0)
+            try:
                 return NDMPS.from_tensors_begin([tensor_list[i] for i in idx], norm=norm, mode=mode, max_bond=max_bond,
                                                 cutoff=cutoff, reconstruct=reconstruct)
-        finally:
-            lib.ndmps_syevd_topk_set_streamed(was)
+            finally:
+                lib.ndmps_syevd_topk_set_streamed(was)
 
     if pool is None:
-        pool = _group_pools.get(len(parts))
-        if pool is None:
-            pool = _group_pools.setdefault(len(parts), ThreadPoolExecutor(len(parts), thread_name_prefix="ndmps-group"))
+        pool = _group_pool(len(parts))
     return PendingBatch(list(pool.map(work, range(len(parts)))), reconstruct)
 
 
@@ -323,28 +322,17 @@ def _map_on_lanes(fn, items, lanes: int = 3):
     lanes = min(int(lanes), len(items))
     if lanes < 2 or os.environ.get("NDMPS_LIST_SERIAL") or os.environ.get("NDMPS_COMPRESS_LIST_SERIAL"):
         return [fn(item) for item in items]
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-
-    main = torch.cuda.current_stream()
-    ready = torch.cuda.Event()
-    ready.record(main)
-    device_index = torch.cuda.current_device()
+    fork = _Fork()
     streams = group_streams(lanes)
     results = [None] * len(items)
 
     def work(slot):
-        torch.cuda.set_device(device_index)  # pool threads start on device 0
-        with torch.cuda.stream(streams[slot]):
-            streams[slot].wait_event(ready)  # operands produced on the caller's stream
+        with fork.on(streams[slot]):
             for idx in range(slot, len(items), lanes):
                 results[idx] = fn(items[idx])
         streams[slot].synchronize()
 
-    pool = _group_pools.get(lanes)
-    if pool is None:
-        pool = _group_pools.setdefault(lanes, ThreadPoolExecutor(lanes, thread_name_prefix="ndmps-group"))
-    list(pool.map(work, range(lanes)))
+    list(_group_pool(lanes).map(work, range(lanes)))
     return results
 
 

@@ -192,9 +192,8 @@ def loads(data: bytes, device=None):
                 q = torch.from_numpy(host.copy()).to(device)
                 lo, hi = header["bounds"][i]
                 cores.append(_ft.scale_back(q, lo, hi, _DTYPES[name]))
-        obj = NDMPS(DeviceMPS(cores), plan.qubit_size.copy(), None, [[0.0, 0.0]] * len(cores), header["norm"],
-                    header["norm_value"], header["mode"], header["dim"])
-        obj._shape = shape
+        obj = NDMPS._from_mps(DeviceMPS(cores), plan.qubit_size.copy(), shape, header["norm"], header["mode"],
+                              header["dim"], norm_value=header["norm_value"])
         obj.update_boundary_list()
     return obj
 

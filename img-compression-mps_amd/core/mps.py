@@ -209,15 +209,10 @@ class DeviceMPS:
     def _core_ptrs(self):
         return (C.c_void_p * len(self.cores))(*[c.data_ptr() for c in self.cores])
 
-    def _f32_ptrs(self):
-        """(keep-alive list, pointer array) of the cores as fp32 (bf16 cores are upcast: a few MB at most)."""
-        torch = _torch()
-        keep = [c if c.dtype == torch.float32 else c.to(torch.float32) for c in self.cores]
-        return keep, (C.c_void_p * len(keep))(*[c.data_ptr() for c in keep])
-
-    def _f64_ptrs(self):
-        torch = _torch()
-        keep = [c if c.dtype == torch.float64 else c.to(torch.float64) for c in self.cores]
+    def _ptrs_as(self, dtype):
+        """(keep-alive list, pointer array) of the cores as ``dtype`` (cores of another type are converted: bf16 cores
+        upcast to fp32 are a few MB at most)."""
+        keep = [c if c.dtype == dtype else c.to(dtype) for c in self.cores]
         return keep, (C.c_void_p * len(keep))(*[c.data_ptr() for c in keep])
 
     @property
@@ -236,49 +231,46 @@ class DeviceMPS:
         nbytes = lib.ndmps_overlap_workspace_bytes(L, dims, ba, bb)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         out = C.c_double()
-        if self.dtype == torch.float64 or other.dtype == torch.float64:
-            keep_a, pa = self._f64_ptrs()  # fp64 cores are contracted as they are (a mixed pair: upcast)
-            keep_b, pb = other._f64_ptrs()
-            fn = lib.ndmps_overlap_f64
-        else:
-            keep_a, pa = self._f32_ptrs()
-            keep_b, pb = other._f32_ptrs()
-            fn = lib.ndmps_overlap_f32
+        f64 = self.dtype == torch.float64 or other.dtype == torch.float64
+        work = torch.float64 if f64 else torch.float32  # fp64 cores are contracted as they are (a mixed pair: upcast)
+        keep_a, pa = self._ptrs_as(work)
+        keep_b, pb = other._ptrs_as(work)
+        fn = lib.ndmps_overlap_f64 if f64 else lib.ndmps_overlap_f32
         _lib.check(fn(L, dims, ba, pa, bb, pb, C.byref(out), ws.data_ptr(), nbytes, _lib.stream_ptr()))
         del keep_a, keep_b
         return float(out.value)
+
+    def _chain_args(self):
+        """(L, dims, bonds, workspace) of the ndmps_chain_contract_* calls on these cores."""
+        torch = _torch()
+        lib = _lib.load()
+        L = len(self.cores)
+        dims, bonds = _lib.i64_array(self.dims), _lib.i64_array(self.bonds)
+        query = lib.ndmps_chain_workspace_bytes_f64 if self.dtype == torch.float64 else lib.ndmps_chain_workspace_bytes
+        return L, dims, bonds, torch.empty(query(L, dims, bonds), dtype=torch.uint8, device=self.device)
 
     def to_dense(self, out=None):
         """Left->right chain contraction (core/ndmps.py:140); returns N elements in site order, in the
         storage type of the cores (fp32, or bf16 on the bf16 MFMA)."""
         torch = _torch()
         lib = _lib.load()
-        L = len(self.cores)
-        dims, bonds = _lib.i64_array(self.dims), _lib.i64_array(self.bonds)
-        numel = int(np.prod(self.dims, dtype=np.int64))
         if out is None:
-            out = torch.empty(numel, dtype=self.dtype, device=self.device)
-        f64 = self.dtype == torch.float64
-        nbytes = (lib.ndmps_chain_workspace_bytes_f64 if f64 else lib.ndmps_chain_workspace_bytes)(L, dims, bonds)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        fn = (lib.ndmps_chain_contract_f64 if f64 else
+            out = torch.empty(int(np.prod(self.dims, dtype=np.int64)), dtype=self.dtype, device=self.device)
+        L, dims, bonds, ws = self._chain_args()
+        fn = (lib.ndmps_chain_contract_f64 if self.dtype == torch.float64 else
               lib.ndmps_chain_contract_bf16 if self.dtype == torch.bfloat16 else lib.ndmps_chain_contract_f32)
-        _lib.check(fn(L, dims, bonds, self._core_ptrs(), out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr()))
+        _lib.check(fn(L, dims, bonds, self._core_ptrs(), out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         return out
 
     def to_volume(self, out, n_tail, tables):
         """Chain contraction straight into the C-order volume ``out`` (fp32 cores): the last product scatters
         through the inverse permutation (``tables`` = _Plan.split_tables(n_tail, device))."""
-        torch = _torch()
         lib = _lib.load()
-        L = len(self.cores)
-        dims, bonds = _lib.i64_array(self.dims), _lib.i64_array(self.bonds)
+        L, dims, bonds, ws = self._chain_args()
         row_off, col_off, col_perm = tables
-        nbytes = lib.ndmps_chain_workspace_bytes(L, dims, bonds)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         _lib.check(lib.ndmps_chain_contract_scatter_f32(L, dims, bonds, self._core_ptrs(), out.data_ptr(),
                                                         row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(),
-                                                        int(n_tail), ws.data_ptr(), nbytes, _lib.stream_ptr()))
+                                                        int(n_tail), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         return out
 
     def compress_bond_(self, i, cutoff, max_bond=None):

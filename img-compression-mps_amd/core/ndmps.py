@@ -28,6 +28,7 @@ import math
 import numbers
 import os
 import threading
+import weakref
 
 import numpy as np
 
@@ -221,6 +222,72 @@ def _pooled_dct_basis(n, block, op, device, f64=False):
         return _POOL_DCT_CACHE[key]
 
 
+# ------------------------------------------------------------------------------------------------ decode tail
+def _fused_tail_columns(dtype, dims):
+    """Columns of the chain's last product that scatter straight into the C-order volume (the fused decode of fp32
+    cores); 0: contract the chain in site order and permute afterwards."""
+    if dtype != _torch().float32 or os.environ.get("NDMPS_NO_FUSED_DECODE"):  # the switch: A/B timing
+        return 0
+    return int(_lib.load().ndmps_chain_tail_columns(len(dims), _lib.i64_array(dims)))
+
+
+def _decode_chain(chain, plan, shape):
+    """One chain (a DeviceMPS whose site-order tensor ``plan`` maps onto ``shape``) as a C-order device tensor in the
+    chain's own type.  Runs on the chain's device, which the caller has made current."""
+    torch = _torch()
+    device = chain.device
+    n_tail = _fused_tail_columns(chain.dtype, chain.dims)
+    if n_tail > 0:
+        # fp32: the inverse permutation rides on the last product of the chain; no site-order tensor
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+        with _span("chain"):
+            chain.to_volume(out, n_tail, plan.split_tables(n_tail, device))
+    else:
+        with _span("chain"):
+            dense = chain.to_dense()
+        out = torch.empty(shape, dtype=dense.dtype, device=device)
+        with _span("decode_permute"):
+            _lib.check(_lib.load().ndmps_decode_permute(plan.handle, dense.data_ptr(), out.data_ptr(),
+                                                        dense.element_size(), _lib.stream_ptr()))
+    return out
+
+
+def _decode_chains_f32(batch, L, cdims, bonds, cores, n_tail, plan, shape, device, dct):
+    """``batch`` fp32 chains of one shape -- ``cores``: batch x L device pointers, ``bonds``: batch x (L + 1) -- as one
+    (batch,) + shape tensor, inverse DCT included (``dct``): ONE library call issues the launches of every volume.
+    Buffers are taken in the order reconstruction, chain workspace, IDCT output, and the workspace is held until the
+    IDCT is enqueued (the encode path depends on that order: the allocator note in NDMPS._encode_group)."""
+    torch = _torch()
+    lib = _lib.load()
+    row_off, col_off, col_perm = plan.split_tables(n_tail, device)
+    out = torch.empty((batch,) + tuple(shape), dtype=torch.float32, device=device)
+    ws_bytes = int(lib.ndmps_chain_batched_workspace_bytes(batch, L, cdims, bonds))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    base, step = out.data_ptr(), plan.numel * 4
+    outs = (C.c_void_p * batch)(*[base + b * step for b in range(batch)])
+    with _span("chain"):
+        _lib.check(lib.ndmps_chain_contract_scatter_batched_f32(
+            batch, L, cdims, bonds, cores, outs, row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(),
+            n_tail, ws.data_ptr(), ws_bytes, _lib.stream_ptr()))
+    # the volumes sit back to back in `out`: their rows are the rows of one tall matrix, one launch
+    return _idct_last(out, shape[-1]) if dct else out
+
+
+def _idct_last(x, n):
+    """Inverse DCT along rows of length ``n`` that lie contiguous in ``x`` (a volume's last axis, the volumes of a
+    group back to back, the rows of a region), as a new tensor of x's shape: float64 for float64, float32 otherwise."""
+    torch = _torch()
+    lib = _lib.load()
+    f64 = x.dtype == torch.float64
+    if not f64:
+        x = x.to(torch.float32)  # the IDCT kernel is fp32 (bf16 storage: upcast copy)
+    rec = torch.empty_like(x)
+    idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
+    _lib.check(idct(x.data_ptr(), rec.data_ptr(), x.numel() // n, n, _dct_basis(n, x.device, f64).data_ptr(),
+                    _lib.stream_ptr()))
+    return rec
+
+
 class _GroupState:
     """min / max of every core and the norm of every volume of a lockstep group, ISSUED with the sweep (one
     launch over the group's arena) and COLLECTED when the first object is asked for boundary_list / norm_value:
@@ -228,10 +295,6 @@ class _GroupState:
     the copy back to the host waits until somebody wants the numbers."""
 
     def __init__(self, objs, partial, count, n_cores, stream):
-        import weakref
-
-        import threading
-
         self.refs = [weakref.ref(o) for o in objs]
         self.partial, self.count, self.n_cores, self.stream = partial, count, n_cores, stream
         self.device = partial.device
@@ -305,6 +368,295 @@ class PendingGroup:
         return self._value[0]
 
 
+def _stage_inputs(tensors, device, store, norm):
+    """The group's volumes on ``device`` in the storage type ``store`` (inputs are never mutated), and their shape."""
+    torch = _torch()
+    xs = []
+    for tensor in tensors:
+        if isinstance(tensor, torch.Tensor):
+            if tensor.dim() == 0:
+                raise ValueError("Shape cannot be empty.")
+            # the volume is only written to when it is normalised in place: copy then, otherwise
+            # a volume already resident on the device in the storage type is read where it lies
+            if tensor.dtype == store and tensor.device == device and tensor.is_contiguous() and not tensor.requires_grad:
+                x = tensor  # resident in the storage type already: read where it lies
+            else:
+                x = tensor.detach().to(device=device, dtype=store).contiguous()
+            if norm and x.data_ptr() == tensor.data_ptr():
+                x = x.clone()
+        else:
+            arr = np.asarray(tensor)
+            if arr.ndim == 0:
+                raise ValueError("Shape cannot be empty.")
+            if arr.dtype.kind not in "fiub":
+                raise TypeError(f"unsupported tensor dtype {arr.dtype}")
+            host_type = np.float64 if store == torch.float64 else np.float32
+            x = torch.from_numpy(np.ascontiguousarray(arr, dtype=host_type)).to(device).to(store)
+        xs.append(x)
+    shape = tuple(int(v) for v in xs[0].shape)
+    if any(tuple(x.shape) != shape for x in xs):
+        raise ValueError("from_tensors needs tensors of one shape; encode other shapes separately")
+    return xs, shape
+
+
+def _normalise_and_transform(xs, shape, norm, mode, store, device):
+    """Norm (ndmps.py:60-61) and last-axis DCT (ndmps.py:62-63) of a group's staged volumes, on the current stream;
+    returns them in the storage type."""
+    torch = _torch()
+    lib = _lib.load()
+    stream = _lib.stream_ptr()
+    f64 = store == torch.float64
+    batch, numel = len(xs), xs[0].numel()
+    if (norm or mode == "DCT") and store == torch.bfloat16:
+        xs = [x.to(torch.float32) for x in xs]  # the norm / DCT kernels are fp32; rounded back to bf16 below
+    if norm:
+        # the norms of the whole group from ONE launch and one synchronisation (the reference divides volume by
+        # volume, ndmps.py:60-61; a sum-of-squares call per volume was a host round trip per volume)
+        _, sumsqs = _ft.minmax_many(xs, with_sumsq=True)
+        if f64:
+            for x, ss in zip(xs, sumsqs):
+                _lib.check(lib.ndmps_scale_f64(x.data_ptr(), numel, 1.0 / float(np.sqrt(ss)), stream))
+        else:  # one launch for the group (the reference divides volume by volume, ndmps.py:60-61)
+            _lib.check(lib.ndmps_scale_many_f32(batch, _ptr_array(xs), numel,
+                                                _lib.f64_array([1.0 / float(np.sqrt(ss)) for ss in sumsqs]), stream))
+    if mode == "DCT":
+        n = shape[-1]
+        ys = list(torch.empty((batch,) + shape, dtype=xs[0].dtype, device=device).unbind(0))
+        if f64:
+            for x, y in zip(xs, ys):
+                _lib.check(lib.ndmps_dct_last_f64(x.data_ptr(), y.data_ptr(), numel // n, n,
+                                                  _dct_basis(n, device, True).data_ptr(), stream))
+        else:  # one launch for the group (ndmps.py:62-63 per volume)
+            _lib.check(lib.ndmps_dct_last_many_f32(batch, _ptr_array(xs), _ptr_array(ys), numel // n, n,
+                                                   _dct_basis(n, device).data_ptr(), stream))
+        xs = ys
+    return [x.to(store) for x in xs]
+
+
+class _SweptGroup:
+    """One lockstep group from the reshape stage to its objects.  The stages (reshape_stage, launch_sweep,
+    decode_from_arena, mark_enqueued) run on the group's device and stream and leave here, by name, everything the second
+    half needs: the arena the cores lie in, the host buffers of ranks and spectra -- for a sweep with device-side ranks
+    the pinned buffers they are copied into and the event behind those copies -- the layout (caps, offsets) and the
+    reconstructions.  ``finish()`` is that second half: ranks and spectra to the host, objects, state launch; a
+    ``PendingGroup`` (from_tensors_begin) holds this object and nothing else of the encode."""
+
+    def __init__(self, cls, batch, shape, device, store, norm, mode, max_bond, mirrored, reconstruct):
+        torch = _torch()
+        lib = _lib.load()
+        self.cls, self.batch, self.shape, self.device, self.store = cls, batch, shape, device, store
+        self.norm, self.mode, self.mirrored, self.reconstruct = norm, mode, mirrored, reconstruct
+        self.bf16, self.f64 = store == torch.bfloat16, store == torch.float64
+        self.esize = 2 if self.bf16 else (8 if self.f64 else 4)
+        self.ref_plan = _plan_for(shape, device.index)  # the reference's site order (qubit_size, decode)
+        # mirrored (sweep_from="left"): the sweep runs on the chain read backwards -- the reshape stage writes the
+        # site-order tensor with its axes reversed and `dims` below are the sites in that order
+        self.plan = _plan_for(shape, device.index, reverse_sites=True) if mirrored else self.ref_plan
+        self.stream = _lib.stream_ptr()
+        dims = [int(q) for q in self.ref_plan.qubit_size]
+        if mirrored:
+            dims = dims[::-1]
+        self.dims, self.L, self.cdims = dims, len(dims), _lib.i64_array(dims)
+        self.mb = int(max_bond) if max_bond else 0
+        # fp32, bond-capped: the reshape stage rides on the first Gram pass and the first projection of the
+        # sweep (the volume is read through the permutation tables, no site-order tensor is formed)
+        self.n_merge = (0 if (self.bf16 or self.f64 or os.environ.get("NDMPS_NO_FUSED_ENCODE"))
+                        else int(lib.ndmps_tt_merge_columns(self.L, self.cdims, self.mb)))
+        self.gather = self.plan.gather_tables(self.n_merge, device) if self.n_merge > 0 else None
+        self.padded = bool(lib.ndmps_tt_sweep_pads_cores(self.L, self.cdims, self.mb))
+        self.use_async = False
+        self.ws = self.pin_i = self.pin_d = self.done = self.recs = None
+
+    # ------------------------------------------------------------------ first half: enqueue
+    def reshape_stage(self, xs):
+        """What the sweep reads: the reshape stage of the group in one launch (ndmps.py:66-71 per volume)."""
+        if self.gather is not None:
+            return xs  # read in place by the fused sweep, never written
+        denses = list(_torch().empty((self.batch, self.plan.numel), dtype=self.store, device=self.device).unbind(0))
+        with _span("encode_permute"):
+            _lib.check(_lib.load().ndmps_encode_permute_many(self.plan.handle, self.batch, _ptr_array(xs), _ptr_array(denses),
+                                                             self.esize, self.stream))
+        return denses
+
+    def launch_sweep(self, denses, cutoff, defer):
+        """Layout, arena, workspace and the sweep itself.  ``defer`` with a sweep that decides its ranks on the device:
+        the sweep is enqueued whole (``use_async``), ranks and spectra arrive in pinned buffers."""
+        torch = _torch()
+        lib = _lib.load()
+        batch, L, cdims, mb, device, stream = self.batch, self.L, self.cdims, self.mb, self.device, self.stream
+        max_bonds = (C.c_int64 * (L + 1))()
+        core_off = (C.c_int64 * (L + 1))()
+        self.spec_off = spec_off = (C.c_int64 * (L + 1))()
+        _lib.check(lib.ndmps_tt_layout(L, cdims, mb, max_bonds, core_off, spec_off, None))
+        ws_query = lib.ndmps_tt_sweep_batched_workspace_bytes_f64 if self.f64 else lib.ndmps_tt_sweep_batched_workspace_bytes
+        ws_bytes = ws_query(batch, L, cdims, mb)
+        if ws_bytes < 0:
+            _lib.check(_lib.EINVAL)
+        # one arena for the group: volume b's cores at row b (views of it are what the objects keep)
+        self.core_total = core_total = -(-int(core_off[L]) // 128) * 128  # rows stay 256-byte aligned in either storage type
+        self.arena_all = torch.empty((batch, core_total), dtype=self.store, device=device)
+        self.ws = ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=device)
+        self.bonds = bonds = (C.c_int64 * (batch * (L + 1)))()
+        spec_total = int(spec_off[L])
+        self.spectra = spectra = (C.c_double * max(batch * spec_total, 1))()
+        dense_ptrs = (C.c_void_p * batch)(*[d.data_ptr() for d in denses])
+        self.arena_base, arena_step = self.arena_all.data_ptr(), core_total * self.esize
+        arena_ptrs = (C.c_void_p * batch)(*[self.arena_base + b * arena_step for b in range(batch)])
+        # everything a sweep with device-side ranks needs from the host is known now: it can be enqueued whole
+        self.use_async = bool(defer and self.gather is not None and self.padded and L > 1)
+        with _span("sweep"):
+            if self.gather is not None:
+                row_off, col_off, col_perm = self.gather
+                row_sorted, row_order = self.plan.sorted_rows(self.n_merge, device)
+                tables = (row_off.data_ptr(), row_sorted.data_ptr(), row_order.data_ptr(), col_off.data_ptr(),
+                          col_perm.data_ptr(), self.n_merge, ws.data_ptr(), ws.numel())
+                if self.use_async:
+                    n_d = int(lib.ndmps_tt_sweep_async_doubles(batch, L, cdims, mb))
+                    self.pin_i = torch.empty(int(lib.ndmps_tt_sweep_async_ints(batch, L)), dtype=torch.int32, pin_memory=True)
+                    self.pin_d = torch.empty(max(n_d, 1), dtype=torch.float64, pin_memory=True)
+                    _lib.check(lib.ndmps_tt_sweep_batched_fused_begin_f32(
+                        batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds, *tables,
+                        self.pin_i.data_ptr(), self.pin_d.data_ptr(), stream))
+                else:
+                    _lib.check(lib.ndmps_tt_sweep_batched_fused_f32(
+                        batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds, spectra, spec_off,
+                        *tables, stream))
+            else:
+                sweep = (lib.ndmps_tt_sweep_batched_bf16 if self.bf16 else
+                         lib.ndmps_tt_sweep_batched_f64 if self.f64 else lib.ndmps_tt_sweep_batched_f32)
+                _lib.check(sweep(batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds,
+                                 spectra, spec_off, ws.data_ptr(), ws.numel(), stream))
+        # ranks decided on the device: cores sit in the arena in padded shape (cap_i, d_i, cap_{i+1}), zeros
+        # beyond the actual bonds; slicing is a no-op whenever the caps bind (the usual case)
+        self.bonds_np = np.frombuffer(bonds, dtype=np.int64).reshape(batch, L + 1)  # filled by the sweep / by finish
+        self.spec_np = np.frombuffer(spectra, dtype=np.float64)[: batch * spec_total].reshape(batch, spec_total)
+        self.caps = np.array([int(max_bonds[i]) for i in range(L + 1)], dtype=np.int64)
+        self.offs = [int(core_off[i]) for i in range(L + 1)]
+        self.spec_offs = [int(spec_off[i]) for i in range(L + 1)]
+
+    def decode_from_arena(self):
+        """``reconstruct=True``, where the batched fused decode serves: decode straight from the arena -- padded cores
+        are valid cores of the cap bonds (zeros beyond the rank).  Otherwise ``finish()`` decodes from the objects."""
+        batch, L, esize = self.batch, self.L, self.esize
+        n_tail = _fused_tail_columns(self.store, self.dims) if self.reconstruct and batch > 1 and not self.mirrored else 0
+        if n_tail <= 0:
+            return
+        dec_bonds = _lib.i64_array([v for b in range(batch) for v in (self.caps if self.padded else self.bonds_np[b])])
+        dec_cores = (C.c_void_p * (batch * L))(*[self.arena_base + (b * self.core_total + self.offs[i]) * esize
+                                                 for b in range(batch) for i in range(L)])
+        out = _decode_chains_f32(batch, L, self.cdims, dec_bonds, dec_cores, n_tail, self.ref_plan, self.shape, self.device,
+                                 self.mode == "DCT")
+        self.recs = list(out.unbind(0))
+
+    def mark_enqueued(self):
+        """The stream ``finish()`` continues on and, behind an asynchronous sweep, the event it waits for."""
+        self.tstream = _torch().cuda.current_stream(self.device)
+        if self.use_async:
+            self.done = _torch().cuda.Event()
+            self.done.record(self.tstream)
+
+    # ------------------------------------------------------------------ second half: objects
+    def wait(self):
+        """Until the copies into the pinned buffers have landed (nothing to wait for after a synchronous sweep)."""
+        if self.done is not None:
+            self.done.synchronize()
+
+    def finish(self):
+        """Ranks and spectra to the host (asynchronous sweep: behind its event), objects, state launch."""
+        torch = _torch()
+        with torch.cuda.device(self.device), torch.cuda.stream(self.tstream):
+            if self.use_async:
+                self.done.synchronize()
+                _lib.check(_lib.load().ndmps_tt_sweep_finish(self.batch, self.L, self.cdims, self.mb, self.pin_i.data_ptr(),
+                                                             self.pin_d.data_ptr(), self.bonds, self.spectra, self.spec_off))
+            per_site = self._cap_shaped_cores()
+            objs = self._build_objects(per_site)
+            self._launch_state(objs, per_site is not None)
+            if not self.reconstruct:
+                return objs
+            return objs, (self.recs if self.recs is not None else self.cls.to_tensors(objs, as_torch=True))
+
+    def _cap_shaped_cores(self):
+        """[site][volume] views of the arena when every cap binds, else None."""
+        if not (self.padded and bool((self.bonds_np == self.caps).all()) and not self.mirrored):
+            return None
+        # every cap binds: the padded cores ARE the cores; L narrow / view / unbind calls serve the whole
+        # group (per-core slicing was 2 ms of host time per group of 32 with the GPU idle)
+        caps, offs, dims = self.caps, self.offs, self.dims
+        return [self.arena_all[:, offs[i]: offs[i] + int(caps[i]) * dims[i] * int(caps[i + 1])]
+                .view(self.batch, int(caps[i]), dims[i], int(caps[i + 1])).unbind(0) for i in range(self.L)]
+
+    def _cores_of(self, b):
+        """Volume b's cores cut out of the arena at its own ranks, in the reference's site order."""
+        caps, offs, dims, kb = self.caps, self.offs, self.dims, self.bonds_np[b]
+        cores = []
+        for i in range(self.L):
+            k0, k1 = int(kb[i]), int(kb[i + 1])
+            if self.padded:
+                c0, c1 = int(caps[i]), int(caps[i + 1])
+                full = self.arena_all[b, offs[i]: offs[i] + c0 * dims[i] * c1].view(c0, dims[i], c1)
+                cores.append(full[:k0, :, :k1].contiguous())
+            else:
+                view = self.arena_all[b, offs[i]: offs[i] + k0 * dims[i] * k1].view(k0, dims[i], k1)
+                # truncated arenas are compact, keep the views; exact sweeps own worst-case arenas
+                cores.append(view if self.mb else view.clone())
+        if self.mirrored:
+            # back to the reference's chain: site j is mirrored site L-1-j with its bond axes swapped
+            cores = [c.permute(2, 1, 0).contiguous() for c in reversed(cores)]
+        return cores
+
+    def _build_objects(self, per_site):
+        L, dims, shape, spec_offs = self.L, self.dims, self.shape, self.spec_offs
+        lefts = [math.prod(dims[:i]) for i in range(L)]
+        objs = []
+        bl0 = np.zeros((L, 2))
+        for b in range(self.batch):
+            kb = self.bonds_np[b]
+            cores = [per_site[i][b] for i in range(L)] if per_site is not None else self._cores_of(b)
+            obj = self.cls._from_mps(DeviceMPS(cores, _trusted=True), self.ref_plan.qubit_size.copy(), shape, self.norm,
+                                     self.mode, len(shape), boundary_list=bl0)
+            counts = [min(lefts[i], dims[i] * int(kb[i + 1])) for i in range(L)]
+            row = self.spec_np[b]
+            if self.mirrored:
+                # the values of mirrored bond (i-1 | i) belong to bond (L-i-1 | L-i)
+                obj.sweep_spectra = [None] + [row[spec_offs[L - j]: spec_offs[L - j] + counts[L - j]].copy()
+                                              for j in range(1, L)]
+            else:
+                # singular values of the sweep, cut out of the group's buffer on first use
+                obj._spectra_lazy = (row, spec_offs, counts)
+            objs.append(obj)
+        return objs
+
+    def _launch_state(self, objs, cap_shaped):
+        torch = _torch()
+        lib = _lib.load()
+        batch, L, caps, dims = self.batch, self.L, self.caps, self.dims
+        with _span("state"):
+            # boundary_list (ndmps.py:75) and norm_value (ndmps.py:76) of every volume from one
+            # launch.  The sweep leaves sites 1..L-1 right-isometric (rows of V^T), so
+            # mps @ mps = ||site 0||_F^2 up to the fp32 rounding of those rows (~1e-7 relative);
+            # update_norm() evaluates the full overlap contraction like the reference.
+            if cap_shaped and not self.bf16 and not self.f64 and L <= 64 and batch * L <= 65535:
+                # cores = cap-shaped views of the arena: one launch now, the numbers on first access
+                count = batch * L
+                partial = torch.empty(int(lib.ndmps_minmax_partials_bytes(count)) // 8, dtype=torch.float64, device=self.device)
+                lens = _lib.i64_array([int(caps[i]) * dims[i] * int(caps[i + 1]) for i in range(L)])
+                _lib.check(lib.ndmps_minmax_arena_launch_f32(self.arena_base, self.core_total, batch, L,
+                                                             _lib.i64_array(self.offs[:L]), lens, partial.data_ptr(),
+                                                             self.stream))
+                group = _GroupState(objs, partial, count, L, self.stream)
+                for o in objs:
+                    o.__dict__["_state_group"] = group
+            else:
+                all_cores = [c for o in objs for c in o.mps.cores]
+                mm, ss = _ft.minmax_many(all_cores, with_sumsq=True)
+                mm_np = np.asarray(mm, dtype=np.float64).reshape(batch, L, 2)
+                for b, o in enumerate(objs):
+                    o.boundary_list = mm_np[b]
+                    # the site that carries the norm: 0 after a right-to-left sweep, L-1 after the mirrored one
+                    o.norm_value = np.sqrt(ss[b * L + (L - 1 if self.mirrored else 0)])
+
+
 class NDMPS:
     """
     Class for storing and compressing N-dimensional tensors using MPS (device resident).
@@ -323,6 +675,28 @@ class NDMPS:
         # tensor shape: known from the map when one is handed in (the reference's constructor allows
         # that, ndmps.py:17-35), set by from_tensors / codec.loads otherwise
         self._shape = tuple(int(v) for v in np.shape(encoding_map)[:-1]) if encoding_map is not None else None
+
+    @classmethod
+    def _from_mps(cls, mps, qubit_size, shape, norm, mode, dim, encoding_map=None, norm_value=None, boundary_list=None):
+        """An object around finished cores: the fields of __init__, set without its array conversions (the encode path
+        builds 32 objects per group inside the timed region), plus the tensor shape."""
+        obj = cls.__new__(cls)
+        obj.qubit_size = qubit_size
+        obj._encoding_map = encoding_map
+        obj.mps = mps
+        obj.dim = dim
+        obj.norm = norm
+        obj.norm_value = norm_value
+        obj.mode = mode
+        obj.boundary_list = boundary_list
+        obj._shape = shape
+        return obj
+
+    def _like(self, cores, norm=None):
+        """A new object for ``cores`` (finished: contiguous, 3-D) of the tensor this one stores -- same shape, mode,
+        site dimensions and encoding map; boundary_list and norm_value are left to the caller."""
+        return NDMPS._from_mps(DeviceMPS(cores, _trusted=True), self.qubit_size, self._shape,
+                               self.norm if norm is None else norm, self.mode, self.dim, self._encoding_map)
 
     # boundary_list / norm_value: plain attributes as in the reference; after from_tensors their device-side
     # reductions are in flight and the values arrive on first access (_GroupState)
@@ -516,7 +890,6 @@ class NDMPS:
         (fp32, bond-capped) everything is only ENQUEUED -- sweep, decode, the copies of ranks and spectra into pinned host
         memory, an event -- and ``result()`` waits for the event, reads the ranks and builds the objects."""
         torch = _torch()
-        lib = _lib.load()
         first = tensors[0]
         if device is None:
             device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else "cuda"
@@ -526,272 +899,23 @@ class NDMPS:
         store = torch.float32 if dtype is None else dtype
         if store not in (torch.float32, torch.bfloat16, torch.float64):
             raise ValueError("storage dtype must be torch.float32, torch.bfloat16 or torch.float64")
-        bf16 = store == torch.bfloat16
-        f64 = store == torch.float64
-        esize = 2 if bf16 else (8 if f64 else 4)
-        xs = []
-        for tensor in tensors:
-            if isinstance(tensor, torch.Tensor):
-                if tensor.dim() == 0:
-                    raise ValueError("Shape cannot be empty.")
-                # the volume is only written to when it is normalised in place: copy then, otherwise
-                # a volume already resident on the device in the storage type is read where it lies
-                if tensor.dtype == store and tensor.device == device and tensor.is_contiguous() and not tensor.requires_grad:
-                    x = tensor  # resident in the storage type already: read where it lies
-                else:
-                    x = tensor.detach().to(device=device, dtype=store).contiguous()
-                if norm and x.data_ptr() == tensor.data_ptr():
-                    x = x.clone()
-            else:
-                arr = np.asarray(tensor)
-                if arr.ndim == 0:
-                    raise ValueError("Shape cannot be empty.")
-                if arr.dtype.kind not in "fiub":
-                    raise TypeError(f"unsupported tensor dtype {arr.dtype}")
-                host_type = np.float64 if f64 else np.float32
-                x = torch.from_numpy(np.ascontiguousarray(arr, dtype=host_type)).to(device).to(store)
-            xs.append(x)
-        shape = tuple(int(v) for v in xs[0].shape)
-        if any(tuple(x.shape) != shape for x in xs):
-            raise ValueError("from_tensors needs tensors of one shape; encode other shapes separately")
-        batch = len(xs)
+        xs, shape = _stage_inputs(tensors, device, store, norm)
         with torch.cuda.device(device):
-            ref_plan = _plan_for(shape, device.index)  # the reference's site order (qubit_size, decode)
-            # mirrored (sweep_from="left"): the sweep runs on the chain read backwards -- the reshape stage writes the
-            # site-order tensor with its axes reversed and `dims` below are the sites in that order
-            plan = _plan_for(shape, device.index, reverse_sites=True) if mirrored else ref_plan
-            stream = _lib.stream_ptr()
-            numel = plan.numel
-            dims = [int(q) for q in ref_plan.qubit_size]
-            if mirrored:
-                dims = dims[::-1]
-            L = len(dims)
-            cdims = _lib.i64_array(dims)
-            mb = int(max_bond) if max_bond else 0
-            # fp32, bond-capped: the reshape stage rides on the first Gram pass and the first projection of the
-            # sweep (the volume is read through the permutation tables, no site-order tensor is formed)
-            n_merge = 0 if (bf16 or f64 or os.environ.get("NDMPS_NO_FUSED_ENCODE")) else int(lib.ndmps_tt_merge_columns(L, cdims, mb))
-            gather = plan.gather_tables(n_merge, device) if n_merge > 0 else None
-            denses = []
-            if (norm or mode == "DCT") and bf16:
-                xs = [x.to(torch.float32) for x in xs]  # the norm / DCT kernels are fp32; rounded back to bf16 below
-            if norm:
-                # the norms of the whole group from ONE launch and one synchronisation (the reference divides volume by
-                # volume, ndmps.py:60-61; a sum-of-squares call per volume was a host round trip per volume)
-                _, sumsqs = _ft.minmax_many(xs, with_sumsq=True)
-                if f64:
-                    for x, ss in zip(xs, sumsqs):
-                        _lib.check(lib.ndmps_scale_f64(x.data_ptr(), numel, 1.0 / float(np.sqrt(ss)), stream))
-                else:  # one launch for the group (the reference divides volume by volume, ndmps.py:60-61)
-                    _lib.check(lib.ndmps_scale_many_f32(batch, _ptr_array(xs), numel,
-                                                        _lib.f64_array([1.0 / float(np.sqrt(ss)) for ss in sumsqs]), stream))
-            if mode == "DCT":
-                n = shape[-1]
-                ys = list(torch.empty((batch,) + shape, dtype=xs[0].dtype, device=device).unbind(0))
-                if f64:
-                    for x, y in zip(xs, ys):
-                        _lib.check(lib.ndmps_dct_last_f64(x.data_ptr(), y.data_ptr(), numel // n, n,
-                                                          _dct_basis(n, device, True).data_ptr(), stream))
-                else:  # one launch for the group (ndmps.py:62-63 per volume)
-                    _lib.check(lib.ndmps_dct_last_many_f32(batch, _ptr_array(xs), _ptr_array(ys), numel // n, n,
-                                                           _dct_basis(n, device).data_ptr(), stream))
-                xs = ys
-            xs = [x.to(store) for x in xs]
-            if gather is not None:
-                denses = xs  # read in place by the fused sweep, never written
-            else:
-                # the reshape stage of the group in one launch (ndmps.py:66-71 per volume)
-                denses = list(torch.empty((batch, numel), dtype=store, device=device).unbind(0))
-                with _span("encode_permute"):
-                    _lib.check(lib.ndmps_encode_permute_many(plan.handle, batch, _ptr_array(xs), _ptr_array(denses), esize,
-                                                             stream))
+            group = _SweptGroup(cls, len(xs), shape, device, store, norm, mode, max_bond, mirrored, reconstruct)
+            xs = _normalise_and_transform(xs, shape, norm, mode, store, device)
+            denses = group.reshape_stage(xs)
             del xs
-
-            max_bonds = (C.c_int64 * (L + 1))()
-            core_off = (C.c_int64 * (L + 1))()
-            spec_off = (C.c_int64 * (L + 1))()
-            _lib.check(lib.ndmps_tt_layout(L, cdims, mb, max_bonds, core_off, spec_off, None))
-            ws_query = lib.ndmps_tt_sweep_batched_workspace_bytes_f64 if f64 else lib.ndmps_tt_sweep_batched_workspace_bytes
-            ws_bytes = ws_query(batch, L, cdims, mb)
-            if ws_bytes < 0:
-                _lib.check(_lib.EINVAL)
-            # one arena for the group: volume b's cores at row b (views of it are what the objects keep)
-            core_total = -(-int(core_off[L]) // 128) * 128  # rows stay 256-byte aligned in either storage type
-            arena_all = torch.empty((batch, core_total), dtype=store, device=device)
-            ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=device)
-            bonds = (C.c_int64 * (batch * (L + 1)))()
-            spec_total = int(spec_off[L])
-            spectra = (C.c_double * max(batch * spec_total, 1))()
-            dense_ptrs = (C.c_void_p * batch)(*[d.data_ptr() for d in denses])
-            arena_base, arena_step = arena_all.data_ptr(), core_total * esize
-            arena_ptrs = (C.c_void_p * batch)(*[arena_base + b * arena_step for b in range(batch)])
-            padded = bool(lib.ndmps_tt_sweep_pads_cores(L, cdims, mb))
-            # everything a sweep with device-side ranks needs from the host is known now: it can be enqueued whole
-            use_async = bool(defer and gather is not None and padded and L > 1)
-            pin_i = pin_d = done = None
-            with _span("sweep"):
-                if use_async:
-                    row_off, col_off, col_perm = gather
-                    row_sorted, row_order = plan.sorted_rows(n_merge, device)
-                    n_d = int(lib.ndmps_tt_sweep_async_doubles(batch, L, cdims, mb))
-                    pin_i = torch.empty(int(lib.ndmps_tt_sweep_async_ints(batch, L)), dtype=torch.int32, pin_memory=True)
-                    pin_d = torch.empty(max(n_d, 1), dtype=torch.float64, pin_memory=True)
-                    _lib.check(lib.ndmps_tt_sweep_batched_fused_begin_f32(
-                        batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds,
-                        row_off.data_ptr(), row_sorted.data_ptr(), row_order.data_ptr(), col_off.data_ptr(),
-                        col_perm.data_ptr(), n_merge, ws.data_ptr(), ws.numel(), pin_i.data_ptr(), pin_d.data_ptr(), stream))
-                elif gather is not None:
-                    row_off, col_off, col_perm = gather
-                    row_sorted, row_order = plan.sorted_rows(n_merge, device)
-                    _lib.check(lib.ndmps_tt_sweep_batched_fused_f32(
-                        batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds, spectra, spec_off,
-                        row_off.data_ptr(), row_sorted.data_ptr(), row_order.data_ptr(), col_off.data_ptr(),
-                        col_perm.data_ptr(), n_merge, ws.data_ptr(), ws.numel(), stream))
-                else:
-                    sweep = (lib.ndmps_tt_sweep_batched_bf16 if bf16 else
-                             lib.ndmps_tt_sweep_batched_f64 if f64 else lib.ndmps_tt_sweep_batched_f32)
-                    _lib.check(sweep(batch, dense_ptrs, L, cdims, float(cutoff), mb, arena_ptrs, core_off, bonds,
-                                     spectra, spec_off, ws.data_ptr(), ws.numel(), stream))
+            group.launch_sweep(denses, cutoff, defer)
             del denses
-            # (the workspace is released further down, behind the decode's buffers: freed here, the caching allocator cut the
-            # reconstruction buffer out of its block whenever earlier reconstructions were still held by a pending batch,
-            # and the next batch's workspace -- several GB -- came from a fresh hipMalloc: one second, now and then)
-            # ranks decided on the device: cores sit in the arena in padded shape (cap_i, d_i, cap_{i+1}), zeros
-            # beyond the actual bonds; slicing is a no-op whenever the caps bind (the usual case)
-            bonds_np = np.frombuffer(bonds, dtype=np.int64).reshape(batch, L + 1)  # filled by the sweep / by finish
-            spec_np = np.frombuffer(spectra, dtype=np.float64)[: batch * spec_total].reshape(batch, spec_total)
-            caps = np.array([int(max_bonds[i]) for i in range(L + 1)], dtype=np.int64)
-            offs = [int(core_off[i]) for i in range(L + 1)]
-            spec_offs = [int(spec_off[i]) for i in range(L + 1)]
-            recs = None
-            n_tail = (int(lib.ndmps_chain_tail_columns(L, cdims))
-                      if (reconstruct and not bf16 and not f64 and batch > 1 and not mirrored) else 0)
-            if n_tail > 0 and not os.environ.get("NDMPS_NO_FUSED_DECODE"):
-                # decode straight from the arena: padded cores are valid cores of the cap bonds (zeros beyond the rank)
-                dec_bonds = (C.c_int64 * (batch * (L + 1)))()
-                dec_cores = (C.c_void_p * (batch * L))()
-                for b in range(batch):
-                    dec_bonds[b * (L + 1): (b + 1) * (L + 1)] = [int(v) for v in (caps if padded else bonds_np[b])]
-                    row = arena_base + b * arena_step
-                    for i in range(L):
-                        dec_cores[b * L + i] = row + offs[i] * esize
-                r_off, c_off, c_perm = plan.split_tables(n_tail, device)
-                out = torch.empty((batch,) + shape, dtype=torch.float32, device=device)
-                cws_bytes = int(lib.ndmps_chain_batched_workspace_bytes(batch, L, cdims, dec_bonds))
-                cws = torch.empty(cws_bytes, dtype=torch.uint8, device=device)
-                obase, ostep = out.data_ptr(), numel * 4
-                outs = (C.c_void_p * batch)(*[obase + b * ostep for b in range(batch)])
-                with _span("chain"):
-                    _lib.check(lib.ndmps_chain_contract_scatter_batched_f32(
-                        batch, L, cdims, dec_bonds, dec_cores, outs, r_off.data_ptr(), c_off.data_ptr(), c_perm.data_ptr(),
-                        n_tail, cws.data_ptr(), cws_bytes, stream))
-                recs = list(out.unbind(0))
-                if mode == "DCT":
-                    # the group's volumes sit back to back in `out`: their rows are the rows of one tall matrix
-                    n_last = shape[-1]
-                    rec_all = torch.empty_like(out)
-                    _lib.check(lib.ndmps_idct_last_f32(out.data_ptr(), rec_all.data_ptr(), batch * (numel // n_last), n_last,
-                                                       _dct_basis(n_last, device).data_ptr(), stream))
-                    recs = list(rec_all.unbind(0))
-                del cws
-            del ws
-            tstream = torch.cuda.current_stream(device)
-            if use_async:
-                done = torch.cuda.Event()
-                done.record(tstream)
-
-        def finish():
-            """Ranks and spectra to the host (asynchronous sweep: behind its event), objects, state launch."""
-            with torch.cuda.device(device), torch.cuda.stream(tstream):
-                return finish_on_stream()
-
-        def finish_on_stream():
-            if use_async:
-                done.synchronize()
-                _lib.check(lib.ndmps_tt_sweep_finish(batch, L, cdims, mb, pin_i.data_ptr(), pin_d.data_ptr(), bonds, spectra,
-                                                     spec_off))
-            per_site = None
-            if padded and bool((bonds_np == caps).all()) and not mirrored:
-                # every cap binds: the padded cores ARE the cores; L narrow / view / unbind calls serve the whole
-                # group (per-core slicing was 2 ms of host time per group of 32 with the GPU idle)
-                per_site = [arena_all[:, offs[i]: offs[i] + int(caps[i]) * dims[i] * int(caps[i + 1])]
-                            .view(batch, int(caps[i]), dims[i], int(caps[i + 1])).unbind(0) for i in range(L)]
-            lefts = [1] * L
-            for i in range(1, L):
-                lefts[i] = lefts[i - 1] * dims[i - 1]
-            objs = []
-            bl0 = np.zeros((L, 2))
-            for b in range(batch):
-                kb = bonds_np[b]
-                if per_site is not None:
-                    cores = [per_site[i][b] for i in range(L)]
-                else:
-                    cores = []
-                    for i in range(L):
-                        k0, k1 = int(kb[i]), int(kb[i + 1])
-                        if padded:
-                            c0, c1 = int(caps[i]), int(caps[i + 1])
-                            full = arena_all[b, offs[i]: offs[i] + c0 * dims[i] * c1].view(c0, dims[i], c1)
-                            cores.append(full[:k0, :, :k1].contiguous())
-                        else:
-                            view = arena_all[b, offs[i]: offs[i] + k0 * dims[i] * k1].view(k0, dims[i], k1)
-                            # truncated arenas are compact, keep the views; exact sweeps own worst-case arenas
-                            cores.append(view if mb else view.clone())
-                counts = [min(lefts[i], dims[i] * int(kb[i + 1])) for i in range(L)]
-                spec_view = (spec_np[b], spec_offs, counts)
-                if mirrored:
-                    # back to the reference's chain: site j is mirrored site L-1-j with its bond axes swapped; the
-                    # values of mirrored bond (i-1 | i) belong to bond (L-i-1 | L-i)
-                    cores = [c.permute(2, 1, 0).contiguous() for c in reversed(cores)]
-                    row = spec_np[b]
-                    spec_view = None
-                    mirrored_spectra = [None] + [row[spec_offs[L - j]: spec_offs[L - j] + counts[L - j]].copy()
-                                                 for j in range(1, L)]
-                obj = cls.__new__(cls)  # the fields of __init__, without its array conversions (32 objects per group)
-                obj.qubit_size = ref_plan.qubit_size.copy()
-                obj._encoding_map = None
-                obj.mps = DeviceMPS(cores, _trusted=True)
-                obj.dim = len(shape)
-                obj.norm = norm
-                obj.norm_value = None
-                obj.mode = mode
-                obj.boundary_list = bl0
-                obj._shape = shape
-                # singular values of the sweep, cut out of the group's buffer on first use
-                obj._spectra_lazy = spec_view
-                if mirrored:
-                    obj.sweep_spectra = mirrored_spectra
-                objs.append(obj)
-            with _span("state"):
-                # boundary_list (ndmps.py:75) and norm_value (ndmps.py:76) of every volume from one
-                # launch.  The sweep leaves sites 1..L-1 right-isometric (rows of V^T), so
-                # mps @ mps = ||site 0||_F^2 up to the fp32 rounding of those rows (~1e-7 relative);
-                # update_norm() evaluates the full overlap contraction like the reference.
-                if per_site is not None and not bf16 and not f64 and L <= 64 and batch * L <= 65535:
-                    # cores = cap-shaped views of the arena: one launch now, the numbers on first access
-                    count = batch * L
-                    partial = torch.empty(int(lib.ndmps_minmax_partials_bytes(count)) // 8, dtype=torch.float64, device=device)
-                    lens = _lib.i64_array([int(caps[i]) * dims[i] * int(caps[i + 1]) for i in range(L)])
-                    _lib.check(lib.ndmps_minmax_arena_launch_f32(arena_base, core_total, batch, L, _lib.i64_array(offs[:L]),
-                                                                 lens, partial.data_ptr(), stream))
-                    group = _GroupState(objs, partial, count, L, stream)
-                    for o in objs:
-                        o.__dict__["_state_group"] = group
-                else:
-                    all_cores = [c for o in objs for c in o.mps.cores]
-                    mm, ss = _ft.minmax_many(all_cores, with_sumsq=True)
-                    mm_np = np.asarray(mm, dtype=np.float64).reshape(batch, L, 2)
-                    for b, o in enumerate(objs):
-                        o.boundary_list = mm_np[b]
-                        # the site that carries the norm: 0 after a right-to-left sweep, L-1 after the mirrored one
-                        o.norm_value = np.sqrt(ss[b * L + (L - 1 if mirrored else 0)])
-            if reconstruct:
-                return objs, (recs if recs is not None else cls.to_tensors(objs, as_torch=True))
-            return objs
-
+            group.decode_from_arena()
+            # the workspace is released here, behind the decode's buffers: freed in front of them, the caching allocator cut
+            # the reconstruction buffer out of its block whenever earlier reconstructions were still held by a pending batch,
+            # and the next batch's workspace -- several GB -- came from a fresh hipMalloc: one second, now and then
+            group.ws = None
+            group.mark_enqueued()
         if defer:
-            return PendingGroup(finish, asynchronous=use_async, wait=done.synchronize if use_async else None)
-        return finish()
+            return PendingGroup(group.finish, asynchronous=group.use_async, wait=group.wait)
+        return group.finish()
 
     # ----------------------------------------------------------------- bookkeeping
     def astype(self, dtype):
@@ -801,11 +925,7 @@ class NDMPS:
         torch = _torch()
         if dtype not in (torch.float32, torch.bfloat16, torch.float64):
             raise ValueError("storage dtype must be torch.float32, torch.bfloat16 or torch.float64")
-        from .mps import DeviceMPS
-
-        out = NDMPS(DeviceMPS([c.to(dtype).contiguous() for c in self.mps.cores]), self.qubit_size, None, None, self.norm, None,
-                    self.mode, self.dim)
-        out._shape = self._shape
+        out = self._like([c.to(dtype).contiguous() for c in self.mps.cores])
         out.update_boundary_list()
         out.update_norm()
         return out
@@ -937,9 +1057,7 @@ class NDMPS:
                  for j in range(L)]
         if dtype == torch.bfloat16:
             cores = [c.to(torch.bfloat16) for c in cores]
-        out = NDMPS(DeviceMPS(cores, _trusted=True), first.qubit_size, None, None, False, None, first.mode, first.dim)
-        out._shape = first._shape
-        out._encoding_map = first._encoding_map
+        out = first._like(cores, norm=False)
         out.update_boundary_list()
         out.update_norm()
         st = int(stride.value)
@@ -960,9 +1078,7 @@ class NDMPS:
         """A copy with site 0 multiplied by ``c`` (no rounding; bonds unchanged)."""
         cores = [t.clone() for t in self.mps.cores]
         cores[0].mul_(c)
-        out = NDMPS(DeviceMPS(cores, _trusted=True), self.qubit_size, None, None, self.norm, None, self.mode, self.dim)
-        out._shape = self._shape
-        out._encoding_map = self._encoding_map
+        out = self._like(cores)
         out.update_boundary_list()
         out.norm_value = abs(c) * float(self.norm_value)
         spec = self.sweep_spectra
@@ -1007,6 +1123,11 @@ class NDMPS:
                 print(f"Compression ratio at {c}: {self.compression_ratio()}")
 
     # ------------------------------------------------------------------ reconstruct
+    def _require_shape(self):
+        if self._shape is None:
+            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        return self._shape
+
     def to_tensor(self, as_torch: bool = False, dtype=None):
         """
         Convert MPS back to tensor format (with optional inverse DCT).
@@ -1015,46 +1136,15 @@ class NDMPS:
         ``dtype`` (e.g. ``torch.bfloat16``) selects its storage type (arithmetic stays fp32).  fp64 cores
         (``from_tensor(dtype=torch.float64)``) are contracted on the fp64 MFMA and give a float64 result.
         """
-        torch = _torch()
-        lib = _lib.load()
-        if self._shape is None:
-            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        shape = self._require_shape()
         device = self.mps.device
-        with torch.cuda.device(device):
-            plan = _plan_for(self._shape, device.index or 0)
-            stream = _lib.stream_ptr()
-            dims = _lib.i64_array(self.mps.dims)
-            n_tail = lib.ndmps_chain_tail_columns(len(self.mps.dims), dims) if self.mps.dtype == torch.float32 else 0
-            if os.environ.get("NDMPS_NO_FUSED_DECODE"):  # A/B timing
-                n_tail = 0
-            if n_tail > 0:
-                # fp32: the inverse permutation rides on the last product of the chain; no site-order tensor
-                out = torch.empty(self._shape, dtype=torch.float32, device=device)
-                with _span("chain"):
-                    self.mps.to_volume(out, n_tail, plan.split_tables(n_tail, device))
-            else:
-                with _span("chain"):
-                    dense = self.mps.to_dense()
-                out = torch.empty(self._shape, dtype=dense.dtype, device=device)
-                with _span("decode_permute"):
-                    _lib.check(lib.ndmps_decode_permute(plan.handle, dense.data_ptr(), out.data_ptr(),
-                                                        dense.element_size(), stream))
+        with _torch().cuda.device(device):
+            out = _decode_chain(self.mps, _plan_for(shape, device.index or 0), shape)
             if self.mode == "DCT":
-                n = self._shape[-1]
-                f64 = out.dtype == torch.float64
-                if not f64:
-                    out = out.to(torch.float32)  # the IDCT kernel is fp32 (bf16 storage: upcast copy)
-                rec = torch.empty_like(out)
-                idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
-                _lib.check(idct(out.data_ptr(), rec.data_ptr(), plan.numel // n, n, _dct_basis(n, device, f64).data_ptr(), stream))
-                out = rec
+                out = _idct_last(out, shape[-1])
             elif self.mode != "Std":
                 return None  # ndmps.py:150-153: unknown modes fall through
-        if as_torch:
-            return out if dtype is None else out.to(dtype)
-        if out.dtype == torch.float64:
-            return out.cpu().numpy()
-        return out.to(torch.float32).cpu().numpy()  # NumPy has no bf16
+        return self._result(out, as_torch, dtype)
 
     @staticmethod
     def to_tensors(objs, as_torch: bool = False):
@@ -1072,75 +1162,34 @@ class NDMPS:
         group = (len(objs) > 1 and first._shape is not None and first.mode in ("Std", "DCT")
                  and all(o._shape == first._shape and o.mode == first.mode and o.mps.dtype == first.mps.dtype
                          and o.mps.device == first.mps.device and o.mps.dims == first.mps.dims for o in objs))
-        same = group and first.mps.dtype == torch.float32 and not os.environ.get("NDMPS_NO_FUSED_DECODE")
-        lib = _lib.load()
-        n_tail = 0
-        if same:
-            dims_list = first.mps.dims
-            cdims = _lib.i64_array(dims_list)
-            n_tail = int(lib.ndmps_chain_tail_columns(len(dims_list), cdims))
         if not group:
             return [o.to_tensor(as_torch=as_torch) for o in objs]
-        device = first.mps.device
-        if not same or n_tail <= 0:
-            # bf16 / fp64 cores (or the fused decode switched off): a chain per volume, then the inverse permutation and
-            # the IDCT of the whole group in one launch each (to_tensor's steps, ndmps.py:140-153)
-            batch = len(objs)
-            with torch.cuda.device(device):
-                plan = _plan_for(first._shape, device.index or 0)
-                stream = _lib.stream_ptr()
+        lib = _lib.load()
+        device, shape, batch = first.mps.device, tuple(first._shape), len(objs)
+        dims_list = first.mps.dims
+        n_tail = _fused_tail_columns(first.mps.dtype, dims_list)
+        with torch.cuda.device(device):
+            plan = _plan_for(shape, device.index or 0)
+            if n_tail > 0:
+                L = len(dims_list)
+                bonds = _lib.i64_array([k for o in objs for k in o.mps.bonds])
+                cores = _ptr_array([c for o in objs for c in o.mps.cores])
+                out = _decode_chains_f32(batch, L, _lib.i64_array(dims_list), bonds, cores, n_tail, plan, shape, device,
+                                         first.mode == "DCT")
+            else:
+                # bf16 / fp64 cores (or the fused decode switched off): a chain per volume, then the inverse permutation and
+                # the IDCT of the whole group in one launch each (to_tensor's steps, ndmps.py:140-153)
                 with _span("chain"):
                     denses = [o.mps.to_dense() for o in objs]
-                out = torch.empty((batch,) + tuple(first._shape), dtype=denses[0].dtype, device=device)
+                out = torch.empty((batch,) + shape, dtype=denses[0].dtype, device=device)
                 with _span("decode_permute"):
                     _lib.check(lib.ndmps_decode_permute_many(plan.handle, batch, _ptr_array(denses),
-                                                             _ptr_array(list(out.unbind(0))), denses[0].element_size(), stream))
+                                                             _ptr_array(list(out.unbind(0))), denses[0].element_size(),
+                                                             _lib.stream_ptr()))
                 del denses
                 if first.mode == "DCT":
-                    n = first._shape[-1]
-                    f64 = out.dtype == torch.float64
-                    if not f64:
-                        out = out.to(torch.float32)  # the IDCT kernel is fp32 (bf16 storage: upcast copy)
-                    rec_all = torch.empty_like(out)
-                    idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
-                    _lib.check(idct(out.data_ptr(), rec_all.data_ptr(), batch * (plan.numel // n), n,
-                                    _dct_basis(n, device, f64).data_ptr(), stream))
-                    out = rec_all
-                recs = list(out.unbind(0))
-            if as_torch:
-                return recs
-            return [(r if r.dtype == torch.float64 else r.to(torch.float32)).cpu().numpy() for r in recs]
-        batch, L = len(objs), len(dims_list)
-        with torch.cuda.device(device):
-            plan = _plan_for(first._shape, device.index or 0)
-            stream = _lib.stream_ptr()
-            row_off, col_off, col_perm = plan.split_tables(n_tail, device)
-            out = torch.empty((batch,) + tuple(first._shape), dtype=torch.float32, device=device)
-            bonds = (C.c_int64 * (batch * (L + 1)))()
-            cores = (C.c_void_p * (batch * L))()
-            for b, o in enumerate(objs):
-                bonds[b * (L + 1): (b + 1) * (L + 1)] = o.mps.bonds
-                for i, c in enumerate(o.mps.cores):
-                    cores[b * L + i] = c.data_ptr()
-            ws_bytes = int(lib.ndmps_chain_batched_workspace_bytes(batch, L, cdims, bonds))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-            base, step = out.data_ptr(), plan.numel * 4
-            outs = (C.c_void_p * batch)(*[base + b * step for b in range(batch)])
-            with _span("chain"):
-                _lib.check(lib.ndmps_chain_contract_scatter_batched_f32(
-                    batch, L, cdims, bonds, cores, outs, row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(),
-                    n_tail, ws.data_ptr(), ws_bytes, stream))
-            recs = list(out.unbind(0))
-            if first.mode == "DCT":
-                # the volumes sit back to back in `out`: their rows are the rows of one tall matrix, one launch
-                n = first._shape[-1]
-                rec_all = torch.empty_like(out)
-                _lib.check(lib.ndmps_idct_last_f32(out.data_ptr(), rec_all.data_ptr(), batch * (plan.numel // n), n,
-                                                   _dct_basis(n, device).data_ptr(), stream))
-                recs = list(rec_all.unbind(0))
-        if as_torch:
-            return recs
-        return [r.cpu().numpy() for r in recs]
+                    out = _idct_last(out, shape[-1])
+        return [o._result(r, as_torch, None) for o, r in zip(objs, out.unbind(0))]
 
     # ---------------------------------------------------------------- region decode
     def _region_values(self, plan):
@@ -1150,7 +1199,7 @@ class NDMPS:
         lib = _lib.load()
         mps = self.mps
         f64 = mps.dtype == torch.float64
-        keep, ptrs = mps._f64_ptrs() if f64 else mps._f32_ptrs()
+        keep, ptrs = mps._ptrs_as(torch.float64 if f64 else torch.float32)
         L = len(mps.cores)
         dims, bonds = _lib.i64_array(mps.dims), _lib.i64_array(mps.bonds)
         nodes, tiles = _lib.i64_array(plan.nodes), _lib.i64_array(plan.n_tiles)
@@ -1166,19 +1215,8 @@ class NDMPS:
         del keep
         return out
 
-    def _idct_rows(self, rows, n):
-        """Inverse DCT of the last axis on rows of length n (the region's rows in DCT mode)."""
-        torch = _torch()
-        lib = _lib.load()
-        f64 = rows.dtype == torch.float64
-        rec = torch.empty_like(rows)
-        idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
-        _lib.check(idct(rows.data_ptr(), rec.data_ptr(), rows.numel() // n, n,
-                        _dct_basis(n, rows.device, f64).data_ptr(), _lib.stream_ptr()))
-        return rec
-
-    def _region_result(self, res, as_torch, dtype):
-        """to_tensor's result types: float64 for fp64 cores, float32 otherwise; as_torch with bf16 cores in Std mode
+    def _result(self, res, as_torch, dtype):
+        """A decoded device tensor as what the caller asked for -- to_tensor's result types: float64 for fp64 cores, float32 otherwise; as_torch with bf16 cores in Std mode
         gives bf16 like to_tensor's bf16 chain (the NumPy result keeps the fp32 contraction unrounded)."""
         torch = _torch()
         if as_torch:
@@ -1205,11 +1243,9 @@ class NDMPS:
         transformed back, then indexed.  A region restricted only on the last axis costs a full decode there.
         """
         torch = _torch()
-        if self._shape is None:
-            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        shape = tuple(self._require_shape())
         from . import region as _region
 
-        shape = tuple(self._shape)
         idx, keep = _region.normalize_key(key, shape)
         if self.mode not in ("Std", "DCT"):
             return None
@@ -1224,9 +1260,9 @@ class NDMPS:
             else:
                 n = shape[-1]
                 rows = self._region_values(_region.plan_outer(shape, idx[:-1] + [np.arange(n, dtype=np.int64)]))
-                rec = self._idct_rows(rows, n).view(-1, n)
+                rec = _idct_last(rows, n).view(-1, n)
                 res = rec.index_select(1, torch.from_numpy(idx[-1]).to(device)).reshape(out_shape)
-        return self._region_result(res, as_torch, dtype)
+        return self._result(res, as_torch, dtype)
 
     def values_at(self, coords, as_torch: bool = False, dtype=None):
         """
@@ -1235,11 +1271,9 @@ class NDMPS:
         distinct row of the last axis that the points touch is decoded in full.
         """
         torch = _torch()
-        if self._shape is None:
-            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        shape = tuple(self._require_shape())
         from . import region as _region
 
-        shape = tuple(self._shape)
         pts = _region.normalize_points(coords, shape)
         if self.mode not in ("Std", "DCT"):
             return None
@@ -1261,20 +1295,19 @@ class NDMPS:
                     uniq, inv, lead = np.zeros(1, np.int64), np.zeros(N, np.int64), np.zeros((0, 1), np.int64)
                 full = np.concatenate([np.repeat(lead, n, axis=1), np.tile(np.arange(n, dtype=np.int64), uniq.size)[None]])
                 rows = self._region_values(_region.plan_points(shape, full))
-                rec = self._idct_rows(rows, n).view(-1, n)
+                rec = _idct_last(rows, n).view(-1, n)
                 sel = torch.from_numpy(inv.ravel() * n + pts[-1]).to(device)
                 res = rec.reshape(-1).index_select(0, sel)
-        return self._region_result(res, as_torch, dtype)
+        return self._result(res, as_torch, dtype)
 
     # ------------------------------------------------------------ block-averaged decode
     def _pool_levels(self, levels):
         """(factor_arr, normalised levels) for this object's shape; ValueError without one."""
-        if self._shape is None:
-            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
+        shape = self._require_shape()
         from . import pool as _pool
 
-        fa = _core.get_factorlist(tuple(self._shape))[0]
-        return fa, _pool.normalize_levels(levels, len(self._shape), fa.shape[0])
+        fa = _core.get_factorlist(tuple(shape))[0]
+        return fa, _pool.normalize_levels(levels, len(shape), fa.shape[0])
 
     def block_shape(self, levels):
         """Block size ``B_a = prod(factor_arr[L - levels[a]:, a])`` per axis: the voxels that ``downsample(levels)``
@@ -1352,22 +1385,8 @@ class NDMPS:
                 res = outs[0].view(plan.coarse_shape)
             else:
                 cores = self._rank_safe([o if o is not None else mps.cores[l] for l, o in enumerate(outs)])
-                chain = DeviceMPS(cores, _trusted=True)
                 cplan = _plan_for(plan.coarse_shape, device.index or 0, factor_arr=plan.out_factor)
-                cdims = _lib.i64_array(chain.dims)
-                n_tail = int(lib.ndmps_chain_tail_columns(len(cores), cdims)) if not f64 else 0
-                if n_tail > 0:
-                    res = torch.empty(plan.coarse_shape, dtype=torch.float32, device=device)
-                    with _span("chain"):
-                        chain.to_volume(res, n_tail, cplan.split_tables(n_tail, device))
-                else:
-                    with _span("chain"):
-                        dense = chain.to_dense()
-                    res = torch.empty(plan.coarse_shape, dtype=work, device=device)
-                    with _span("decode_permute"):
-                        _lib.check(lib.ndmps_decode_permute(cplan.handle, dense.data_ptr(), res.data_ptr(),
-                                                            dense.element_size(), stream))
-                    del dense
+                res = _decode_chain(DeviceMPS(cores, _trusted=True), cplan, plan.coarse_shape)
             if self.mode == "DCT" and lev[-1] < L:
                 n = int(self._shape[-1])
                 rows = res.numel() // n
@@ -1382,7 +1401,7 @@ class NDMPS:
                                     stream))
                     res = rec
                 else:
-                    res = self._idct_rows(res, n)
+                    res = _idct_last(res, n)
         return res.view(plan.out_shape)
 
     def downsample(self, levels=1, op: str = "mean", as_torch: bool = False, dtype=None):
@@ -1409,16 +1428,15 @@ class NDMPS:
             return None
         with _torch().cuda.device(self.mps.device):
             res = self._pooled(fa, lev, op)
-        return self._region_result(res, as_torch, dtype)
+        return self._result(res, as_torch, dtype)
 
     def _axis_reduce(self, axis, keepdims, op, as_torch, dtype):
         from . import pool as _pool
 
-        if self._shape is None:
-            raise ValueError("this NDMPS was not created by from_tensor; the tensor shape is unknown")
-        ndim = len(self._shape)
+        shape = self._require_shape()
+        ndim = len(shape)
         axes = _pool.normalize_axes(axis, ndim)
-        fa = _core.get_factorlist(tuple(self._shape))[0]
+        fa = _core.get_factorlist(tuple(shape))[0]
         lev = np.array([fa.shape[0] if a in axes else 0 for a in range(ndim)], dtype=np.int64)
         if self.mode not in ("Std", "DCT"):
             return None
@@ -1426,7 +1444,7 @@ class NDMPS:
             res = self._pooled(fa, lev, op)
             if not keepdims:
                 res = res.reshape([n for a, n in enumerate(res.shape) if a not in axes])
-        return self._region_result(res, as_torch, dtype)
+        return self._result(res, as_torch, dtype)
 
     def sum(self, axis=None, keepdims: bool = False, as_torch: bool = False, dtype=None):
         """``to_tensor().sum(axis=axis, keepdims=keepdims)`` without decoding the whole volume (``downsample`` with
