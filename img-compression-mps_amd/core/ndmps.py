@@ -1074,6 +1074,106 @@ class NDMPS:
         is unchanged."""
         return NDMPS.linear_combination([self], [1.0], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
 
+    # ------------------------------------------------------- Gram matrix and PCA of a series (core/series.py)
+    @staticmethod
+    def _series_args(objs, others):
+        """Checked lists and the C arguments of the ndmps_series_gram* calls."""
+        from . import lincomb as _lc
+        from . import series as _se
+
+        objs = list(objs)
+        rows = objs if others is None else objs + list(others)
+        for o in rows:
+            if not isinstance(o, NDMPS):
+                raise TypeError(f"gram takes NDMPS objects, not {type(o).__name__}")
+        _se.check_lists(len(objs), None if others is None else len(rows) - len(objs))
+        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
+                                   dims=o.mps.dims) for o in rows])
+        cols = objs if others is None else rows[len(objs):]
+
+        def side(lst):
+            L = lst[0].mps.L
+            return (_lib.i64_array([b for o in lst for b in o.mps.bonds]),
+                    (C.c_int * len(lst))(*[_lc.dtype_code(o.mps.dtype) for o in lst]),
+                    (C.c_void_p * (len(lst) * L))(*[c.data_ptr() for o in lst for c in o.mps.cores]))
+
+        sa = side(objs)
+        sb = sa if others is None else side(cols)
+        return objs, cols, _lib.i64_array(objs[0].mps.dims), sa, sb
+
+    @staticmethod
+    def gram_route(objs, others=None) -> str:
+        """Which path ``gram`` takes for these lists: "resident" (every inner bond <= 64: one launch, one workgroup
+        per pair), "batched" (larger bonds, equal in all objects) or "per-pair" (larger ragged bonds)."""
+        from . import series as _se
+
+        objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
+        return _se.ROUTES[_lib.check(_lib.load().ndmps_series_gram_route(len(objs), len(cols), objs[0].mps.L, c_dims,
+                                                                         sa[0], sb[0]))]
+
+    @staticmethod
+    def gram(objs, others=None, as_torch: bool = False):
+        """
+        The fp64 Gram matrix ``G[a, b] = objs[a].mps @ others[b].mps`` of a series, computed on the cores in one call
+        (csrc/series.hip); ``others=None`` gives the symmetric K x K matrix, where only a <= b is computed and
+        ``G[b, a]`` is a copy.  In Std and DCT mode ``G[a, b]`` is the voxel inner product of the two ``to_tensor()``
+        results (the DCT is orthonormal).  Covariance, correlation, squared distances and the temporal PCA of a
+        series (``pca``) are functions of G.  Storage types may mix; the same inputs give the same bits.  NumPy
+        array by default, device tensor with ``as_torch=True``.  No counterpart in the reference.
+
+        Raises TypeError for a non-NDMPS, ValueError for an empty list or objects that differ in qubit_size, shape,
+        mode, device or site dims (as ``linear_combination``).
+        """
+        torch = _torch()
+        lib = _lib.load()
+        objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
+        Ka, Kb, L = len(objs), len(cols), objs[0].mps.L
+        device = objs[0].mps.device
+        nbytes = _lib.check(lib.ndmps_series_gram_workspace_bytes(Ka, Kb, L, c_dims, sa[0], sb[0]))
+        with torch.cuda.device(device):
+            G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
+            ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+            with _span("gram"):
+                _lib.check(lib.ndmps_series_gram(Ka, Kb, 1 if others is None else 0, L, c_dims, sa[0], sa[1], sa[2],
+                                                 sb[0], sb[1], sb[2], G.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _lib.stream_ptr()))
+            del ws
+        return G if as_torch else G.cpu().numpy()
+
+    def inner(self, other) -> float:
+        """``<self, other>``: the entry of ``NDMPS.gram([self], [other])``."""
+        return float(NDMPS.gram([self], [other])[0, 0])
+
+    @staticmethod
+    def pca(objs, n_components=None, center: bool = True, cutoff: float = 0.0, max_bond=None, dtype=None):
+        """
+        Temporal PCA of a series without a decoded volume (core/series.py): from ``G = gram(objs)`` the centred Gram
+        matrix ``H G H = U diag(lam) U^T`` (host, fp64), ``sigma_k = sqrt(lam_k)``; component k is the unit volume
+        ``sum_a c_{a,k} objs[a]``, ``c_k = H u_k / sigma_k``, built by one ``linear_combination(objs, c_k, cutoff,
+        max_bond, dtype)`` on the original objects.  Kept: ``sigma_k`` above the storage floor (1e-6 for fp32 / bf16
+        work, 1e-8 for fp64) times ``max(sigma_0, largest frame norm)``, at most ``n_components``.  The entry of
+        ``u_k`` with the largest magnitude is positive.  Returns a ``SeriesPCA``: singular_values, explained_variance
+        (``lam / (K - 1)``, or ``lam / K`` uncentred), scores (K x r), weights (K x r), components (NDMPS) and mean
+        (``linear_combination(objs, [1/K] * K, cutoff, max_bond, dtype)`` when ``center``, else None).  Errors as
+        ``gram`` and ``linear_combination`` (the summed bonds of the series must not exceed 4096).
+        """
+        torch = _torch()
+        from . import lincomb as _lc
+        from . import series as _se
+
+        objs = list(objs)
+        _se.check_components(n_components)
+        _lc.check_args(max(len(objs), 1), [0.0] * max(len(objs), 1), cutoff, max_bond)
+        G = NDMPS.gram(objs)
+        K = len(objs)
+        f64 = dtype == torch.float64 or (dtype != torch.float32
+                                         and _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]))
+        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(f64))
+        components = [NDMPS.linear_combination(objs, W[:, k], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
+                      for k in range(len(sigma))]
+        mean = NDMPS.linear_combination(objs, [1.0 / K] * K, cutoff=cutoff, max_bond=max_bond, dtype=dtype) if center else None
+        return _se.SeriesPCA(sigma, _se.explained_variance(sigma, K, center), U * sigma[None, :], W, components, mean)
+
     def _scaled(self, c: float) -> "NDMPS":
         """A copy with site 0 multiplied by ``c`` (no rounding; bonds unchanged)."""
         cores = [t.clone() for t in self.mps.cores]

@@ -1,0 +1,424 @@
+// Gram matrix of a series of MPS (core/series.py, NDMPS.gram / inner / pca):  G[a, b] = <X^a, X^b>  for every pair of
+// two lists of chains over the same site dims, computed on the cores.
+//
+// For one pair the transfer matrix E_j (chi_{a,j} x chi_{b,j}, fp64, E_0 = [1]) moves through the chain as
+//     E_{j+1} = sum_i  A_j[:, i, :]^T ( E_j B_j[:, i, :] ),        G[a, b] = E_L[0, 0]
+// (`E B` first: the other association of oracle.mps.mps_overlap and of ndmps_overlap_*).  Pairs are independent.
+//
+// Resident route (every inner bond of both lists <= 64): ONE launch, one workgroup of four waves per pair, all L sites.
+//   LDS   Et  64 x 64 fp64  E_j transposed, Et[k][m] = E_j[m][k]            32 KiB
+//         Z   64 x 64 fp64  Z_i = E_j B_j[:, i, :], row-major               32 KiB      64 KiB: two workgroups per CU
+//   Both images have 512-byte rows with the 16-column block index XORed by the row's parity.  An operand read of
+//   v_mfma_f64_16x16x4_f64 takes 16 consecutive doubles of four consecutive rows; ds_read_b64 resolves banks per half
+//   wave (two rows), and the XOR puts the odd row on the other 128-byte half of the bank row: no conflict.
+//   Per physical index i:  phase 1, wave w forms column tile w of Z_i (four row tiles, 16 registers) with E from LDS
+//   as the A operand and the core of b from GLOBAL memory as the B operand; phase 2, wave w accumulates row tile w of
+//   E_{j+1} (four column tiles, kept in accumulators over all i) with the core of a from global memory as the A
+//   operand and Z_i from LDS as the B operand.  Departure from the planned design: the cores are not staged through
+//   LDS.  With this split of the tiles every core element is the operand of exactly one wave, so a copy in LDS would
+//   be written once and read once; instead each lane loads its <= 16 operands of a phase into registers one phase
+//   ahead (the core of a during phase 1, the core of b of i + 1 during phase 2), in the storage type (fp32, bf16,
+//   fp64: widening is exact).  LDS operand reads are fenced in groups of eight so that they do not pile up in registers.  Bonds that are not multiples of 16 are zero-padded in registers and LDS; tiles past a
+//   pair's own bonds are skipped.  Order of summation is fixed (k ascending inside a product, i ascending), nothing
+//   is shared between workgroups, and nothing waits.
+// General route (some inner bond > 64): every core widened to fp64 once, then per site and pair two products on
+//   ndmps_dgemm; when all chains of both lists have the same bonds the pairs go through ndmps_dgemm_batched in chunks
+//   of ndmps_gemm_batched_max().  The last product writes its 1 x 1 result into G.
+// The symmetric case computes a <= b and copies G[a, b] to G[b, a].
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+using ndmps::Arena;
+using ndmps::ceil_div;
+
+constexpr int kResident = 64;  // largest inner bond of the resident kernel
+constexpr int kLd = 64;        // row length of the LDS images (doubles)
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+struct SeriesArgs {
+  const void* const* cores_a;  // Ka x L
+  const void* const* cores_b;  // Kb x L
+  const int* bonds_a;          // Ka x (L + 1)
+  const int* bonds_b;          // Kb x (L + 1)
+  const int* codes_a;          // storage codes: 0 fp32, 1 bf16, 2 fp64
+  const int* codes_b;
+  const int* dims;             // L
+  double* G;                   // Ka x Kb
+  int Ka, Kb, L, symmetric;
+};
+
+// element (row, col) of a 64 x 64 LDS image: odd rows hold their 16-column blocks pairwise swapped
+__device__ __forceinline__ int img(int row, int col) { return row * kLd + (col ^ ((row & 1) << 4)); }
+
+// this lane's operands of one phase: core[4 ks + lr, i, col] for ks < 16, zero outside chi x chi2.  Branch-free per
+// element (a lane outside reads element 0 and discards it); the storage type is switched once per call.
+template <typename T>
+__device__ __forceinline__ void load_operands_as(double (&q)[16], const T* __restrict__ core, int chi, int d, int chi2, int i,
+                                                 int lr, int col, bool active) {
+  const bool col_ok = active && col < chi2;
+  const int64_t base = ((int64_t)lr * d + i) * chi2 + col, step = (int64_t)4 * d * chi2;
+  T raw[16];
+#pragma unroll
+  for (int ks = 0; ks < 16; ++ks) raw[ks] = core[(col_ok && 4 * ks + lr < chi) ? base + ks * step : 0];
+#pragma unroll
+  for (int ks = 0; ks < 16; ++ks) q[ks] = (col_ok && 4 * ks + lr < chi) ? ndmps::to_f64(raw[ks]) : 0.0;
+}
+__device__ __forceinline__ void load_operands(double (&q)[16], const void* core, int code, int chi, int d, int chi2, int i,
+                                              int lr, int col, bool active) {
+  if (code == 2) load_operands_as(q, (const double*)core, chi, d, chi2, i, lr, col, active);
+  else if (code == 1) load_operands_as(q, (const __bf16*)core, chi, d, chi2, i, lr, col, active);
+  else load_operands_as(q, (const float*)core, chi, d, chi2, i, lr, col, active);
+}
+
+__global__ void __launch_bounds__(256, 2) series_gram_resident_kernel(SeriesArgs g) {
+  const int a = (int)(blockIdx.x / (unsigned)g.Kb), b = (int)(blockIdx.x % (unsigned)g.Kb);
+  if (a >= g.Ka || (g.symmetric && a > b)) return;
+  __shared__ double Et[kLd * kLd];
+  __shared__ double Z[kLd * kLd];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
+  const int L = g.L;
+  const int* ba = g.bonds_a + (int64_t)a * (L + 1);
+  const int* bb = g.bonds_b + (int64_t)b * (L + 1);
+  const int code_a = g.codes_a[a], code_b = g.codes_b[b];
+
+  for (int e = tid; e < kLd * kLd; e += 256) Et[e] = e == 0 ? 1.0 : 0.0;  // E_0 = [1]
+  __syncthreads();
+
+  for (int j = 0; j < L; ++j) {
+    const int ca = ba[j], ca2 = ba[j + 1], cb = bb[j], cb2 = bb[j + 1], d = g.dims[j];
+    const void* A = g.cores_a[(int64_t)a * L + j];
+    const void* B = g.cores_b[(int64_t)b * L + j];
+    const int tiles_a = (ca + 15) >> 4, tiles_a2 = (ca2 + 15) >> 4, tiles_b2 = (cb2 + 15) >> 4;
+    const int steps_b = (cb + 3) >> 2, steps_a = (ca + 3) >> 2;
+    const bool own1 = wave < tiles_b2, own2 = wave < tiles_a2;  // this wave's tile of Z / of E' exists
+    const int col = wave * 16 + lc;
+
+    f64x4 acc[4];  // E_{j+1}: rows 16 wave + lr + 4 r, columns 16 nt + lc
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    double bq[16], aq[16];
+    load_operands(bq, B, code_b, cb, d, cb2, 0, lr, col, own1);
+
+    for (int i = 0; i < d; ++i) {
+      load_operands(aq, A, code_a, ca, d, ca2, i, lr, col, own2);
+      // ---- phase 1: Z_i[:, 16 wave ..] = E_j B_j[:, i, 16 wave ..]
+      f64x4 z[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) z[mt] = (f64x4){0.0, 0.0, 0.0, 0.0};
+      if (own1) {
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+          if (ks < steps_b) {
+            const int k = 4 * ks + lr;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+              if (mt < tiles_a) z[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Et[img(k, 16 * mt + lc)], bq[ks], z[mt], 0, 0, 0);
+          }
+          if (ks & 1) __builtin_amdgcn_sched_barrier(0);  // at most eight LDS operands in flight: no spill
+        }
+      }
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Z[img(16 * mt + lr + 4 * r, col)] = z[mt][r];
+      __syncthreads();
+      if (i + 1 < d) load_operands(bq, B, code_b, cb, d, cb2, i + 1, lr, col, own1);
+      // ---- phase 2: E_{j+1}[16 wave .., :] += A_j[:, i, 16 wave ..]^T Z_i
+      if (own2) {
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+          if (ks < steps_a) {
+            const int k = 4 * ks + lr;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+              if (nt < tiles_b2) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[ks], Z[img(k, 16 * nt + lc)], acc[nt], 0, 0, 0);
+          }
+          if (ks & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __syncthreads();
+    }
+    // E_{j+1} transposed into Et (every entry: the padding is zero in the accumulators)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Et[img(16 * nt + lc, 16 * wave + lr + 4 * r)] = acc[nt][r];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double v = Et[0];
+    g.G[(int64_t)a * g.Kb + b] = v;
+    if (g.symmetric && a != b) g.G[(int64_t)b * g.Kb + a] = v;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) widen_kernel(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
+}
+// G[b, a] <- G[a, b] for a < b (K x K)
+__global__ void __launch_bounds__(256) mirror_kernel(double* __restrict__ G, int64_t K) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < K * K; e += (int64_t)gridDim.x * 256) {
+    const int64_t r = e / K, c = e % K;
+    if (r > c) G[e] = G[c * K + r];
+  }
+}
+inline int grid1d(int64_t n) {
+  return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
+}
+
+enum { kRouteResident = 0, kRouteBatched = 1, kRoutePerPair = 2 };
+
+// Host plan: the checked arguments, the route and the workspace carve (a null arena counts bytes).
+struct Plan {
+  int Ka = 0, Kb = 0, L = 0, route = 0, chunk = 1;
+  std::vector<int64_t> dims;
+  const int64_t *ba = nullptr, *bb = nullptr;
+  int64_t emax = 1, zmax = 1;  // largest E_j and Z of any pair
+  int64_t chi_a(int a, int j) const { return ba[(int64_t)a * (L + 1) + j]; }
+  int64_t chi_b(int b, int j) const { return bb[(int64_t)b * (L + 1) + j]; }
+  int64_t core_a(int a, int j) const { return chi_a(a, j) * dims[j] * chi_a(a, j + 1); }
+  int64_t core_b(int b, int j) const { return chi_b(b, j) * dims[j] * chi_b(b, j + 1); }
+};
+
+int make_plan(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* ba, const int64_t* bb, Plan& p) {
+  NDMPS_REQUIRE(Ka >= 1 && Kb >= 1 && L >= 1 && h_dims && ba && bb, "bad series argument (Ka = %d, Kb = %d, L = %d)", Ka, Kb, L);
+  NDMPS_REQUIRE((int64_t)Ka * Kb <= INT32_MAX, "series of %d x %d pairs exceeds one grid", Ka, Kb);
+  p.Ka = Ka;
+  p.Kb = Kb;
+  p.L = L;
+  p.ba = ba;
+  p.bb = bb;
+  p.dims.assign(h_dims, h_dims + L);
+  for (int j = 0; j < L; ++j)
+    NDMPS_REQUIRE(p.dims[j] >= 1 && p.dims[j] <= INT32_MAX, "site %d: bad physical dim %lld", j, (long long)p.dims[j]);
+  int64_t top = 1, amax = 1, bmax = 1, a2max = 1, b2max = 1;
+  bool same = true;
+  for (int side = 0; side < 2; ++side) {
+    const int64_t* bl = side ? bb : ba;
+    for (int a = 0; a < (side ? Kb : Ka); ++a) {
+      const int64_t* row = bl + (int64_t)a * (L + 1);
+      NDMPS_REQUIRE(row[0] == 1 && row[L] == 1, "list %d, chain %d: the outer bonds must be 1", side, a);
+      for (int j = 0; j <= L; ++j) {
+        NDMPS_REQUIRE(row[j] >= 1 && row[j] <= (1 << 20), "list %d, chain %d, bond %d: bad bond %lld", side, a, j,
+                      (long long)row[j]);
+        top = std::max(top, row[j]);
+        same = same && row[j] == ba[j];
+      }
+    }
+  }
+  for (int j = 0; j < L; ++j) {  // bounds over all pairs: per site, largest factors of either list
+    amax = a2max = bmax = b2max = 1;
+    for (int a = 0; a < Ka; ++a) amax = std::max(amax, p.chi_a(a, j)), a2max = std::max(a2max, p.chi_a(a, j + 1));
+    for (int b = 0; b < Kb; ++b) bmax = std::max(bmax, p.chi_b(b, j)), b2max = std::max(b2max, p.chi_b(b, j + 1));
+    p.emax = std::max(p.emax, a2max * b2max);
+    p.zmax = std::max(p.zmax, amax * p.dims[j] * b2max);
+  }
+  p.route = top <= kResident ? kRouteResident : same ? kRouteBatched : kRoutePerPair;
+  p.chunk = p.route == kRouteBatched ? (int)std::min<int64_t>((int64_t)Ka * Kb, ndmps_gemm_batched_max()) : 1;
+  return NDMPS_OK;
+}
+
+struct Buffers {
+  // resident: the tables of SeriesArgs
+  const void** cores = nullptr;
+  int *bonds = nullptr, *codes = nullptr, *dims = nullptr;
+  // general: the widened cores (null where a core is fp64 already), and per pair of a chunk two E and one Z
+  std::vector<double*> wa, wb;
+  double *E[2] = {nullptr, nullptr}, *Z = nullptr;
+};
+
+void carve(const Plan& p, const int* codes_a, const int* codes_b, bool symmetric, Arena& ar, Buffers& b) {
+  const int64_t K = (int64_t)p.Ka + p.Kb;
+  if (p.route == kRouteResident) {
+    b.cores = ar.take<const void*>(K * p.L);
+    b.bonds = ar.take<int>(K * (p.L + 1));
+    b.codes = ar.take<int>(K);
+    b.dims = ar.take<int>(p.L);
+    return;
+  }
+  // workspace query (no codes): every core counted as if it had to be widened
+  b.wa.assign((size_t)p.Ka * p.L, nullptr);
+  b.wb.assign((size_t)p.Kb * p.L, nullptr);
+  for (int a = 0; a < p.Ka; ++a)
+    for (int j = 0; j < p.L; ++j)
+      if (!codes_a || codes_a[a] != 2) b.wa[(size_t)a * p.L + j] = ar.take<double>(p.core_a(a, j));
+  if (!symmetric || !codes_a)
+    for (int c = 0; c < p.Kb; ++c)
+      for (int j = 0; j < p.L; ++j)
+        if (!codes_b || codes_b[c] != 2) b.wb[(size_t)c * p.L + j] = ar.take<double>(p.core_b(c, j));
+  b.E[0] = ar.take<double>(p.emax * p.chunk);
+  b.E[1] = ar.take<double>(p.emax * p.chunk);
+  b.Z = ar.take<double>(p.zmax * p.chunk);
+}
+
+int widen(const void* src, int code, int64_t n, double* dst, hipStream_t s) {
+  if (code == 1)
+    hipLaunchKernelGGL(widen_kernel<__bf16>, dim3(grid1d(n)), dim3(256), 0, s, (const __bf16*)src, n, dst);
+  else
+    hipLaunchKernelGGL(widen_kernel<float>, dim3(grid1d(n)), dim3(256), 0, s, (const float*)src, n, dst);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
+
+int run_resident(const Plan& p, int symmetric, const int* codes_a, const void* const* cores_a, const int* codes_b,
+                 const void* const* cores_b, double* d_G, const Buffers& b, hipStream_t s) {
+  const int L = p.L, Ka = p.Ka, Kb = p.Kb;
+  std::vector<const void*> hc(cores_a, cores_a + (size_t)Ka * L);
+  hc.insert(hc.end(), cores_b, cores_b + (size_t)Kb * L);
+  std::vector<int> hb((size_t)(Ka + Kb) * (L + 1)), hk(codes_a, codes_a + Ka), hd(p.dims.begin(), p.dims.end());
+  for (size_t e = 0; e < (size_t)Ka * (L + 1); ++e) hb[e] = (int)p.ba[e];
+  for (size_t e = 0; e < (size_t)Kb * (L + 1); ++e) hb[(size_t)Ka * (L + 1) + e] = (int)p.bb[e];
+  hk.insert(hk.end(), codes_b, codes_b + Kb);
+  NDMPS_CHECK_HIP(hipMemcpyAsync(b.cores, hc.data(), hc.size() * sizeof(void*), hipMemcpyHostToDevice, s));
+  NDMPS_CHECK_HIP(hipMemcpyAsync(b.bonds, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  NDMPS_CHECK_HIP(hipMemcpyAsync(b.codes, hk.data(), hk.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  NDMPS_CHECK_HIP(hipMemcpyAsync(b.dims, hd.data(), hd.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  NDMPS_CHECK_HIP(hipStreamSynchronize(s));  // the host vectors go out of scope; nothing waits after the launch
+  SeriesArgs g;
+  g.cores_a = b.cores;
+  g.cores_b = b.cores + (size_t)Ka * L;
+  g.bonds_a = b.bonds;
+  g.bonds_b = b.bonds + (size_t)Ka * (L + 1);
+  g.codes_a = b.codes;
+  g.codes_b = b.codes + Ka;
+  g.dims = b.dims;
+  g.G = d_G;
+  g.Ka = Ka;
+  g.Kb = Kb;
+  g.L = L;
+  g.symmetric = symmetric;
+  // 1-D grid over the pairs (a, b) = (x / Kb, x % Kb): no 65535 limit; the symmetric case leaves a > b at once
+  hipLaunchKernelGGL(series_gram_resident_kernel, dim3((unsigned)((int64_t)Ka * Kb)), dim3(256), 0, s, g);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
+
+int run_general(const Plan& p, int symmetric, const int* codes_a, const void* const* cores_a, const int* codes_b,
+                const void* const* cores_b, double* d_G, const Buffers& b, hipStream_t s) {
+  const int L = p.L, Ka = p.Ka, Kb = p.Kb;
+  std::vector<const double*> A((size_t)Ka * L), B((size_t)Kb * L);
+  for (int a = 0; a < Ka; ++a)
+    for (int j = 0; j < L; ++j) {
+      const size_t e = (size_t)a * L + j;
+      A[e] = (const double*)cores_a[e];
+      if (codes_a[a] != 2) {
+        NDMPS_TRY(widen(cores_a[e], codes_a[a], p.core_a(a, j), b.wa[e], s));
+        A[e] = b.wa[e];
+      }
+    }
+  for (int c = 0; c < Kb; ++c)
+    for (int j = 0; j < L; ++j) {
+      const size_t e = (size_t)c * L + j;
+      if (symmetric) {
+        B[e] = A[e];
+        continue;
+      }
+      B[e] = (const double*)cores_b[e];
+      if (codes_b[c] != 2) {
+        NDMPS_TRY(widen(cores_b[e], codes_b[c], p.core_b(c, j), b.wb[e], s));
+        B[e] = b.wb[e];
+      }
+    }
+  std::vector<std::pair<int, int>> pairs;
+  for (int a = 0; a < Ka; ++a)
+    for (int c = symmetric ? a : 0; c < Kb; ++c) pairs.emplace_back(a, c);
+  const int chunk = p.chunk;
+  std::vector<const double*> pa(chunk), pb(chunk);
+  std::vector<double*> pc(chunk);
+  for (size_t p0 = 0; p0 < pairs.size(); p0 += chunk) {
+    const int n = (int)std::min<size_t>(chunk, pairs.size() - p0);
+    int cur = 0;
+    for (int j = 0; j < L; ++j) {
+      // shapes of the chunk: one pair, or pairs that share every bond
+      const int a0 = pairs[p0].first, c0 = pairs[p0].second;
+      const int64_t ca = p.chi_a(a0, j), ca2 = p.chi_a(a0, j + 1), cb = p.chi_b(c0, j), cb2 = p.chi_b(c0, j + 1), d = p.dims[j];
+      if (j > 0) {  // Z (ca x d cb2) = E_j (ca x cb) B_j (cb x d cb2); at site 0 E_0 = [1] and Z is the core itself
+        for (int q = 0; q < n; ++q) {
+          pa[q] = b.E[cur] + (int64_t)q * p.emax;
+          pb[q] = B[(size_t)pairs[p0 + q].second * L + j];
+          pc[q] = b.Z + (int64_t)q * p.zmax;
+        }
+        if (p.route == kRouteBatched)
+          NDMPS_TRY(ndmps_dgemm_batched(n, 0, 0, ca, d * cb2, cb, pa.data(), cb, pb.data(), d * cb2, pc.data(), d * cb2, s));
+        else
+          NDMPS_TRY(ndmps_dgemm(0, 0, ca, d * cb2, cb, pa[0], cb, pb[0], d * cb2, pc[0], d * cb2, s));
+      }
+      // E_{j+1} (ca2 x cb2) = (A_j viewed ca d x ca2)^T (Z viewed ca d x cb2); the last one is G[a, b]
+      for (int q = 0; q < n; ++q) {
+        const int a = pairs[p0 + q].first, c = pairs[p0 + q].second;
+        pa[q] = A[(size_t)a * L + j];
+        pb[q] = j > 0 ? b.Z + (int64_t)q * p.zmax : B[(size_t)c * L + j];
+        pc[q] = j + 1 == L ? d_G + (int64_t)a * Kb + c : b.E[cur ^ 1] + (int64_t)q * p.emax;
+      }
+      if (p.route == kRouteBatched)
+        NDMPS_TRY(ndmps_dgemm_batched(n, 1, 0, ca2, cb2, ca * d, pa.data(), ca2, pb.data(), cb2, pc.data(), cb2, s));
+      else
+        NDMPS_TRY(ndmps_dgemm(1, 0, ca2, cb2, ca * d, pa[0], ca2, pb[0], cb2, pc[0], cb2, s));
+      cur ^= 1;
+    }
+  }
+  if (symmetric) {
+    hipLaunchKernelGGL(mirror_kernel, dim3(grid1d((int64_t)Ka * Ka)), dim3(256), 0, s, d_G, (int64_t)Ka);
+    NDMPS_LAUNCH_CHECK();
+  }
+  return NDMPS_OK;
+}
+
+}  // namespace
+
+extern "C" int ndmps_series_gram_route(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                                       const int64_t* h_bonds_b) {
+  Plan p;
+  NDMPS_TRY(make_plan(Ka, Kb, L, h_dims, h_bonds_a, h_bonds_b, p));
+  return p.route;
+}
+
+extern "C" int64_t ndmps_series_gram_workspace_bytes(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                                                     const int64_t* h_bonds_b) {
+  Plan p;
+  NDMPS_TRY(make_plan(Ka, Kb, L, h_dims, h_bonds_a, h_bonds_b, p));
+  Arena ar(nullptr, 0);
+  Buffers b;
+  carve(p, nullptr, nullptr, false, ar, b);
+  return ndmps::round_up(ar.used, 256) + 256;
+}
+
+extern "C" int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                                 const int* h_codes_a, const void* const* h_cores_a, const int64_t* h_bonds_b,
+                                 const int* h_codes_b, const void* const* h_cores_b, double* d_G, void* d_ws,
+                                 int64_t ws_bytes, ndmps_stream_t stream) {
+  NDMPS_REQUIRE(h_codes_a && h_cores_a && h_codes_b && h_cores_b && d_G, "NULL series argument");
+  Plan p;
+  NDMPS_TRY(make_plan(Ka, Kb, L, h_dims, h_bonds_a, h_bonds_b, p));
+  symmetric = symmetric != 0;
+  if (symmetric) {
+    NDMPS_REQUIRE(Ka == Kb, "a symmetric series needs one list (Ka = %d, Kb = %d)", Ka, Kb);
+    for (int64_t e = 0; e < (int64_t)Ka * L; ++e)
+      NDMPS_REQUIRE(h_cores_a[e] == h_cores_b[e], "a symmetric series needs the same cores in both lists");
+    for (int64_t e = 0; e < (int64_t)Ka * (L + 1); ++e)
+      NDMPS_REQUIRE(h_bonds_a[e] == h_bonds_b[e], "a symmetric series needs the same bonds in both lists");
+  }
+  for (int side = 0; side < 2; ++side)
+    for (int a = 0; a < (side ? Kb : Ka); ++a) {
+      const int code = (side ? h_codes_b : h_codes_a)[a];
+      NDMPS_REQUIRE(code >= 0 && code <= 2, "list %d, chain %d: bad dtype code %d", side, a, code);
+      for (int j = 0; j < L; ++j)
+        NDMPS_REQUIRE((side ? h_cores_b : h_cores_a)[(int64_t)a * L + j], "list %d, chain %d, site %d: NULL core", side, a, j);
+    }
+  Arena ar(d_ws, ws_bytes);
+  Buffers b;
+  carve(p, h_codes_a, h_codes_b, symmetric, ar, b);
+  if (!d_ws || ar.used > ws_bytes) {
+    ndmps::set_error("series workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
+    return NDMPS_EWORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (p.route == kRouteResident) return run_resident(p, symmetric, h_codes_a, h_cores_a, h_codes_b, h_cores_b, d_G, b, s);
+  return run_general(p, symmetric, h_codes_a, h_cores_a, h_codes_b, h_cores_b, d_G, b, s);
+}

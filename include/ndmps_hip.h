@@ -547,6 +547,25 @@ int ndmps_lincomb_round(int K, int L, const int64_t* h_dims, const int64_t* h_bo
                         int64_t spec_stride, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Gram matrix of a series (no reference counterpart; core/series.py, csrc/series.hip): d_G[a, b] = <X^a, X^b> for
+ * every pair of two lists of chains with the same L site dims, fp64, row-major Ka x Kb on the device.
+ * h_bonds_*: K x (L + 1) (outer bonds 1); h_codes_*: storage codes (0 fp32, 1 bf16, 2 fp64); h_cores_*: K x L device
+ * pointers.  symmetric != 0: both lists are the same (same pointers); a <= b is computed and copied to [b, a].
+ * Route (ndmps_series_gram_route): 0 every inner bond <= 64, one launch with one workgroup per pair; 1 larger bonds,
+ * all chains with the same bonds, ndmps_dgemm_batched per site; 2 larger ragged bonds, ndmps_dgemm pair by pair.
+ * The same inputs give the same bits.  The result is left in d_G in stream order; route 0 waits for the upload of
+ * its task tables before it launches, nothing waits afterwards.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_series_gram_workspace_bytes(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                                          const int64_t* h_bonds_b);
+int ndmps_series_gram_route(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                            const int64_t* h_bonds_b);
+int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                      const int* h_codes_a, const void* const* h_cores_a, const int64_t* h_bonds_b,
+                      const int* h_codes_b, const void* const* h_cores_b, double* d_G, void* d_ws, int64_t ws_bytes,
+                      ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
