@@ -40,7 +40,8 @@ void set_error(const char* fmt, ...);
 static inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 static inline int64_t ceil_div(int64_t x, int64_t a) { return (x + a - 1) / a; }
 
-// bump allocator over a caller-provided device workspace (256-byte aligned pieces)
+// bump allocator over a caller-provided device workspace (256-byte aligned pieces); on no memory (p == NULL) take()
+// returns NULL and still advances `used`: a carve of Arena(nullptr, 0) is the size query of that carve
 struct Arena {
   char* base;
   int64_t size;
@@ -54,10 +55,8 @@ struct Arena {
     if (end > size || base == nullptr) return nullptr;
     return (T*)(base + off);
   }
+  bool fits() const { return base != nullptr && used <= size; }  // every take() so far returned memory
 };
-static inline int64_t arena_bytes(int64_t used, int64_t elem, int64_t count) {
-  return round_up(used, 256) + elem * count;
-}
 
 constexpr int kNumCU = 256;  // MI355X
 

@@ -45,7 +45,6 @@ inline double sweep_eig_tol(bool f64_storage = false) {
   return f64_storage ? 1e-15 : kSweepEigTol;  // fp64 data: iterate down to the rounding of the Gram matrix
 }
 
-using ndmps::arena_bytes;
 using ndmps::Arena;
 using ndmps::ceil_div;
 
@@ -86,31 +85,49 @@ __global__ void tail_norm_reduce_kernel(const double* __restrict__ partial, int 
   for (int b = 0; b < nblk; ++b) s += partial[(int64_t)b * t + j];
   out[j] = s;
 }
+// Both launches: *sums <- the device pointer of the t values |A v_j|^2.  Partials (nblk x t) and sums (t) live in `scratch`
+// (scratch_elems doubles): nblk = ceil(rows / 4) row blocks where they fit, else fewer blocks of more rows each (a tall
+// unfolding, e.g. 4096 rows of order 8 in an order-64 layout).
+template <typename T>
+int tail_norms(const T* A, int64_t rs, int64_t cs, int64_t rows, int64_t cols, const double* V, int64_t ldv, int64_t i0,
+               int64_t t, double* scratch, int64_t scratch_elems, double** sums, hipStream_t s) {
+  int nblk = (int)ceil_div(rows, 4);
+  if ((int64_t)nblk * t + t > scratch_elems) nblk = (int)((scratch_elems - t) / t);
+  NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= scratch_elems, "internal: no room for the tail norms (%lld x %lld)",
+                (long long)nblk, (long long)t);
+  *sums = scratch + (int64_t)nblk * t;
+  hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s, A, rs, cs,
+                     (int)rows, (int)cols, V, (int)ldv, (int)i0, (int)t, scratch);
+  hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, scratch, nblk, (int)t, *sums);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
 
 __global__ void set_scalar_f64_kernel(double* p, double v) { *p = v; }
 
-template <typename T = float>
-__global__ void __launch_bounds__(256) f32_to_f64_kernel(const T* __restrict__ x, int64_t n, double* y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    y[i] = ndmps::to_f64(x[i]);
+// ---- elementwise bodies: each is shared by a per-volume kernel and by its `_batched` twin, which resolves the volume's
+//      pointers from blockIdx.y first
+template <typename T>
+__device__ __forceinline__ void f32_to_f64_body(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
 }
-
-// core (k x n) fp32 <- first k columns of V (n x n fp64), transposed
-template <typename T = float>
-__global__ void __launch_bounds__(256)
-core_from_vectors_kernel(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core) {
+// core (k x n) <- first k columns of V (n x n fp64), transposed
+template <typename T>
+__device__ __forceinline__ void core_from_vectors_body(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core) {
   const int64_t total = k * n;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t i = e / n, c = e % n;
     core[e] = ndmps::from_f64<T>(V[c * n + i]);
   }
 }
-
-// out (rows x k) fp32 <- M (rows x ldm fp64)[:, :k] * scale[col]^power
-template <typename T = float>
-__global__ void __launch_bounds__(256)
-scale_cols_to_f32_kernel(const double* __restrict__ M, int64_t rows, int64_t ldm, int64_t k,
-                         const double* __restrict__ sigma, double power, T* __restrict__ out) {
+// s <- sqrt(max(w, 0))
+__device__ __forceinline__ void sqrt_clamp_body(const double* __restrict__ w, int64_t n, double* __restrict__ s) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s[i] = sqrt(fmax(w[i], 0.0));
+}
+// out (rows x k) <- M (rows x ldm fp64)[:, :k] * sigma[col]^power
+template <typename T>
+__device__ __forceinline__ void scale_cols_body(const double* __restrict__ M, int64_t rows, int64_t ldm, int64_t k,
+                                                const double* __restrict__ sigma, double power, T* __restrict__ out) {
   const int64_t total = rows * k;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t r = e / k, c = e % k;
@@ -118,18 +135,40 @@ scale_cols_to_f32_kernel(const double* __restrict__ M, int64_t rows, int64_t ldm
     out[e] = ndmps::from_f64<T>(sg > 0.0 ? M[r * ldm + c] * pow(sg, power) : 0.0);
   }
 }
-
-// out (k x n) fp32 <- M (k x n fp64) with row i scaled by sigma[i]^power
-template <typename T = float>
-__global__ void __launch_bounds__(256)
-scale_rows_to_f32_kernel(const double* __restrict__ M, int64_t k, int64_t n, const double* __restrict__ sigma,
-                         double power, T* __restrict__ out) {
+// out (k x n) <- M (k x n fp64) with row i scaled by sigma[i]^power
+template <typename T>
+__device__ __forceinline__ void scale_rows_body(const double* __restrict__ M, int64_t k, int64_t n,
+                                                const double* __restrict__ sigma, double power, T* __restrict__ out) {
   const int64_t total = k * n;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
-  {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const double sg = sigma[e / n];
     out[e] = ndmps::from_f64<T>(sg > 0.0 ? M[e] * pow(sg, power) : 0.0);
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) f32_to_f64_kernel(const T* __restrict__ x, int64_t n, double* y) {
+  f32_to_f64_body(x, n, y);
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+core_from_vectors_kernel(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core) {
+  core_from_vectors_body(V, n, k, core);
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+scale_cols_to_f32_kernel(const double* __restrict__ M, int64_t rows, int64_t ldm, int64_t k,
+                         const double* __restrict__ sigma, double power, T* __restrict__ out) {
+  scale_cols_body(M, rows, ldm, k, sigma, power, out);
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+scale_rows_to_f32_kernel(const double* __restrict__ M, int64_t k, int64_t n, const double* __restrict__ sigma,
+                         double power, T* __restrict__ out) {
+  scale_rows_body(M, k, n, sigma, power, out);
+}
+__global__ void __launch_bounds__(256) sqrt_clamp_kernel(const double* __restrict__ w, int64_t n, double* s) {
+  sqrt_clamp_body(w, n, s);
 }
 
 // in-place: M (rows x cols fp64), column c scaled by sqrt(max(w[c], 0))
@@ -145,13 +184,8 @@ scale_cols_sqrt_kernel(double* __restrict__ M, int64_t rows, int64_t cols, const
   }
 }
 
-__global__ void __launch_bounds__(256) sqrt_clamp_kernel(const double* __restrict__ w, int64_t n, double* s) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    s[i] = sqrt(fmax(w[i], 0.0));
-}
-
-// ---- the same small kernels for a whole lockstep group (blockIdx.y = volume): fp64 side arrays are strided in the
-//      workspace, volumes / carried matrices / cores come as pointers in the kernel arguments
+// ---- the same for a whole lockstep group (blockIdx.y = volume): fp64 side arrays are strided in the workspace,
+//      volumes / carried matrices / cores come as pointers in the kernel arguments
 constexpr int kSmallBatch = 64;
 struct BatchOps {
   const void* in[kSmallBatch];
@@ -159,53 +193,30 @@ struct BatchOps {
 };
 template <typename T>
 __global__ void __launch_bounds__(256) f32_to_f64_batched_kernel(BatchOps ops, int64_t n, double* __restrict__ y, int64_t y_stride) {
-  const T* x = static_cast<const T*>(ops.in[blockIdx.y]);
-  double* yb = y + (int64_t)blockIdx.y * y_stride;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) yb[i] = ndmps::to_f64(x[i]);
+  f32_to_f64_body(static_cast<const T*>(ops.in[blockIdx.y]), n, y + (int64_t)blockIdx.y * y_stride);
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
 core_from_vectors_batched_kernel(const double* __restrict__ V, int64_t v_stride, int64_t n, int64_t k, BatchOps ops) {
-  const double* Vb = V + (int64_t)blockIdx.y * v_stride;
-  T* core = static_cast<T*>(ops.out[blockIdx.y]);
-  const int64_t total = k * n;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int64_t i = e / n, c = e % n;
-    core[e] = ndmps::from_f64<T>(Vb[c * n + i]);
-  }
+  core_from_vectors_body(V + (int64_t)blockIdx.y * v_stride, n, k, static_cast<T*>(ops.out[blockIdx.y]));
 }
 __global__ void __launch_bounds__(256)
 sqrt_clamp_batched_kernel(const double* __restrict__ w, int64_t stride, int64_t n, double* __restrict__ sg) {
-  const double* wb = w + (int64_t)blockIdx.y * stride;
-  double* sb = sg + (int64_t)blockIdx.y * stride;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) sb[i] = sqrt(fmax(wb[i], 0.0));
+  sqrt_clamp_body(w + (int64_t)blockIdx.y * stride, n, sg + (int64_t)blockIdx.y * stride);
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
 scale_cols_to_f32_batched_kernel(const double* __restrict__ M, int64_t m_stride, int64_t rows, int64_t ldm, int64_t k,
                                  const double* __restrict__ sigma, int64_t s_stride, double power, BatchOps ops) {
-  const double* Mb = M + (int64_t)blockIdx.y * m_stride;
-  const double* sb = sigma + (int64_t)blockIdx.y * s_stride;
-  T* out = static_cast<T*>(ops.out[blockIdx.y]);
-  const int64_t total = rows * k;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int64_t r = e / k, c = e % k;
-    const double sg = sb[c];
-    out[e] = ndmps::from_f64<T>(sg > 0.0 ? Mb[r * ldm + c] * pow(sg, power) : 0.0);
-  }
+  scale_cols_body(M + (int64_t)blockIdx.y * m_stride, rows, ldm, k, sigma + (int64_t)blockIdx.y * s_stride, power,
+                  static_cast<T*>(ops.out[blockIdx.y]));
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
 scale_rows_to_f32_batched_kernel(const double* __restrict__ M, int64_t m_stride, int64_t k, int64_t n,
                                  const double* __restrict__ sigma, int64_t s_stride, double power, BatchOps ops) {
-  const double* Mb = M + (int64_t)blockIdx.y * m_stride;
-  const double* sb = sigma + (int64_t)blockIdx.y * s_stride;
-  T* out = static_cast<T*>(ops.out[blockIdx.y]);
-  const int64_t total = k * n;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const double sg = sb[e / n];
-    out[e] = ndmps::from_f64<T>(sg > 0.0 ? Mb[e] * pow(sg, power) : 0.0);
-  }
+  scale_rows_body(M + (int64_t)blockIdx.y * m_stride, k, n, sigma + (int64_t)blockIdx.y * s_stride, power,
+                  static_cast<T*>(ops.out[blockIdx.y]));
 }
 
 // ------------------------------------------------------------ merged trailing sites (bond-capped sweep)
@@ -425,8 +436,49 @@ struct SweepLayout {
   int64_t transpose_bytes = 0;  // bf16 path: transposed copy of the merged basis
   bool device_rank = false;   // every site on the direct solver: ranks decided on the device, padded cores
   int64_t spec_stride = 0;    // singular values kept per site and volume on the device
-  int64_t workspace = 0;      // for the batch size it was computed for
+  int L = 0, batch = 0;       // what it was computed for
+  int elem_bytes = 4;         // storage element as the workspace counts it: 4 (fp32 and bf16) or 8 (fp64)
+  int64_t eig_bytes = 0;      // workspace of the eigen-solvers
+  int64_t workspace = 0;      // sum of the pieces carve_sweep() takes
 };
+
+// The sweep's workspace, piece by piece.  This is the only description of it: the size query carves an arena without
+// memory (sweep_layout), the sweep carves the caller's.  Storage-type buffers are taken at lay.elem_bytes per element.
+struct SweepBuffers {
+  void* other;           // second carry buffer per volume (storage type)
+  double *G, *V;         // Gram matrices; eigenvectors V / U (small_max^2 per volume)
+  double *w, *sig;       // eigenvalues, singular values (small_max per volume)
+  char *ev_ws, *gram_ws; // eigen-solver and Gram workspaces (the latter shared, stream-ordered)
+  double *A64, *UtA;     // wide unfoldings in fp64 and U_k^T A64, per volume
+  double *Graw, *Tm;     // merged run: raw Gram, T = Graw B
+  double* Wm[2];         // merged run: accumulated basis W, ping and pong
+  void* W32;             // ... and its copy in the storage type for the projection
+  char* tws;             // bf16 products: transposed copy of the merged basis
+  int *d_ranks, *d_status;  // device ranks and solver status, [site][volume] each
+  double* d_spec;        // device spectra per site
+};
+void carve_sweep(Arena& ar, const SweepLayout& lay, SweepBuffers& b) {
+  const int64_t batch = lay.batch, sq = lay.small_max * lay.small_max, raw = lay.merge_n * lay.merge_n,
+                basis = lay.merge_n * lay.merge_w;
+  b.other = ar.take<char>(lay.elem_bytes * batch * lay.numel);
+  b.G = ar.take<double>(batch * sq);
+  b.V = ar.take<double>(batch * sq);
+  b.w = ar.take<double>(batch * lay.small_max);
+  b.sig = ar.take<double>(batch * lay.small_max);
+  b.ev_ws = ar.take<char>(lay.eig_bytes);
+  b.gram_ws = ar.take<char>(lay.gram_ws);
+  b.A64 = ar.take<double>(batch * lay.wide_elems);
+  b.UtA = ar.take<double>(batch * lay.wide_elems);
+  b.Graw = ar.take<double>(batch * raw);
+  b.Tm = ar.take<double>(batch * raw);
+  b.Wm[0] = ar.take<double>(batch * basis);
+  b.Wm[1] = ar.take<double>(batch * basis);
+  b.W32 = ar.take<char>(lay.elem_bytes * batch * basis);
+  b.tws = ar.take<char>(lay.transpose_bytes);
+  b.d_ranks = ar.take<int>((int64_t)2 * lay.L * batch);
+  b.d_status = b.d_ranks ? b.d_ranks + (int64_t)lay.L * batch : nullptr;
+  b.d_spec = ar.take<double>((int64_t)lay.L * batch * lay.spec_stride);
+}
 
 int sweep_layout(int L, const int64_t* dims, int64_t max_bond, int batch, SweepLayout& out, int elem_bytes = 4) {
   NDMPS_REQUIRE(L >= 1 && L <= 64, "L=%d outside [1, 64]", L);
@@ -473,27 +525,15 @@ int sweep_layout(int L, const int64_t* dims, int64_t max_bond, int batch, SweepL
   for (int i = 1; i < L && out.device_rank; ++i)
     if (std::min(left[i], dims[i] * out.max_bonds[i + 1]) > ndmps_syevd_topk_max_n()) out.device_rank = false;
   out.spec_stride = max_bond > 0 ? std::min<int64_t>(max_bond, out.small_max) : 0;
-  const int64_t sq = out.small_max * out.small_max;
-  int64_t used = 0;
-  used = arena_bytes(used, elem_bytes, (int64_t)batch * out.numel);     // second carry buffer per volume
-  used = arena_bytes(used, 8, (int64_t)batch * sq);                     // G
-  used = arena_bytes(used, 8, (int64_t)batch * sq);                     // V / U
-  used = arena_bytes(used, 8, (int64_t)batch * out.small_max);          // w
-  used = arena_bytes(used, 8, (int64_t)batch * out.small_max);          // sigma
-  used = arena_bytes(used, 1, eig_workspace_bytes(out.small_max, batch, max_bond));
-  used = arena_bytes(used, 1, out.gram_ws);                             // shared, stream-ordered
-  used = arena_bytes(used, 8, (int64_t)batch * out.wide_elems);         // A64 per volume
-  used = arena_bytes(used, 8, (int64_t)batch * out.wide_elems);         // U_k^T A64 per volume
-  used = arena_bytes(used, 8, (int64_t)batch * out.merge_n * out.merge_n);      // raw Gram of the merged run
-  used = arena_bytes(used, 8, (int64_t)batch * out.merge_n * out.merge_n);      // T = Graw B
-  used = arena_bytes(used, 8, (int64_t)batch * out.merge_n * out.merge_w);      // accumulated basis W (ping)
-  used = arena_bytes(used, 8, (int64_t)batch * out.merge_n * out.merge_w);      // (pong)
-  used = arena_bytes(used, elem_bytes, (int64_t)batch * out.merge_n * out.merge_w);  // copy in the storage type for the projection
+  out.L = L;
+  out.batch = batch;
+  out.elem_bytes = elem_bytes;
+  out.eig_bytes = eig_workspace_bytes(out.small_max, batch, max_bond);
   out.transpose_bytes = ndmps_gemm_bf16_workspace_bytes(0, std::max<int64_t>(out.merge_w, 1), std::max<int64_t>(out.merge_n, 1));
-  used = arena_bytes(used, 1, out.transpose_bytes);
-  used = arena_bytes(used, 4, (int64_t)2 * L * batch);                          // device ranks, status per site
-  used = arena_bytes(used, 8, (int64_t)L * batch * out.spec_stride);            // device spectra per site
-  out.workspace = ndmps::round_up(used, 256) + 256;
+  Arena sizing(nullptr, 0);  // a carve on no memory: only `used` advances
+  SweepBuffers unused;
+  carve_sweep(sizing, out, unused);
+  out.workspace = ndmps::round_up(sizing.used, 256) + 256;
   return NDMPS_OK;
 }
 
@@ -528,9 +568,10 @@ extern "C" int64_t ndmps_tt_sweep_batched_workspace_bytes_f64(int batch, int L, 
   return lay.workspace;
 }
 
-// All volumes of the batch have the same site dims; they advance through the sites in lockstep
-// so that every site's eigenproblems are solved by ONE batched Jacobi (its sequential depth is
-// the cost of the path); Gram / projection launches stay per volume (they fill the chip alone).
+// All volumes of the batch have the same site dims; they advance through the sites in lockstep so that every site's
+// eigenproblems are solved by ONE batched solve (its sequential depth is the cost of the path).  While the volumes
+// of a group stay in the same state their Gram matrices, cores and projections are one launch per step as well
+// (Sweep::uniform); a group whose ranks have diverged goes volume by volume.
 namespace {
 // element-type dispatch of the two streaming products of the sweep
 inline int gram_T(const float* A, int64_t m, int64_t n, int64_t lda, double* G, void* ws, int64_t wsb, hipStream_t s) {
@@ -704,340 +745,379 @@ int retry_without_team(F&& sweep) {
   return rc;
 }
 
+// One TT-SVD sweep over a lockstep group of `batch` volumes: the arguments, the layout, the carved workspace and the
+// per-volume state, with one member function per stage.  sweep_impl() below drives them:
+//
+//   prepare()                   argument checks, layout, workspace carve, initial state
+//   merged_run()                sites merge_from .. L-1 from ONE Gram pass and ONE projection pass:
+//     merged_raw_gram()           the raw Gram of the group
+//     merged_site_gram(i)         G_i = B^T G_raw B (batched fp64 products, or merge_stage1 / merge_stage2)
+//     merged_basis_and_core(i)    W_i = B V_i and the core of site i
+//     merged_project()            carry = A_raw W
+//   then for every remaining site i, right to left:
+//     site_gram(i)                small-side Gram matrices: one launch for the group, the wide pair, or per volume
+//     solve_site(i, have_a)       the eigenproblems of the site and the rank of every volume:
+//       solve_on_device()           ranks decided on the device (no host round trip)
+//       solve_direct()              eigenvalues to the host, rank decision, kept vectors (direct solver)
+//       measure_doubt()             singular values the eigenvalues cannot resolve, measured as |A v|
+//       solve_jacobi()              the block Jacobi, also as the redo of a direct solve that lost rank
+//     site_core_and_carry(i)      core and carried matrix: core_and_carry_uniform() or core_and_carry_volume()
+//   finish()                    the site-0 copy; ranks and spectra back from the device, or their async enqueue
+//
+// Every stage enqueues on `s` in program order; the host waits only where eigenvalues or tail norms are fetched and in
+// finish().
 template <typename T>
-int sweep_impl(int batch, T* const* h_dense, int L, const int64_t* h_dims, double cutoff, int64_t max_bond,
-               T* const* h_cores, const int64_t* h_core_offsets, int64_t* h_bonds_out, double* h_spectra,
-               const int64_t* h_spec_offsets, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream,
-               const SweepSource* src = nullptr, const SweepAsync* async = nullptr) {
-  NDMPS_REQUIRE(h_dense && h_dims && h_cores && h_core_offsets && h_bonds_out, "NULL sweep argument");
-  NDMPS_REQUIRE(cutoff >= 0.0, "cutoff must be non-negative");
+struct Sweep {
+  // ---- arguments
+  int batch;
+  T* const* h_dense;
+  int L;
+  const int64_t* h_dims;
+  double cutoff;
+  int64_t max_bond;
+  T* const* h_cores;
+  const int64_t* h_core_offsets;
+  int64_t* h_bonds_out;
+  double* h_spectra;
+  const int64_t* h_spec_offsets;
+  void* d_ws;
+  int64_t ws_bytes;
+  hipStream_t s;
+  const SweepSource* src;
+  const SweepAsync* async;
+  // ---- layout and workspace
   SweepLayout lay;
-  NDMPS_TRY(sweep_layout(L, h_dims, max_bond, batch, lay, sizeof(T) == 8 ? 8 : 4));
-  if (d_ws == nullptr || ws_bytes < lay.workspace) {
-    ndmps::set_error("sweep workspace too small: %lld < %lld", (long long)ws_bytes, (long long)lay.workspace);
-    return NDMPS_EWORKSPACE;
-  }
-  for (int b = 0; b < batch; ++b) NDMPS_REQUIRE(h_dense[b] && h_cores[b], "NULL volume or core arena %d", b);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t sq = lay.small_max * lay.small_max;
-  Arena ar(d_ws, ws_bytes);
-  T* other = ar.take<T>((int64_t)batch * lay.numel);
-  double* G = ar.take<double>((int64_t)batch * sq);
-  double* V = ar.take<double>((int64_t)batch * sq);
-  double* w = ar.take<double>((int64_t)batch * lay.small_max);
-  double* sig = ar.take<double>((int64_t)batch * lay.small_max);
-  const int64_t ev_ws_bytes = eig_workspace_bytes(lay.small_max, batch, max_bond);
-  char* ev_ws = ar.take<char>(ev_ws_bytes);
-  char* gram_ws = ar.take<char>(lay.gram_ws);
-  double* A64 = ar.take<double>((int64_t)batch * lay.wide_elems);
-  double* UtA = ar.take<double>((int64_t)batch * lay.wide_elems);
-  NDMPS_REQUIRE(other && G && V && w && sig && ev_ws && gram_ws && A64 && UtA, "workspace carve failed");
+  SweepBuffers ws;
+  int64_t sq = 0;          // small_max^2: doubles per volume in G and V
+  int64_t spec_total = 0;  // spectrum values per volume in h_spectra
+  // ---- per-volume state
+  std::vector<T*> cur, nxt;                 // carried matrix and the buffer the next one goes to
+  std::vector<int64_t> chi_r, cur_elems;    // bond to the right of the current site; elements of cur
+  std::vector<int64_t> eig_n, kept, doubt;  // order of the site's eigenproblem, kept rank, first eigenvalue in doubt
+  std::vector<double> host_w;               // eigenvalues on the host, small_max per volume
 
-  double* Graw = ar.take<double>((int64_t)batch * lay.merge_n * lay.merge_n);
-  double* Tm = ar.take<double>((int64_t)batch * lay.merge_n * lay.merge_n);
-  double* Wm[2] = {ar.take<double>((int64_t)batch * lay.merge_n * lay.merge_w),
-                   ar.take<double>((int64_t)batch * lay.merge_n * lay.merge_w)};
-  T* W32 = ar.take<T>((int64_t)batch * lay.merge_n * lay.merge_w);
-  const int64_t tws_bytes = lay.transpose_bytes;
-  char* tws = ar.take<char>(tws_bytes);
-  int* d_ranks = ar.take<int>((int64_t)2 * L * batch);
-  int* d_status = d_ranks ? d_ranks + (int64_t)L * batch : nullptr;
-  double* d_spec = ar.take<double>((int64_t)L * batch * lay.spec_stride);
-  const bool dev_rank = lay.device_rank;
-  NDMPS_REQUIRE(d_ranks && (d_spec || lay.spec_stride == 0), "workspace carve failed");
-  NDMPS_REQUIRE(Graw && Tm && Wm[0] && Wm[1] && W32 && tws, "workspace carve failed");
-
-  std::vector<T*> cur(batch), nxt(batch);
-  std::vector<int64_t> chi_r(batch, 1), cur_elems(batch, lay.numel), eig_n(batch), kept(batch);
-  if (src) {
-    // h_dense[b] is the C-order volume and stays untouched: the carried matrices ping-pong between the halves
-    // of the workspace buffer (the first one is already <= half the tensor)
-    NDMPS_REQUIRE(lay.merge_from < L && src->n_cols == lay.merge_n &&
-                      (lay.numel / lay.merge_n) * lay.merge_w <= lay.numel / 2,
-                  "the fused reshape stage needs a merged run of %lld columns (see ndmps_tt_merge_columns)",
-                  (long long)src->n_cols);
-  }
-  for (int b = 0; b < batch; ++b) {
-    cur[b] = h_dense[b];
-    nxt[b] = other + (int64_t)b * lay.numel;
-    h_bonds_out[(int64_t)b * (L + 1)] = 1;
-    h_bonds_out[(int64_t)b * (L + 1) + L] = 1;
-  }
-  const int64_t spec_total = h_spec_offsets ? h_spec_offsets[L] : 0;
-  std::vector<double> host_w((size_t)batch * lay.small_max);
-  std::vector<int> eig_status;
-  std::vector<int64_t> doubt;  // first eigenvalue in doubt per matrix (direct solver, every eigenpair wanted)
-
-  // One batched eigen-solve for site i on the matrices G[b] (order eig_n[b], ld eig_n[b]): eigenvalues to the
-  // host, rank decision per volume (kept[b]), then the kept eigenvectors in the columns of V[b].
-  auto solve_site = [&](int i, bool have_a = false) -> int {
-    int sweeps = 0;
-    int64_t site_n = 0;
-    for (int b = 0; b < batch; ++b) site_n = std::max(site_n, eig_n[b]);
-    const bool topk = use_topk(site_n, max_bond);
-    const int64_t k_cap = std::min<int64_t>(max_bond, site_n);
-    if (dev_rank) {
-      // no host round trip: eigenvalues -> rank (device) -> k_b eigenvectors, the other columns up to the cap zero
-      NDMPS_TRY(ndmps_syevd_topk_values_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, k_cap, ev_ws,
-                                            ev_ws_bytes, s));
-      NDMPS_TRY(ndmps_syevd_topk_vectors_auto_f64(batch, eig_n.data(), k_cap, std::max(cutoff, cutoff_floor<T>()),
-                                                  d_ranks + (int64_t)i * batch, d_spec + (int64_t)i * batch * lay.spec_stride,
-                                                  lay.spec_stride, d_status + (int64_t)i * batch, ev_ws, ev_ws_bytes, s));
-      for (int b = 0; b < batch; ++b) kept[b] = k_cap;
-      return NDMPS_OK;
-    }
-    bool full = !topk && use_direct_full(lay.small_max, batch, max_bond);  // every eigenpair above the cutoff, direct solver
-    if (topk) {
-      NDMPS_TRY(ndmps_syevd_topk_values_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, k_cap, ev_ws,
-                                            ev_ws_bytes, s));
-      // the host waits for the eigenvalues anyway: a resident launch that gave up is redone on the column launches
-      NDMPS_TRY(ndmps_syevd_topk_recover_f64(batch, eig_n.data(), k_cap, ev_ws, ev_ws_bytes, nullptr, s));
-    } else if (full) {
-      NDMPS_TRY(ndmps_syevd_topk_values_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, lay.small_max, ev_ws,
-                                            ev_ws_bytes, s));
-      NDMPS_TRY(ndmps_syevd_topk_recover_f64(batch, eig_n.data(), lay.small_max, ev_ws, ev_ws_bytes, nullptr, s));
-    }
-    if (topk || full) {
-      NDMPS_CHECK_HIP(hipMemcpyAsync(host_w.data(), w, sizeof(double) * batch * lay.small_max, hipMemcpyDeviceToHost, s));
-      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-      if (full) {
-        // eigenvalues in doubt (direct_doubt_from): with the unfolding at hand their singular values are measured
-        // as |A v| behind the solve (below); without it (merged run) the Jacobi decides (G is untouched)
-        const double c = std::max(cutoff, cutoff_floor<T>());
-        doubt.assign(batch, 0);
-        for (int b = 0; b < batch; ++b) {
-          doubt[b] = direct_doubt_from(host_w.data() + (int64_t)b * lay.small_max, eig_n[b], c);
-          if (doubt[b] < eig_n[b] && !have_a) full = false;
-        }
-      }
-    }
-    if (!topk && !full) {
-      NDMPS_TRY(ndmps_syevj_batched_values_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, sweep_eig_tol(sizeof(T) == 8),
-                                               ev_ws, ev_ws_bytes, &sweeps, s));
-      NDMPS_CHECK_HIP(hipMemcpyAsync(host_w.data(), w, sizeof(double) * batch * lay.small_max, hipMemcpyDeviceToHost, s));
-      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-    }
-    for (int b = 0; b < batch; ++b) {
-      const int64_t small = eig_n[b];
-      std::vector<double> sv(host_w.begin() + (int64_t)b * lay.small_max,
-                             host_w.begin() + (int64_t)b * lay.small_max + small);
-      for (auto& x : sv) x = sqrt(std::max(x, 0.0));
-      kept[b] = kept_rank(sv, cutoff, max_bond, cutoff_floor<T>());
-      if (full && doubt[b] < small) kept[b] = small;  // every vector first; the rank follows from |A v| below
-      if (h_spectra && h_spec_offsets) {
-        // the layout reserves min(m, d_i max_bond_{i+1}) values for the bond; a merged site may be larger
-        const int64_t room = h_spec_offsets[i + 1] - h_spec_offsets[i];
-        memcpy(h_spectra + (int64_t)b * spec_total + h_spec_offsets[i], sv.data(),
-               std::min(small, room) * sizeof(double));
-      }
-    }
-    if (topk || full) {
-      eig_status.assign(batch, 0);
-      NDMPS_TRY(ndmps_syevd_topk_vectors_f64(batch, eig_n.data(), kept.data(), topk ? k_cap : lay.small_max, ev_ws, ev_ws_bytes,
-                                             eig_status.data(), s));
-      bool redo = false;
-      for (int b = 0; b < batch; ++b)
-        if (eig_status[b] != 0) {
-          if (!full) return solver_failed(i, b, eig_status[b]);
-          redo = true;  // the wide block lost rank (a cluster tighter than the shifts resolve): the Jacobi has no such case
-        }
-      if (redo) {
-        NDMPS_TRY(ndmps_syevj_batched_values_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max,
-                                                 sweep_eig_tol(sizeof(T) == 8), ev_ws, ev_ws_bytes, &sweeps, s));
-        NDMPS_CHECK_HIP(hipMemcpyAsync(host_w.data(), w, sizeof(double) * batch * lay.small_max, hipMemcpyDeviceToHost, s));
-        NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < batch; ++b) {
-          std::vector<double> sv(host_w.begin() + (int64_t)b * lay.small_max, host_w.begin() + (int64_t)b * lay.small_max + eig_n[b]);
-          for (auto& x : sv) x = sqrt(std::max(x, 0.0));
-          kept[b] = kept_rank(sv, cutoff, max_bond, cutoff_floor<T>());
-        }
-        NDMPS_TRY(ndmps_syevj_batched_vectors_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, kept.data(), ev_ws,
-                                                  ev_ws_bytes, s));
-      } else if (full) {
-        // ---- singular values in doubt, measured: s_j = |A v_j| (or |A^T u_j|) for the eigenvectors from doubt[b] on;
-        //      G (free now) is the scratch.  The kept rank = the vectors in front + those whose s_j passes the cutoff.
-        for (int b = 0; b < batch; ++b) {
-          const int64_t small = eig_n[b], i0 = doubt[b], t = small - i0;
-          if (t <= 0) continue;
-          const int64_t n = h_dims[i] * chi_r[b], m = cur_elems[b] / n;
-          const bool right = n <= m;  // G = A^T A: vectors in R^n, |A v|; else G = A A^T: |A^T u|
-          const int rows = (int)(right ? m : n), cols = (int)(right ? n : m);
-          // partials (nblk x t) and sums (t) live in this volume's G (sq doubles): a tall unfolding (rows / 4 row blocks
-          // beyond what fits, e.g. 4096 rows of order 8 in an order-64 layout) takes fewer blocks of more rows each
-          int nblk = (int)ceil_div(rows, 4);
-          if ((int64_t)nblk * t + t > sq) nblk = (int)((sq - t) / t);
-          double* partial = G + (int64_t)b * sq;
-          NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= sq, "internal: no room for the tail norms (%lld x %lld)",
-                        (long long)nblk, (long long)t);
-          double* out = partial + (int64_t)nblk * t;
-          hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
-                             (const T*)cur[b], right ? n : (int64_t)1, right ? (int64_t)1 : n, rows, cols,
-                             (const double*)(V + (int64_t)b * sq), (int)small, (int)i0, (int)t, partial);
-          hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, partial, nblk, (int)t, out);
-          NDMPS_LAUNCH_CHECK();
-          std::vector<double> s2((size_t)t);
-          NDMPS_CHECK_HIP(hipMemcpyAsync(s2.data(), out, sizeof(double) * t, hipMemcpyDeviceToHost, s));
-          NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-          const double s0 = sqrt(std::max(host_w[(int64_t)b * lay.small_max], 0.0));
-          const double c = std::max(cutoff, cutoff_floor<T>());
-          int64_t k = i0;
-          for (int64_t j = 0; j < t; ++j) k += sqrt(std::max(s2[(size_t)j], 0.0)) > c * s0;
-          k = std::max<int64_t>(k, 1);
-          if (max_bond > 0) k = std::min(k, max_bond);
-          kept[b] = std::min(k, small);
-          if (h_spectra && h_spec_offsets) {
-            const int64_t room = h_spec_offsets[i + 1] - h_spec_offsets[i];
-            for (int64_t j = 0; j < t && i0 + j < room; ++j)
-              h_spectra[(int64_t)b * spec_total + h_spec_offsets[i] + i0 + j] = sqrt(std::max(s2[(size_t)j], 0.0));
-          }
-        }
-      }
-    } else {
-      NDMPS_TRY(ndmps_syevj_batched_vectors_f64(batch, G, sq, eig_n.data(), V, sq, w, lay.small_max, kept.data(),
-                                                ev_ws, ev_ws_bytes, s));
-    }
-    return NDMPS_OK;
-  };
+  double rel_cutoff() const { return std::max(cutoff, cutoff_floor<T>()); }
+  T* core(int b, int i) const { return h_cores[b] + h_core_offsets[i]; }
+  double* Gb(int b) const { return ws.G + (int64_t)b * sq; }
+  double* Vb(int b) const { return ws.V + (int64_t)b * sq; }
 
   // every volume in the same state (always so when the ranks are decided on the device): the per-volume launches of
   // a site become one launch each
-  auto uniform = [&]() {
+  bool uniform() const {
     if (batch < 2) return false;
     for (int b = 1; b < batch; ++b)
       if (chi_r[b] != chi_r[0] || cur_elems[b] != cur_elems[0]) return false;
     return true;
-  };
-  auto uniform_kept = [&]() {
+  }
+  bool uniform_kept() const {
     for (int b = 1; b < batch; ++b)
       if (kept[b] != kept[0] || eig_n[b] != eig_n[0]) return false;
     return true;
-  };
+  }
+  // base + b stride for every volume: the pointer table of a batched product
+  std::vector<double*> strided(double* base, int64_t stride) const {
+    std::vector<double*> p(batch);
+    for (int b = 0; b < batch; ++b) p[b] = base + (int64_t)b * stride;
+    return p;
+  }
+  // ... and small enough for the pointer tables of the group kernels and of the batched products
+  bool uniform_small() const { return uniform() && batch <= std::min(kSmallBatch, ndmps_gemm_batched_max()); }
 
-  int i_start = L - 1;
-  if (lay.merge_from < L) {
-    // ---- merged trailing run: sites merge_from .. L-1 from ONE Gram pass and ONE projection pass
-    const int i0 = lay.merge_from;
-    const int64_t n0 = lay.merge_n, ldw = lay.merge_w, m0 = lay.numel / n0;
-    const int64_t stride_top = n0 * n0, stride_w = n0 * ldw;
+  int prepare() {
+    NDMPS_REQUIRE(h_dense && h_dims && h_cores && h_core_offsets && h_bonds_out, "NULL sweep argument");
+    NDMPS_REQUIRE(cutoff >= 0.0, "cutoff must be non-negative");
+    NDMPS_TRY(sweep_layout(L, h_dims, max_bond, batch, lay, sizeof(T) == 8 ? 8 : 4));
+    if (d_ws == nullptr || ws_bytes < lay.workspace) {
+      ndmps::set_error("sweep workspace too small: %lld < %lld", (long long)ws_bytes, (long long)lay.workspace);
+      return NDMPS_EWORKSPACE;
+    }
+    for (int b = 0; b < batch; ++b) NDMPS_REQUIRE(h_dense[b] && h_cores[b], "NULL volume or core arena %d", b);
+    Arena ar(d_ws, ws_bytes);
+    carve_sweep(ar, lay, ws);
+    NDMPS_REQUIRE(ar.fits(), "workspace carve failed");
+    if (src) {
+      // h_dense[b] is the C-order volume and stays untouched: the carried matrices ping-pong between the halves
+      // of the workspace buffer (the first one is already <= half the tensor)
+      NDMPS_REQUIRE(lay.merge_from < L && src->n_cols == lay.merge_n &&
+                        (lay.numel / lay.merge_n) * lay.merge_w <= lay.numel / 2,
+                    "the fused reshape stage needs a merged run of %lld columns (see ndmps_tt_merge_columns)",
+                    (long long)src->n_cols);
+    }
+    sq = lay.small_max * lay.small_max;
+    spec_total = h_spec_offsets ? h_spec_offsets[L] : 0;
+    cur.assign(h_dense, h_dense + batch);
+    nxt.resize(batch);
+    chi_r.assign(batch, 1);
+    cur_elems.assign(batch, lay.numel);
+    eig_n.assign(batch, 0);
+    kept.assign(batch, 0);
+    host_w.assign((size_t)batch * lay.small_max, 0.0);
+    for (int b = 0; b < batch; ++b) {
+      nxt[b] = static_cast<T*>(ws.other) + (int64_t)b * lay.numel;
+      h_bonds_out[(int64_t)b * (L + 1)] = 1;
+      h_bonds_out[(int64_t)b * (L + 1) + L] = 1;
+    }
+    return NDMPS_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------------ eigenproblems
+  // One batched eigen-solve for site i on the matrices G[b] (order eig_n[b], ld eig_n[b]): the rank of every volume
+  // (kept[b]) and the kept eigenvectors in the columns of V[b].  have_a: the unfolding itself is at hand in cur[b].
+  int solve_site(int i, bool have_a) {
+    const int64_t site_n = *std::max_element(eig_n.begin(), eig_n.end());
+    const int64_t k_cap = std::min<int64_t>(max_bond, site_n);
+    if (lay.device_rank) return solve_on_device(i, k_cap);
+    const bool topk = use_topk(site_n, max_bond);
+    // every eigenpair above the cutoff, direct solver
+    bool full = !topk && use_direct_full(lay.small_max, batch, max_bond);
+    const int64_t k_solver = topk ? k_cap : lay.small_max;
+    if (topk || full) {
+      NDMPS_TRY(ndmps_syevd_topk_values_f64(batch, ws.G, sq, eig_n.data(), ws.V, sq, ws.w, lay.small_max, k_solver,
+                                            ws.ev_ws, lay.eig_bytes, s));
+      // the host waits for the eigenvalues anyway: a resident launch that gave up is redone on the column launches
+      NDMPS_TRY(ndmps_syevd_topk_recover_f64(batch, eig_n.data(), k_solver, ws.ev_ws, lay.eig_bytes, nullptr, s));
+      NDMPS_TRY(fetch_eigenvalues());
+    }
+    if (full) {
+      // eigenvalues in doubt (direct_doubt_from): with the unfolding at hand their singular values are measured
+      // as |A v| behind the solve (measure_doubt); without it (merged run) the Jacobi decides (G is untouched)
+      doubt.assign(batch, 0);
+      for (int b = 0; b < batch; ++b) {
+        doubt[b] = direct_doubt_from(host_w.data() + (int64_t)b * lay.small_max, eig_n[b], rel_cutoff());
+        if (doubt[b] < eig_n[b] && !have_a) full = false;
+      }
+    }
+    if (!topk && !full) return solve_jacobi(i, true);
+    return solve_direct(i, topk, k_solver);
+  }
+
+  // no host round trip: eigenvalues -> rank (device) -> k_b eigenvectors, the other columns up to the cap zero
+  int solve_on_device(int i, int64_t k_cap) {
+    NDMPS_TRY(ndmps_syevd_topk_values_f64(batch, ws.G, sq, eig_n.data(), ws.V, sq, ws.w, lay.small_max, k_cap, ws.ev_ws,
+                                          lay.eig_bytes, s));
+    NDMPS_TRY(ndmps_syevd_topk_vectors_auto_f64(batch, eig_n.data(), k_cap, rel_cutoff(), ws.d_ranks + (int64_t)i * batch,
+                                                ws.d_spec + (int64_t)i * batch * lay.spec_stride, lay.spec_stride,
+                                                ws.d_status + (int64_t)i * batch, ws.ev_ws, lay.eig_bytes, s));
+    for (int b = 0; b < batch; ++b) kept[b] = k_cap;
+    return NDMPS_OK;
+  }
+
+  int fetch_eigenvalues() {
+    NDMPS_CHECK_HIP(hipMemcpyAsync(host_w.data(), ws.w, sizeof(double) * batch * lay.small_max, hipMemcpyDeviceToHost, s));
+    NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+    return NDMPS_OK;
+  }
+
+  // kept[b] from the eigenvalues on the host: singular values = sqrt, the rank rule of kept_rank; record: the singular
+  // values also go to the caller's spectra
+  void ranks_from_eigenvalues(int i, bool record) {
+    for (int b = 0; b < batch; ++b) {
+      const int64_t small = eig_n[b];
+      std::vector<double> sv(host_w.begin() + (int64_t)b * lay.small_max, host_w.begin() + (int64_t)b * lay.small_max + small);
+      for (auto& x : sv) x = sqrt(std::max(x, 0.0));
+      kept[b] = kept_rank(sv, cutoff, max_bond, cutoff_floor<T>());
+      if (record && h_spectra && h_spec_offsets) {
+        // the layout reserves min(m, d_i max_bond_{i+1}) values for the bond; a merged site may be larger
+        const int64_t room = h_spec_offsets[i + 1] - h_spec_offsets[i];
+        memcpy(h_spectra + (int64_t)b * spec_total + h_spec_offsets[i], sv.data(), std::min(small, room) * sizeof(double));
+      }
+    }
+  }
+
+  // the block Jacobi: eigenvalues, rank decision on the host, kept vectors
+  int solve_jacobi(int i, bool record) {
+    int sweeps = 0;
+    NDMPS_TRY(ndmps_syevj_batched_values_f64(batch, ws.G, sq, eig_n.data(), ws.V, sq, ws.w, lay.small_max,
+                                             sweep_eig_tol(sizeof(T) == 8), ws.ev_ws, lay.eig_bytes, &sweeps, s));
+    NDMPS_TRY(fetch_eigenvalues());
+    ranks_from_eigenvalues(i, record);
+    return ndmps_syevj_batched_vectors_f64(batch, ws.G, sq, eig_n.data(), ws.V, sq, ws.w, lay.small_max, kept.data(), ws.ev_ws,
+                                           lay.eig_bytes, s);
+  }
+
+  // the direct solver behind its eigenvalues (already in host_w): ranks, then the kept vectors.  topk: at most k_solver of
+  // them; else every eigenpair above the cutoff, with the eigenvalues in doubt measured afterwards.
+  int solve_direct(int i, bool topk, int64_t k_solver) {
+    ranks_from_eigenvalues(i, true);
+    for (int b = 0; b < batch; ++b)
+      if (!topk && doubt[b] < eig_n[b]) kept[b] = eig_n[b];  // every vector first; the rank follows from |A v| (measure_doubt)
+    std::vector<int> status(batch, 0);
+    NDMPS_TRY(ndmps_syevd_topk_vectors_f64(batch, eig_n.data(), kept.data(), k_solver, ws.ev_ws, lay.eig_bytes, status.data(), s));
+    bool redo = false;
+    for (int b = 0; b < batch; ++b)
+      if (status[b] != 0) {
+        if (topk) return solver_failed(i, b, status[b]);
+        redo = true;  // the wide block lost rank (a cluster tighter than the shifts resolve): the Jacobi has no such case
+      }
+    if (redo) return solve_jacobi(i, false);
+    return topk ? NDMPS_OK : measure_doubt(i);
+  }
+
+  // Singular values in doubt, measured: s_j = |A v_j| (or |A^T u_j|) for the eigenvectors from doubt[b] on; G (free
+  // now) is the scratch.  The kept rank = the vectors in front + those whose s_j passes the cutoff.
+  int measure_doubt(int i) {
+    for (int b = 0; b < batch; ++b) {
+      const int64_t small = eig_n[b], i0 = doubt[b], t = small - i0;
+      if (t <= 0) continue;
+      const int64_t n = h_dims[i] * chi_r[b], m = cur_elems[b] / n;
+      const bool right = n <= m;  // G = A^T A: vectors in R^n, |A v|; else G = A A^T: |A^T u|
+      double* out = nullptr;
+      NDMPS_TRY(tail_norms((const T*)cur[b], right ? n : (int64_t)1, right ? (int64_t)1 : n, right ? m : n, right ? n : m,
+                           Vb(b), small, i0, t, Gb(b), sq, &out, s));
+      std::vector<double> s2((size_t)t);
+      NDMPS_CHECK_HIP(hipMemcpyAsync(s2.data(), out, sizeof(double) * t, hipMemcpyDeviceToHost, s));
+      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+      const double s0 = sqrt(std::max(host_w[(int64_t)b * lay.small_max], 0.0));
+      int64_t k = i0;
+      for (int64_t j = 0; j < t; ++j) k += sqrt(std::max(s2[(size_t)j], 0.0)) > rel_cutoff() * s0;
+      k = std::max<int64_t>(k, 1);
+      if (max_bond > 0) k = std::min(k, max_bond);
+      kept[b] = std::min(k, small);
+      if (h_spectra && h_spec_offsets) {
+        const int64_t room = h_spec_offsets[i + 1] - h_spec_offsets[i];
+        for (int64_t j = 0; j < t && i0 + j < room; ++j)
+          h_spectra[(int64_t)b * spec_total + h_spec_offsets[i] + i0 + j] = sqrt(std::max(s2[(size_t)j], 0.0));
+      }
+    }
+    return NDMPS_OK;
+  }
+
+  // --------------------------------------------------------------------------------------- merged trailing run
+  // sites merge_from .. L-1 from ONE Gram pass and ONE projection pass (see the comment above MergeRanks)
+  int merged_run() {
+    NDMPS_TRY(merged_raw_gram());
+    hipLaunchKernelGGL(merge_basis_init_kernel, dim3(batch), dim3(1), 0, s, ws.Wm[0], lay.merge_n * lay.merge_w);
+    NDMPS_LAUNCH_CHECK();
+    int wcur = 0;         // which of Wm holds W_{i+1}
+    int64_t n_right = 1;  // N_{i+1}
+    for (int i = L - 1; i >= lay.merge_from; --i) {
+      NDMPS_TRY(merged_site_gram(i, n_right, ws.Wm[wcur]));
+      NDMPS_TRY(solve_site(i, false));
+      NDMPS_TRY(merged_basis_and_core(i, n_right, ws.Wm[wcur], ws.Wm[wcur ^ 1]));
+      wcur ^= 1;
+      n_right *= h_dims[i];
+    }
+    return merged_project();
+  }
+
+  int merged_raw_gram() {
+    const int64_t n0 = lay.merge_n, m0 = lay.numel / n0, stride_top = n0 * n0;
     const int64_t raw_batched = gram_batched_need<T>(batch, m0, n0);
     if (batch > 1 && raw_batched > 0 && raw_batched <= lay.gram_ws) {
-      // the whole group in one launch (long slabs: a fraction of the partial tiles, no launch gaps)
-      if (src) {  // columns visited in memory order; the slab reduction stores the result in site order
-        NDMPS_TRY(gram_batched_src(batch, cur.data(), m0, n0, *src, Graw, stride_top, gram_ws, lay.gram_ws, s));
-      } else {
-        NDMPS_TRY(gram_batched_T(batch, cur.data(), m0, n0, Graw, stride_top, gram_ws, lay.gram_ws, s));
+      // the whole group in one launch (long slabs: a fraction of the partial tiles, no launch gaps); with src the columns
+      // are visited in memory order and the slab reduction stores the result in site order
+      return src ? gram_batched_src(batch, cur.data(), m0, n0, *src, ws.Graw, stride_top, ws.gram_ws, lay.gram_ws, s)
+                 : gram_batched_T(batch, cur.data(), m0, n0, ws.Graw, stride_top, ws.gram_ws, lay.gram_ws, s);
+    }
+    for (int b = 0; b < batch; ++b) {
+      double* Gr = ws.Graw + (int64_t)b * stride_top;
+      NDMPS_TRY(src ? gram_src(cur[b], m0, n0, *src, Gr, ws.gram_ws, lay.gram_ws, s)
+                    : gram_T(cur[b], m0, n0, n0, Gr, ws.gram_ws, lay.gram_ws, s));
+    }
+    return NDMPS_OK;
+  }
+
+  // ranks of the volumes base .. base + count - 1 for one merge launch; here == nullptr: k_here = 0
+  MergeRanks merge_ranks(int base, int count, const int64_t* here) const {
+    MergeRanks rk;
+    for (int t = 0; t < count; ++t) {
+      rk.k_right[t] = (int)chi_r[base + t];
+      rk.k_here[t] = here ? (int)here[base + t] : 0;
+    }
+    return rk;
+  }
+
+  // G_i = B^T Graw_i B into G, B = I (x) W (the accumulated basis W_{i+1}); eig_n[b] = its order
+  int merged_site_gram(int i, int64_t n_right, double* W) {
+    const int64_t n0 = lay.merge_n, ldw = lay.merge_w, stride_top = n0 * n0, stride_w = n0 * ldw;
+    const int64_t d_i = h_dims[i], n_i = n_right * d_i;
+    for (int b = 0; b < batch; ++b) eig_n[b] = d_i * chi_r[b];
+    // the top site of the run (its raw Gram IS the one computed: no block sums) of a uniform group: both
+    // congruence stages as batched fp64 products on the MFMA (0.3 + 0.3 ms of scalar loops per group otherwise,
+    // right behind the Gram pass on the critical path)
+    if (n_i == n0 && uniform() && batch <= ndmps_gemm_batched_max() && n_i * chi_r[0] >= 4096) {
+      const int64_t kr = chi_r[0], n = d_i * kr;
+      const auto pa = strided(ws.Graw, stride_top), pb = strided(W, stride_w), pc = strided(ws.Tm, stride_top);
+      std::vector<double*> qa, qb, qc;
+      for (int b = 0; b < batch; ++b)
+        for (int64_t a = 0; a < d_i; ++a) {
+          qa.push_back(pb[b]);
+          qb.push_back(pc[b] + a * n_right * n);
+          qc.push_back(Gb(b) + a * kr * n);
+        }
+      // T[(r, blk)][q] = sum_c Graw[(r, blk)][c] W[c][q]: rows (r, blk) of n_right contiguous elements
+      NDMPS_TRY(ndmps_dgemm_batched(batch, 0, 0, n_i * d_i, kr, n_right, pa.data(), n_right, pb.data(), ldw, pc.data(), kr, s));
+      // G[(a, p)][j] = sum_c W[c][p] T[(a n_right + c)][j]: one product per (volume, a)
+      const size_t per = (size_t)ndmps_gemm_batched_max();
+      for (size_t base = 0; base < qa.size(); base += per) {
+        const int count = (int)std::min(per, qa.size() - base);
+        NDMPS_TRY(ndmps_dgemm_batched(count, 1, 0, kr, n, n_right, qa.data() + base, ldw, qb.data() + base, n,
+                                      qc.data() + base, n, s));
+      }
+      return NDMPS_OK;
+    }
+    for (int base = 0; base < batch; base += 64) {
+      const int count = std::min(64, batch - base);
+      const int64_t biggest = std::max<int64_t>(1, *std::max_element(eig_n.begin() + base, eig_n.begin() + base + count));
+      const MergeRanks rk = merge_ranks(base, count, nullptr);
+      const int g1 = (int)std::min<int64_t>(ceil_div(n_i * biggest, 256), 1024);
+      const int g2 = (int)std::min<int64_t>(ceil_div(biggest * biggest, 256), 1024);
+      hipLaunchKernelGGL(merge_stage1_kernel, dim3(g1, count), dim3(256), 0, s, ws.Graw + base * stride_top, stride_top,
+                         (int)n0, W + base * stride_w, stride_w, (int)ldw, ws.Tm + base * stride_top, stride_top,
+                         (int)n_i, (int)n_right, (int)d_i, rk);
+      hipLaunchKernelGGL(merge_stage2_kernel, dim3(g2, count), dim3(256), 0, s, ws.Tm + base * stride_top, stride_top,
+                         W + base * stride_w, stride_w, (int)ldw, ws.G + base * sq, sq, (int)n_right, (int)d_i, rk);
+    }
+    NDMPS_LAUNCH_CHECK();
+    return NDMPS_OK;
+  }
+
+  // W_i = B V_i into Wnext (at the first site of the run also in the storage type, for the projection), the core of
+  // site i from the kept vectors, and the bond
+  int merged_basis_and_core(int i, int64_t n_right, double* W, double* Wnext) {
+    const int64_t stride_w = lay.merge_n * lay.merge_w, d_i = h_dims[i], n_i = n_right * d_i;
+    T* W32 = static_cast<T*>(ws.W32);
+    for (int base = 0; base < batch; base += 64) {
+      const int count = std::min(64, batch - base);
+      const int64_t biggest = std::max<int64_t>(1, *std::max_element(kept.begin() + base, kept.begin() + base + count));
+      const MergeRanks rk = merge_ranks(base, count, kept.data());
+      const int g3 = (int)std::min<int64_t>(ceil_div(n_i * biggest, 256), 1024);
+      hipLaunchKernelGGL(merge_basis_kernel<T>, dim3(g3, count), dim3(256), 0, s, W + base * stride_w, stride_w,
+                         (int)lay.merge_w, ws.V + base * sq, sq, Wnext + base * stride_w,
+                         i == lay.merge_from ? W32 + base * stride_w : (T*)nullptr, stride_w, (int)n_right, (int)d_i, rk);
+    }
+    NDMPS_LAUNCH_CHECK();
+    if (batch > 1 && uniform_kept()) {
+      for (int base = 0; base < batch; base += kSmallBatch) {
+        const int count = std::min(kSmallBatch, batch - base);
+        BatchOps ops;
+        for (int t = 0; t < count; ++t) ops.out[t] = core(base + t, i);
+        hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(kept[0] * eig_n[0]), count), dim3(256), 0, s,
+                           Vb(base), sq, eig_n[0], kept[0], ops);
       }
     } else {
-      for (int b = 0; b < batch; ++b) {
-        if (src) {
-          NDMPS_TRY(gram_src(cur[b], m0, n0, *src, Graw + (int64_t)b * stride_top, gram_ws, lay.gram_ws, s));
-        } else {
-          NDMPS_TRY(gram_T(cur[b], m0, n0, n0, Graw + (int64_t)b * stride_top, gram_ws, lay.gram_ws, s));
-        }
-      }
+      for (int b = 0; b < batch; ++b)
+        hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(kept[b] * eig_n[b])), dim3(256), 0, s,
+                           Vb(b), eig_n[b], kept[b], core(b, i));
     }
-    hipLaunchKernelGGL(merge_basis_init_kernel, dim3(batch), dim3(1), 0, s, Wm[0], stride_w);
     NDMPS_LAUNCH_CHECK();
-    int wcur = 0;
-    int64_t n_right = 1;  // N_{i+1}
-    for (int i = L - 1; i >= i0; --i) {
-      const int64_t d_i = h_dims[i], n_i = n_right * d_i;
-      // the top site of the run (its raw Gram IS the one computed: no block sums) of a uniform group: both
-      // congruence stages as batched fp64 products on the MFMA (0.3 + 0.3 ms of scalar loops per group otherwise,
-      // right behind the Gram pass on the critical path)
-      bool on_mfma = false;
-      if (n_i == n0 && uniform() && batch <= ndmps_gemm_batched_max() && n_i * chi_r[0] >= 4096) {
-        const int64_t kr = chi_r[0], n = d_i * kr;
-        std::vector<const double*> pa(batch), pb(batch);
-        std::vector<double*> pc(batch);
-        for (int b = 0; b < batch; ++b) {
-          pa[b] = Graw + (int64_t)b * stride_top;
-          pb[b] = Wm[wcur] + (int64_t)b * stride_w;
-          pc[b] = Tm + (int64_t)b * stride_top;
-          eig_n[b] = n;
-        }
-        // T[(r, blk)][q] = sum_c Graw[(r, blk)][c] W[c][q]: rows (r, blk) of n_right contiguous elements
-        NDMPS_TRY(ndmps_dgemm_batched(batch, 0, 0, n_i * d_i, kr, n_right, pa.data(), n_right, pb.data(), ldw, pc.data(), kr, s));
-        // G[(a, p)][j] = sum_c W[c][p] T[(a n_right + c)][j]: one product per (volume, a)
-        const int per = ndmps_gemm_batched_max();
-        std::vector<const double*> qa, qb;
-        std::vector<double*> qc;
-        for (int b = 0; b < batch; ++b)
-          for (int64_t a = 0; a < d_i; ++a) {
-            qa.push_back(Wm[wcur] + (int64_t)b * stride_w);
-            qb.push_back(Tm + (int64_t)b * stride_top + a * n_right * n);
-            qc.push_back(G + (int64_t)b * sq + a * kr * n);
-          }
-        for (size_t base = 0; base < qa.size(); base += per) {
-          const int count = (int)std::min<size_t>(per, qa.size() - base);
-          NDMPS_TRY(ndmps_dgemm_batched(count, 1, 0, kr, n, n_right, qa.data() + base, ldw, qb.data() + base, n,
-                                        qc.data() + base, n, s));
-        }
-        on_mfma = true;
-      }
-      for (int base = 0; base < batch && !on_mfma; base += 64) {
-        const int count = std::min(64, batch - base);
-        MergeRanks rk;
-        int64_t biggest = 1;
-        for (int t = 0; t < count; ++t) {
-          rk.k_right[t] = (int)chi_r[base + t];
-          rk.k_here[t] = 0;
-          eig_n[base + t] = d_i * chi_r[base + t];
-          biggest = std::max(biggest, eig_n[base + t]);
-        }
-        const int g1 = (int)std::min<int64_t>(ceil_div(n_i * biggest, 256), 1024);
-        const int g2 = (int)std::min<int64_t>(ceil_div(biggest * biggest, 256), 1024);
-        hipLaunchKernelGGL(merge_stage1_kernel, dim3(g1, count), dim3(256), 0, s, Graw + base * stride_top, stride_top,
-                           (int)n0, Wm[wcur] + base * stride_w, stride_w, (int)ldw, Tm + base * stride_top, stride_top,
-                           (int)n_i, (int)n_right, (int)d_i, rk);
-        hipLaunchKernelGGL(merge_stage2_kernel, dim3(g2, count), dim3(256), 0, s, Tm + base * stride_top, stride_top,
-                           Wm[wcur] + base * stride_w, stride_w, (int)ldw, G + base * sq, sq, (int)n_right, (int)d_i, rk);
-      }
-      NDMPS_LAUNCH_CHECK();
-      NDMPS_TRY(solve_site(i));
-      for (int base = 0; base < batch; base += 64) {
-        const int count = std::min(64, batch - base);
-        MergeRanks rk;
-        int64_t biggest = 1;
-        for (int t = 0; t < count; ++t) {
-          rk.k_right[t] = (int)chi_r[base + t];
-          rk.k_here[t] = (int)kept[base + t];
-          biggest = std::max(biggest, kept[base + t]);
-        }
-        const int g3 = (int)std::min<int64_t>(ceil_div(n_i * biggest, 256), 1024);
-        hipLaunchKernelGGL(merge_basis_kernel<T>, dim3(g3, count), dim3(256), 0, s, Wm[wcur] + base * stride_w, stride_w,
-                           (int)ldw, V + base * sq, sq, Wm[wcur ^ 1] + base * stride_w,
-                           i == i0 ? W32 + base * stride_w : (T*)nullptr, stride_w, (int)n_right, (int)d_i, rk);
-      }
-      NDMPS_LAUNCH_CHECK();
-      if (batch > 1 && uniform_kept()) {
-        for (int base = 0; base < batch; base += kSmallBatch) {
-          const int count = std::min(kSmallBatch, batch - base);
-          BatchOps ops;
-          for (int t = 0; t < count; ++t) ops.out[t] = h_cores[base + t] + h_core_offsets[i];
-          hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(kept[0] * eig_n[0]), count), dim3(256), 0, s,
-                             V + (int64_t)base * sq, sq, eig_n[0], kept[0], ops);
-        }
-      } else {
-        for (int b = 0; b < batch; ++b)
-          hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(kept[b] * eig_n[b])), dim3(256), 0, s,
-                             V + (int64_t)b * sq, eig_n[b], kept[b], h_cores[b] + h_core_offsets[i]);
-      }
-      for (int b = 0; b < batch; ++b) {
-        chi_r[b] = kept[b];
-        h_bonds_out[(int64_t)b * (L + 1) + i] = kept[b];
-      }
-      NDMPS_LAUNCH_CHECK();
-      wcur ^= 1;
-      n_right = n_i;
+    for (int b = 0; b < batch; ++b) {
+      chi_r[b] = kept[b];
+      h_bonds_out[(int64_t)b * (L + 1) + i] = kept[b];
     }
-    bool projected = false;
+    return NDMPS_OK;
+  }
+
+  // carry = A_raw W (m0 x k): the one projection of the run
+  int merged_project() {
+    const int64_t n0 = lay.merge_n, m0 = lay.numel / n0, stride_top = n0 * n0, stride_w = n0 * lay.merge_w;
+    T* W32 = static_cast<T*>(ws.W32);
     if (src && uniform() && batch <= ndmps_gemm_batched_max()) {
-      // carry = A_raw W for the whole group: the basis rows into memory order (one launch), then one batched product
-      // that reads the volumes through the permutation tables
+      // the whole group: the basis rows into memory order (one launch, into the fp64 slots of T, free now), then one
+      // batched product that reads the volumes through the permutation tables
       const int64_t k = chi_r[0];
-      float* wperm0 = reinterpret_cast<float*>(Tm);
-      const int64_t wperm_stride = stride_top * 2;  // fp64 slots of T, in floats
+      float* wperm0 = reinterpret_cast<float*>(ws.Tm);
+      const int64_t wperm_stride = stride_top * 2;  // in floats
       hipLaunchKernelGGL(gather_rows_kernel, dim3(grid1d(n0 * k), batch), dim3(256), 0, s, (const float*)W32, n0, k,
                          src->col_perm, wperm0, stride_w, wperm_stride);
       NDMPS_LAUNCH_CHECK();
@@ -1053,194 +1133,184 @@ int sweep_impl(int batch, T* const* h_dense, int L, const int64_t* h_dims, doubl
         NDMPS_TRY(ndmps_sgemm_gathered64_stream_batched(batch, m0, k, pa.data(), src->row_sorted, src->row_order, src->col_off,
                                                         pb.data(), k, pc.data(), k, s));
       else
-      NDMPS_TRY(ndmps_sgemm_indexed_batched(batch, m0, k, n0, pa.data(), 0, src->row_off, src->col_off, 1, pb.data(), k,
-                                            pc.data(), k, nullptr, nullptr, s));
+        NDMPS_TRY(ndmps_sgemm_indexed_batched(batch, m0, k, n0, pa.data(), 0, src->row_off, src->col_off, 1, pb.data(), k,
+                                              pc.data(), k, nullptr, nullptr, s));
+    } else {
       for (int b = 0; b < batch; ++b) {
-        cur[b] = nxt[b];
-        nxt[b] = nxt[b] + lay.numel / 2;
-        cur_elems[b] = m0 * k;
+        // with src, T (fp64 scratch of the congruences, free now) holds the basis with its rows in memory order
+        T* wperm = reinterpret_cast<T*>(ws.Tm + (int64_t)b * stride_top);
+        const T* Wb = W32 + (int64_t)b * stride_w;
+        NDMPS_TRY(src ? project_src(cur[b], m0, chi_r[b], n0, *src, Wb, wperm, nxt[b], s)
+                      : gemm_T(0, m0, chi_r[b], n0, cur[b], Wb, chi_r[b], nxt[b], ws.tws, lay.transpose_bytes, s));
       }
-      projected = true;
     }
-    for (int b = 0; b < batch && !projected; ++b) {  // carry = A_raw W (m0 x k)
-      const int64_t k = chi_r[b];
-      if (src) {
-        // T (fp64 scratch of the congruences, free now) holds the basis with its rows in memory order
-        T* wperm = reinterpret_cast<T*>(Tm + (int64_t)b * stride_top);
-        NDMPS_TRY(project_src(cur[b], m0, k, n0, *src, W32 + (int64_t)b * stride_w, wperm, nxt[b], s));
-        cur[b] = nxt[b];
-        nxt[b] = nxt[b] + lay.numel / 2;
-      } else {
-        NDMPS_TRY(gemm_T(0, m0, k, n0, cur[b], W32 + (int64_t)b * stride_w, k, nxt[b], tws, tws_bytes, s));
-        std::swap(cur[b], nxt[b]);
-      }
-      cur_elems[b] = m0 * k;
+    for (int b = 0; b < batch; ++b) {
+      std::swap(cur[b], nxt[b]);
+      if (src) nxt[b] = cur[b] + lay.numel / 2;  // the volume stays untouched: the other half of the workspace buffer
+      cur_elems[b] = m0 * chi_r[b];
     }
-    i_start = i0 - 1;
+    return NDMPS_OK;
   }
 
-  for (int i = i_start; i >= 1; --i) {
-    // ---- small-side Gram matrices
-    int64_t m = 0;
-    // same shape in every volume (always so when the ranks are decided on the device): one Gram launch
-    bool together = batch > 1;
-    for (int b = 1; b < batch && together; ++b) together = chi_r[b] == chi_r[0] && cur_elems[b] == cur_elems[0];
-    if (together) {
-      const int64_t n = h_dims[i] * chi_r[0];
-      m = cur_elems[0] / n;
+  // ------------------------------------------------------------------------------------------- one site at a time
+  // small-side Gram matrix of every volume's unfolding (m x n, n = d_i chi_r) into G; eig_n[b] = min(m, n)
+  int site_gram(int i) {
+    if (uniform()) {
+      const int64_t n = h_dims[i] * chi_r[0], m = cur_elems[0] / n;
+      // tall: one launch for the group
       const int64_t need = n <= m ? gram_batched_need<T>(batch, m, n) : 0;
-      together = need > 0 && need <= lay.gram_ws && n * n <= sq;
-      if (together) {
-        for (int b = 0; b < batch; ++b) eig_n[b] = n;
-        NDMPS_TRY(gram_batched_T(batch, cur.data(), m, n, G, sq, gram_ws, lay.gram_ws, s));
+      if (need > 0 && need <= lay.gram_ws && n * n <= sq) {
+        eig_n.assign(batch, n);
+        return gram_batched_T(batch, cur.data(), m, n, ws.G, sq, ws.gram_ws, lay.gram_ws, s);
       }
-    }
-    // wide unfoldings (n > m, the last sites) of a uniform group: A A^T of every volume from two launches
-    const bool uni = uniform() && batch <= std::min(kSmallBatch, ndmps_gemm_batched_max());
-    bool wide_together = false;
-    if (!together && uni) {
-      const int64_t n = h_dims[i] * chi_r[0];
-      m = cur_elems[0] / n;
-      if (n > m) {
+      // wide (n > m, the last sites): A A^T of every volume from two launches
+      if (n > m && uniform_small()) {
         BatchOps ops;
-        std::vector<const double*> pa(batch);
-        std::vector<double*> pc(batch);
-        for (int b = 0; b < batch; ++b) {
-          ops.in[b] = cur[b];
-          pa[b] = A64 + (int64_t)b * lay.wide_elems;
-          pc[b] = G + (int64_t)b * sq;
-          eig_n[b] = m;
-        }
-        hipLaunchKernelGGL(f32_to_f64_batched_kernel<T>, dim3(grid1d(m * n), batch), dim3(256), 0, s, ops, m * n, A64,
+        for (int b = 0; b < batch; ++b) ops.in[b] = cur[b];
+        const auto pa = strided(ws.A64, lay.wide_elems), pc = strided(ws.G, sq);
+        eig_n.assign(batch, m);
+        hipLaunchKernelGGL(f32_to_f64_batched_kernel<T>, dim3(grid1d(m * n), batch), dim3(256), 0, s, ops, m * n, ws.A64,
                            lay.wide_elems);
         NDMPS_LAUNCH_CHECK();
-        NDMPS_TRY(ndmps_dgemm_batched(batch, 0, 1, m, m, n, pa.data(), n, pa.data(), n, pc.data(), m, s));
-        wide_together = true;
+        return ndmps_dgemm_batched(batch, 0, 1, m, m, n, pa.data(), n, pa.data(), n, pc.data(), m, s);
       }
     }
-    for (int b = 0; b < batch && !together && !wide_together; ++b) {
-      const int64_t n = h_dims[i] * chi_r[b];
-      m = cur_elems[b] / n;
+    for (int b = 0; b < batch; ++b) {
+      const int64_t n = h_dims[i] * chi_r[b], m = cur_elems[b] / n;
       eig_n[b] = std::min(m, n);
-      double* Gb = G + (int64_t)b * sq;
       if (n <= m) {
         const int64_t need = gram_need(cur[b], m, n);
-        NDMPS_REQUIRE(need <= lay.gram_ws, "internal: Gram workspace bound violated (%lld > %lld)",
-                      (long long)need, (long long)lay.gram_ws);
-        NDMPS_TRY(gram_T(cur[b], m, n, n, Gb, gram_ws, lay.gram_ws, s));
+        NDMPS_REQUIRE(need <= lay.gram_ws, "internal: Gram workspace bound violated (%lld > %lld)", (long long)need,
+                      (long long)lay.gram_ws);
+        NDMPS_TRY(gram_T(cur[b], m, n, n, Gb(b), ws.gram_ws, lay.gram_ws, s));
       } else {
-        double* Ab = A64 + (int64_t)b * lay.wide_elems;
-        hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(m * n)), dim3(256), 0, s, cur[b], m * n, Ab);
+        double* Ab = ws.A64 + (int64_t)b * lay.wide_elems;
+        hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(m * n)), dim3(256), 0, s, (const T*)cur[b], m * n, Ab);
         NDMPS_LAUNCH_CHECK();
-        NDMPS_TRY(ndmps_dgemm(0, 1, m, m, n, Ab, n, Ab, n, Gb, m, s));
+        NDMPS_TRY(ndmps_dgemm(0, 1, m, m, n, Ab, n, Ab, n, Gb(b), m, s));
       }
     }
-    NDMPS_TRY(solve_site(i, true));
-    // ---- core and carried matrix: one launch per step for a uniform group, else volume by volume
-    bool done = false;
-    if (uni && uniform_kept()) {
-      const int64_t n = h_dims[i] * chi_r[0], small = eig_n[0], k = kept[0];
-      BatchOps cores_out, carry_out;
-      std::vector<T*> pcur(batch), pcore(batch), pnxt(batch);
-      for (int b = 0; b < batch; ++b) {
-        pcur[b] = cur[b];
-        pcore[b] = h_cores[b] + h_core_offsets[i];
-        pnxt[b] = nxt[b];
-        cores_out.out[b] = pcore[b];
-        carry_out.out[b] = nxt[b];
-      }
-      if (n <= m) {
-        int rc = NDMPS_OK;
-        hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(k * n), batch), dim3(256), 0, s, V, sq, n, k,
-                           cores_out);
-        NDMPS_LAUNCH_CHECK();
-        done = gemm_batched_T(batch, 1, m, k, n, pcur.data(), pcore.data(), n, pnxt.data(), s, &rc);
-        NDMPS_TRY(rc);
-        if (!done)  // bf16 storage: the products go volume by volume
-          for (int b = 0; b < batch; ++b) NDMPS_TRY(gemm_T(1, m, k, n, cur[b], pcore[b], n, nxt[b], tws, tws_bytes, s));
-        done = true;
-      } else {
-        std::vector<const double*> pv(batch), pa(batch);
-        std::vector<double*> pu(batch);
-        for (int b = 0; b < batch; ++b) {
-          pv[b] = V + (int64_t)b * sq;
-          pa[b] = A64 + (int64_t)b * lay.wide_elems;
-          pu[b] = UtA + (int64_t)b * lay.wide_elems;
-        }
-        hipLaunchKernelGGL(sqrt_clamp_batched_kernel, dim3(grid1d(small), batch), dim3(256), 0, s, w, lay.small_max, small,
-                           sig);
-        hipLaunchKernelGGL(scale_cols_to_f32_batched_kernel<T>, dim3(grid1d(m * k), batch), dim3(256), 0, s, V, sq, m, m, k,
-                           sig, lay.small_max, 1.0, carry_out);  // carry = U_k diag(sigma_k)
-        NDMPS_LAUNCH_CHECK();
-        NDMPS_TRY(ndmps_dgemm_batched(batch, 1, 0, k, n, m, pv.data(), m, pa.data(), n, pu.data(), n, s));
-        hipLaunchKernelGGL(scale_rows_to_f32_batched_kernel<T>, dim3(grid1d(k * n), batch), dim3(256), 0, s, UtA,
-                           lay.wide_elems, k, n, sig, lay.small_max, -1.0, cores_out);  // core = diag(1/sigma_k) U_k^T A
-        NDMPS_LAUNCH_CHECK();
-        done = true;
-      }
-      for (int b = 0; b < batch; ++b) {
-        std::swap(cur[b], nxt[b]);
-        cur_elems[b] = m * k;
-        chi_r[b] = k;
-        h_bonds_out[(int64_t)b * (L + 1) + i] = k;
-      }
-    }
-    for (int b = 0; b < batch && !done; ++b) {
-      const int64_t n = h_dims[i] * chi_r[b];
-      m = cur_elems[b] / n;
-      const int64_t small = eig_n[b];
-      const int64_t k = kept[b];
-      T* core = h_cores[b] + h_core_offsets[i];
-      double* Vb = V + (int64_t)b * sq;
-      double* wb = w + (int64_t)b * lay.small_max;
-      double* sigb = sig + (int64_t)b * lay.small_max;
-      if (n <= m) {
-        hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(k * n)), dim3(256), 0, s, Vb, n, k, core);
-        NDMPS_LAUNCH_CHECK();
-        NDMPS_TRY(gemm_T(1, m, k, n, cur[b], core, n, nxt[b], tws, tws_bytes, s));
-      } else {
-        double* Ab = A64 + (int64_t)b * lay.wide_elems;
-        hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(grid1d(small)), dim3(256), 0, s, wb, small, sigb);
-        hipLaunchKernelGGL(scale_cols_to_f32_kernel<T>, dim3(grid1d(m * k)), dim3(256), 0, s, Vb, m, m, k, sigb, 1.0,
-                           nxt[b]);  // carry = U_k diag(sigma_k)
-        NDMPS_LAUNCH_CHECK();
-        NDMPS_TRY(ndmps_dgemm(1, 0, k, n, m, Vb, m, Ab, n, UtA, n, s));
-        hipLaunchKernelGGL(scale_rows_to_f32_kernel<T>, dim3(grid1d(k * n)), dim3(256), 0, s, UtA, k, n, sigb, -1.0,
-                           core);  // core = diag(1/sigma_k) U_k^T A
-        NDMPS_LAUNCH_CHECK();
-      }
-      std::swap(cur[b], nxt[b]);
-      cur_elems[b] = m * k;
-      chi_r[b] = k;
-      h_bonds_out[(int64_t)b * (L + 1) + i] = k;
-    }
+    return NDMPS_OK;
   }
-  // site 0 carries the norm: (1, d_0, chi_1)
-  for (int b = 0; b < batch; ++b)
-    NDMPS_CHECK_HIP(hipMemcpyAsync(h_cores[b] + h_core_offsets[0], cur[b], cur_elems[b] * sizeof(T),
-                                   hipMemcpyDeviceToDevice, s));
-  if (dev_rank && L > 1) {
-    const size_t n_i = (size_t)2 * L * batch, n_s = (size_t)L * batch * lay.spec_stride;
-    if (async) {  // enqueue only: the caller reads the pinned buffers behind its own synchronisation (sweep_collect)
-      NDMPS_REQUIRE(async->h_ranks && (async->h_spec || n_s == 0), "asynchronous sweep without its host buffers");
-      NDMPS_CHECK_HIP(hipMemcpyAsync(async->h_ranks, d_ranks, n_i * sizeof(int), hipMemcpyDeviceToHost, s));
-      if (n_s) NDMPS_CHECK_HIP(hipMemcpyAsync(async->h_spec, d_spec, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
+
+  // core of site i and the carried matrix of site i - 1: one launch per step for a uniform group, else volume by volume
+  int site_core_and_carry(int i) {
+    if (uniform_small() && uniform_kept()) {
+      NDMPS_TRY(core_and_carry_uniform(i));
+    } else {
+      for (int b = 0; b < batch; ++b) NDMPS_TRY(core_and_carry_volume(i, b));
+    }
+    for (int b = 0; b < batch; ++b) {
+      const int64_t m = cur_elems[b] / (h_dims[i] * chi_r[b]);
+      std::swap(cur[b], nxt[b]);
+      cur_elems[b] = m * kept[b];
+      chi_r[b] = kept[b];
+      h_bonds_out[(int64_t)b * (L + 1) + i] = kept[b];
+    }
+    return NDMPS_OK;
+  }
+
+  int core_and_carry_uniform(int i) {
+    const int64_t n = h_dims[i] * chi_r[0], m = cur_elems[0] / n, small = eig_n[0], k = kept[0];
+    BatchOps cores_out, carry_out;
+    std::vector<T*> pcore(batch);
+    for (int b = 0; b < batch; ++b) {
+      pcore[b] = core(b, i);
+      cores_out.out[b] = pcore[b];
+      carry_out.out[b] = nxt[b];
+    }
+    if (n <= m) {  // core = V_k^T, carry = A V_k
+      hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(k * n), batch), dim3(256), 0, s,
+                         ws.V, sq, n, k, cores_out);
+      NDMPS_LAUNCH_CHECK();
+      int rc = NDMPS_OK;
+      const bool grouped = gemm_batched_T(batch, 1, m, k, n, cur.data(), pcore.data(), n, nxt.data(), s, &rc);
+      NDMPS_TRY(rc);
+      for (int b = 0; b < batch && !grouped; ++b)  // bf16 storage: the products go volume by volume
+        NDMPS_TRY(gemm_T(1, m, k, n, cur[b], pcore[b], n, nxt[b], ws.tws, lay.transpose_bytes, s));
       return NDMPS_OK;
     }
-    std::vector<int> host_i(n_i);
-    std::vector<double> host_s(n_s);
-    NDMPS_CHECK_HIP(hipMemcpyAsync(host_i.data(), d_ranks, n_i * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (n_s) NDMPS_CHECK_HIP(hipMemcpyAsync(host_s.data(), d_spec, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
+    const auto pv = strided(ws.V, sq), pa = strided(ws.A64, lay.wide_elems), pu = strided(ws.UtA, lay.wide_elems);
+    hipLaunchKernelGGL(sqrt_clamp_batched_kernel, dim3(grid1d(small), batch), dim3(256), 0, s, ws.w,
+                       lay.small_max, small, ws.sig);
+    hipLaunchKernelGGL(scale_cols_to_f32_batched_kernel<T>, dim3(grid1d(m * k), batch), dim3(256), 0, s, ws.V,
+                       sq, m, m, k, ws.sig, lay.small_max, 1.0, carry_out);  // carry = U_k diag(sigma_k)
+    NDMPS_LAUNCH_CHECK();
+    NDMPS_TRY(ndmps_dgemm_batched(batch, 1, 0, k, n, m, pv.data(), m, pa.data(), n, pu.data(), n, s));
+    hipLaunchKernelGGL(scale_rows_to_f32_batched_kernel<T>, dim3(grid1d(k * n), batch), dim3(256), 0, s,
+                       ws.UtA, lay.wide_elems, k, n, ws.sig, lay.small_max, -1.0,
+                       cores_out);  // core = diag(1/sigma_k) U_k^T A
+    NDMPS_LAUNCH_CHECK();
+    return NDMPS_OK;
+  }
+
+  int core_and_carry_volume(int i, int b) {
+    const int64_t n = h_dims[i] * chi_r[b], m = cur_elems[b] / n, small = eig_n[b], k = kept[b];
+    const double* sigb = ws.sig + (int64_t)b * lay.small_max;
+    if (n <= m) {  // core = V_k^T, carry = A V_k
+      hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(k * n)), dim3(256), 0, s, Vb(b), n, k,
+                         core(b, i));
+      NDMPS_LAUNCH_CHECK();
+      return gemm_T(1, m, k, n, cur[b], core(b, i), n, nxt[b], ws.tws, lay.transpose_bytes, s);
+    }
+    hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(grid1d(small)), dim3(256), 0, s, ws.w + (int64_t)b * lay.small_max,
+                       small, ws.sig + (int64_t)b * lay.small_max);
+    hipLaunchKernelGGL(scale_cols_to_f32_kernel<T>, dim3(grid1d(m * k)), dim3(256), 0, s, Vb(b), m, m, k, sigb,
+                       1.0, nxt[b]);  // carry = U_k diag(sigma_k)
+    NDMPS_LAUNCH_CHECK();
+    NDMPS_TRY(ndmps_dgemm(1, 0, k, n, m, Vb(b), m, ws.A64 + (int64_t)b * lay.wide_elems, n, ws.UtA, n, s));
+    hipLaunchKernelGGL(scale_rows_to_f32_kernel<T>, dim3(grid1d(k * n)), dim3(256), 0, s, ws.UtA, k, n, sigb,
+                       -1.0, core(b, i));  // core = diag(1/sigma_k) U_k^T A
+    NDMPS_LAUNCH_CHECK();
+    return NDMPS_OK;
+  }
+
+  // site 0 carries the norm: (1, d_0, chi_1).  Then the ranks, status words and spectra a device-rank sweep left on the
+  // device: read here, or (async) only enqueued towards the caller's pinned buffers (sweep_collect reads them later).
+  int finish() {
+    for (int b = 0; b < batch; ++b)
+      NDMPS_CHECK_HIP(hipMemcpyAsync(core(b, 0), cur[b], cur_elems[b] * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (!lay.device_rank || L <= 1) {
+      if (async) {
+        ndmps::set_error("an asynchronous sweep needs ranks decided on the device (ndmps_tt_sweep_pads_cores) and more than one site");
+        return NDMPS_EINVAL;
+      }
+      NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+      return NDMPS_OK;
+    }
+    const size_t n_i = (size_t)2 * L * batch, n_s = (size_t)L * batch * lay.spec_stride;
+    std::vector<int> host_i(async ? 0 : n_i);
+    std::vector<double> host_s(async ? 0 : n_s);
+    if (async) NDMPS_REQUIRE(async->h_ranks && (async->h_spec || n_s == 0), "asynchronous sweep without its host buffers");
+    int* dst_i = async ? async->h_ranks : host_i.data();
+    double* dst_s = async ? async->h_spec : host_s.data();
+    NDMPS_CHECK_HIP(hipMemcpyAsync(dst_i, ws.d_ranks, n_i * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (n_s) NDMPS_CHECK_HIP(hipMemcpyAsync(dst_s, ws.d_spec, n_s * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (async) return NDMPS_OK;  // the caller reads the pinned buffers behind its own synchronisation
     NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-    return sweep_collect(batch, L, lay.spec_stride, host_i.data(), n_s ? host_s.data() : nullptr, h_bonds_out, h_spectra,
-                         h_spec_offsets);
+    return sweep_collect(batch, L, lay.spec_stride, dst_i, n_s ? dst_s : nullptr, h_bonds_out, h_spectra, h_spec_offsets);
   }
-  if (async) {
-    ndmps::set_error("an asynchronous sweep needs ranks decided on the device (ndmps_tt_sweep_pads_cores) and more than one site");
-    return NDMPS_EINVAL;
+};
+
+template <typename T>
+int sweep_impl(int batch, T* const* h_dense, int L, const int64_t* h_dims, double cutoff, int64_t max_bond,
+               T* const* h_cores, const int64_t* h_core_offsets, int64_t* h_bonds_out, double* h_spectra,
+               const int64_t* h_spec_offsets, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream,
+               const SweepSource* src = nullptr, const SweepAsync* async = nullptr) {
+  Sweep<T> sw{batch, h_dense, L, h_dims, cutoff, max_bond, h_cores, h_core_offsets, h_bonds_out, h_spectra,
+              h_spec_offsets, d_ws, ws_bytes, (hipStream_t)stream, src, async};
+  NDMPS_TRY(sw.prepare());
+  int i = L - 1;
+  if (sw.lay.merge_from < L) {
+    NDMPS_TRY(sw.merged_run());
+    i = sw.lay.merge_from - 1;
   }
-  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-  return NDMPS_OK;
+  for (; i >= 1; --i) {
+    NDMPS_TRY(sw.site_gram(i));
+    NDMPS_TRY(sw.solve_site(i, true));
+    NDMPS_TRY(sw.site_core_and_carry(i));
+  }
+  return sw.finish();
 }
 }  // namespace
 
@@ -1371,17 +1441,45 @@ extern "C" int ndmps_tt_sweep_f32(float* d_dense, int L, const int64_t* h_dims, 
 
 // =================================================================== bond truncation
 namespace {
-struct BondLayout {
-  int64_t off[16];
-  int64_t total;
-};
-}  // namespace
-
-namespace {
 // eigen workspace of compress_bond: the block Jacobi's, and the direct solver's for every eigenpair where it applies
 inline int64_t bond_eig_bytes(int64_t chi) {
   const int64_t jac = ndmps_syevj_workspace_bytes(chi);
   return use_direct_full(chi, 1, 0) ? std::max(jac, ndmps_syevd_topk_workspace_bytes(chi, 1, chi)) : jac;
+}
+
+// The workspace of compress_bond for cores (m1, chi) and (chi, n2), piece by piece: the size query carves an arena
+// without memory, compress_bond_impl the caller's.
+struct BondBuffers {
+  double *G1, *G2;       // T1^T T1; T2 T2^T (destroyed)
+  ndmps::GramTrunc g;    // the buffers of the truncation itself: Lt, tmp, H, V, P1, w2, wh, sig and the eigen workspace
+  double* P2;            // tmp V
+  double *A1, *B2;       // the two factors in the storage type (chi^2 doubles each, whatever the type)
+  double* t2d;           // T2 in fp64
+  char* gram_ws;
+  int64_t gram_bytes;
+};
+void carve_bond(Arena& ar, int64_t m1, int64_t chi, int64_t n2, BondBuffers& b) {
+  const int64_t c2 = chi * chi;
+  ndmps::GramTrunc& g = b.g;
+  g.chi = chi;
+  b.G1 = ar.take<double>(c2);
+  b.G2 = ar.take<double>(c2);
+  g.Lt = ar.take<double>(c2);
+  g.tmp = ar.take<double>(c2);
+  g.H = ar.take<double>(c2);
+  g.V = ar.take<double>(c2);
+  g.P1 = ar.take<double>(c2);
+  b.P2 = ar.take<double>(c2);
+  g.w2 = ar.take<double>(chi);
+  g.wh = ar.take<double>(chi);
+  g.sig = ar.take<double>(chi);
+  b.A1 = ar.take<double>(c2);
+  b.B2 = ar.take<double>(c2);
+  b.t2d = ar.take<double>(chi * n2);
+  g.ev_bytes = bond_eig_bytes(chi);
+  g.ev_ws = ar.take<char>(g.ev_bytes);
+  b.gram_bytes = std::max(ndmps_gram_workspace_bytes(m1, chi), ndmps_gram_f64_workspace_bytes(m1, chi));
+  b.gram_ws = ar.take<char>(b.gram_bytes);
 }
 }  // namespace
 
@@ -1476,7 +1574,7 @@ int ndmps::gram_truncate(const GramTrunc& g, double* Gf, const double* Gd, const
   }
   // fp64 cores: H carries s^2, so a zero comes back at ~sqrt(n u) s_0 -- on kCutoffFloorF64 itself -- and the eigenvalues
   // in doubt (direct_doubt_from) cannot decide the rank.  Those below the cap are measured directly, s_j = |data Lt v_j|
-  // (H = (data Lt)^T (data Lt)), whose noise is ~u |data| |Lt|, as sweep_impl measures its tail norms; they replace the
+  // (H = (data Lt)^T (data Lt)), whose noise is ~u |data| |Lt|, as the sweep measures its tail norms (Sweep::measure_doubt); they replace the
   // squared values in the rank and in the caller's scalings.  fp32 and bf16 cores: the floor (1e-6) is far above the noise.
   // (k is 1 whatever the values when at most one may be kept; from chi = 2 on, one row block fits H: 2 t <= chi^2)
   if (f64_tails && limit > 1 && direct_doubt_from(sv.data(), chi, c) < limit) {
@@ -1488,16 +1586,8 @@ int ndmps::gram_truncate(const GramTrunc& g, double* Gf, const double* Gd, const
     const int64_t i0 = direct_doubt_from(sv.data(), chi, c), t = chi - i0;
     if (i0 < limit) {
       NDMPS_TRY(ndmps_dgemm(0, 0, chi, chi, chi, Lt, chi, V, chi, P1, chi, s));  // Lt V
-      // partials (nblk x t) and sums (t) in H, free now: fewer blocks of more rows when ceil(rows / 4) do not fit
-      int nblk = (int)ceil_div(rows, 4);
-      if ((int64_t)nblk * t + t > c2) nblk = (int)((c2 - t) / t);
-      NDMPS_REQUIRE(nblk >= 1 && (int64_t)nblk * t + t <= c2, "internal: no room for the tail norms (%lld x %lld)",
-                    (long long)nblk, (long long)t);
-      double* out = H + (int64_t)nblk * t;
-      hipLaunchKernelGGL(tail_norm_partial_kernel<T>, dim3((unsigned)nblk, (unsigned)ceil_div(t, 64)), dim3(256), 0, s,
-                         data, rs, cs, (int)rows, (int)chi, (const double*)P1, (int)chi, (int)i0, (int)t, H);
-      hipLaunchKernelGGL(tail_norm_reduce_kernel, dim3((unsigned)ceil_div(t, 256)), dim3(256), 0, s, H, nblk, (int)t, out);
-      NDMPS_LAUNCH_CHECK();
+      double* out = nullptr;  // partials and sums in H, free now
+      NDMPS_TRY(tail_norms(data, rs, cs, rows, chi, P1, chi, i0, t, H, c2, &out, s));
       NDMPS_CHECK_HIP(hipMemcpyAsync(wh + i0, out, t * sizeof(double), hipMemcpyDeviceToDevice, s));
       NDMPS_CHECK_HIP(hipMemcpyAsync(sv.data() + i0, out, t * sizeof(double), hipMemcpyDeviceToHost, s));
       NDMPS_CHECK_HIP(hipStreamSynchronize(s));
@@ -1524,25 +1614,10 @@ template int ndmps::gram_truncate<double>(const GramTrunc&, double*, const doubl
 extern "C" int64_t ndmps_compress_bond_workspace_bytes(int64_t chi_l, int64_t d1, int64_t chi, int64_t d2,
                                                        int64_t chi_r) {
   if (chi_l <= 0 || d1 <= 0 || chi <= 0 || d2 <= 0 || chi_r <= 0) return 0;
-  const int64_t m1 = chi_l * d1, n2 = d2 * chi_r, c2 = chi * chi;
-  int64_t used = 0;
-  used = arena_bytes(used, 8, c2);       // G1
-  used = arena_bytes(used, 8, c2);       // G2 -> destroyed
-  used = arena_bytes(used, 8, c2);       // W2 / Ltilde
-  used = arena_bytes(used, 8, c2);       // tmp = G1 Ltilde
-  used = arena_bytes(used, 8, c2);       // H
-  used = arena_bytes(used, 8, c2);       // V
-  used = arena_bytes(used, 8, c2);       // P1 = Ltilde V
-  used = arena_bytes(used, 8, c2);       // P2 = tmp V
-  used = arena_bytes(used, 8, chi);      // w2
-  used = arena_bytes(used, 8, chi);      // wh
-  used = arena_bytes(used, 8, chi);      // sigma
-  used = arena_bytes(used, 8, c2);       // A1 in the storage type
-  used = arena_bytes(used, 8, c2);       // B2 in the storage type
-  used = arena_bytes(used, 8, chi * n2); // t2 in fp64
-  used = arena_bytes(used, 1, bond_eig_bytes(chi));
-  used = arena_bytes(used, 1, std::max(ndmps_gram_workspace_bytes(m1, chi), ndmps_gram_f64_workspace_bytes(m1, chi)));
-  return ndmps::round_up(used, 256) + 256;
+  Arena sizing(nullptr, 0);
+  BondBuffers unused;
+  carve_bond(sizing, chi_l * d1, chi, d2 * chi_r, unused);
+  return ndmps::round_up(sizing.used, 256) + 256;
 }
 
 // Truncated SVD of the two-site product P = T1 T2 through the bond, without forming P or
@@ -1563,38 +1638,21 @@ int compress_bond_impl(const T* d_t1, const T* d_t2, int64_t chi_l, int64_t d1, 
     return NDMPS_EWORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  const int64_t m1 = chi_l * d1, n2 = d2 * chi_r, c2 = chi * chi;
+  const int64_t m1 = chi_l * d1, n2 = d2 * chi_r;
   Arena ar(d_ws, ws_bytes);
-  double* G1 = ar.take<double>(c2);
-  double* G2 = ar.take<double>(c2);
-  double* Lt = ar.take<double>(c2);
-  double* tmp = ar.take<double>(c2);
-  double* H = ar.take<double>(c2);
-  double* V = ar.take<double>(c2);
-  double* P1 = ar.take<double>(c2);
-  double* P2 = ar.take<double>(c2);
-  double* w2 = ar.take<double>(chi);
-  double* wh = ar.take<double>(chi);
-  double* sig = ar.take<double>(chi);
-  T* A1 = reinterpret_cast<T*>(ar.take<double>(c2));
-  T* B2 = reinterpret_cast<T*>(ar.take<double>(c2));
-  double* t2d = ar.take<double>(chi * n2);
-  const int64_t ev_bytes = bond_eig_bytes(chi);
-  char* ev_ws = ar.take<char>(ev_bytes);
-  const int64_t gram_bytes = std::max(ndmps_gram_workspace_bytes(m1, chi), ndmps_gram_f64_workspace_bytes(m1, chi));
-  char* gram_ws = ar.take<char>(gram_bytes);
-  NDMPS_REQUIRE(G1 && G2 && Lt && tmp && H && V && P1 && P2 && w2 && wh && sig && A1 && B2 && t2d && ev_ws &&
-                    gram_ws,
-                "workspace carve failed");
+  BondBuffers w;
+  carve_bond(ar, m1, chi, n2, w);
+  NDMPS_REQUIRE(ar.fits(), "workspace carve failed");
+  T *A1 = reinterpret_cast<T*>(w.A1), *B2 = reinterpret_cast<T*>(w.B2);
+  double *Lt = w.g.Lt, *tmp = w.g.tmp, *V = w.g.V, *P1 = w.g.P1, *P2 = w.P2, *sig = w.g.sig;
 
-  NDMPS_TRY(gram_T(d_t1, m1, chi, chi, G1, gram_ws, gram_bytes, s));
-  hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(chi * n2)), dim3(256), 0, s, d_t2, chi * n2, t2d);
+  NDMPS_TRY(gram_T(d_t1, m1, chi, chi, w.G1, w.gram_ws, w.gram_bytes, s));
+  hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(chi * n2)), dim3(256), 0, s, d_t2, chi * n2, w.t2d);
   NDMPS_LAUNCH_CHECK();
-  NDMPS_TRY(ndmps_dgemm(0, 1, chi, chi, n2, t2d, n2, t2d, n2, G2, chi, s));
+  NDMPS_TRY(ndmps_dgemm(0, 1, chi, chi, n2, w.t2d, n2, w.t2d, n2, w.G2, chi, s));
   // G2 = T2 T2^T is the square-rooted metric, G1 = T1^T T1 the data Gram; tail norms measured on the rows of T1
-  const ndmps::GramTrunc g{chi, Lt, tmp, H, V, P1, w2, wh, sig, ev_ws, ev_bytes};
   int64_t k = 0;
-  NDMPS_TRY(ndmps::gram_truncate<T>(g, G2, G1, d_t1, m1, chi, 1, cutoff, cutoff_floor<T>(), -1.0, max_bond, sizeof(T) == 8,
+  NDMPS_TRY(ndmps::gram_truncate<T>(w.g, w.G2, w.G1, d_t1, m1, chi, 1, cutoff, cutoff_floor<T>(), -1.0, max_bond, sizeof(T) == 8,
                                     false, &k, h_s, s));
   *h_new_chi = k;
   NDMPS_TRY(ndmps_dgemm(0, 0, chi, k, chi, Lt, chi, V, chi, P1, k, s));
@@ -2004,23 +2062,34 @@ extern "C" int ndmps_chain_contract_f64(int L, const int64_t* h_dims, const int6
 }
 
 // =================================================================== overlap
+namespace {
+struct OverlapBuffers {
+  double* E[2];    // transfer matrix, ping and pong
+  double *A, *B;   // one core of either state in fp64
+  double* X;       // E^T A
+};
+void carve_overlap(Arena& ar, int L, const int64_t* dims, const int64_t* bonds_a, const int64_t* bonds_b, OverlapBuffers& o) {
+  int64_t emax = 1, amax = 1, bmax = 1, xmax = 1;
+  for (int i = 0; i < L; ++i) {
+    emax = std::max(emax, bonds_a[i + 1] * bonds_b[i + 1]);
+    amax = std::max(amax, bonds_a[i] * dims[i] * bonds_a[i + 1]);
+    bmax = std::max(bmax, bonds_b[i] * dims[i] * bonds_b[i + 1]);
+    xmax = std::max(xmax, bonds_b[i] * dims[i] * bonds_a[i + 1]);
+  }
+  o.E[0] = ar.take<double>(emax);
+  o.E[1] = ar.take<double>(emax);
+  o.A = ar.take<double>(amax);
+  o.B = ar.take<double>(bmax);
+  o.X = ar.take<double>(xmax);
+}
+}  // namespace
 extern "C" int64_t ndmps_overlap_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds_a,
                                                  const int64_t* h_bonds_b) {
   if (L < 1 || !h_dims || !h_bonds_a || !h_bonds_b) return 0;
-  int64_t emax = 1, amax = 1, bmax = 1, xmax = 1;
-  for (int i = 0; i < L; ++i) {
-    emax = std::max(emax, h_bonds_a[i + 1] * h_bonds_b[i + 1]);
-    amax = std::max(amax, h_bonds_a[i] * h_dims[i] * h_bonds_a[i + 1]);
-    bmax = std::max(bmax, h_bonds_b[i] * h_dims[i] * h_bonds_b[i + 1]);
-    xmax = std::max(xmax, h_bonds_b[i] * h_dims[i] * h_bonds_a[i + 1]);
-  }
-  int64_t used = 0;
-  used = arena_bytes(used, 8, emax);
-  used = arena_bytes(used, 8, emax);
-  used = arena_bytes(used, 8, amax);
-  used = arena_bytes(used, 8, bmax);
-  used = arena_bytes(used, 8, xmax);
-  return ndmps::round_up(used, 256) + 256;
+  Arena sizing(nullptr, 0);
+  OverlapBuffers unused;
+  carve_overlap(sizing, L, h_dims, h_bonds_a, h_bonds_b, unused);
+  return ndmps::round_up(sizing.used, 256) + 256;
 }
 
 namespace {
@@ -2036,19 +2105,11 @@ int overlap_impl(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const T
     return NDMPS_EWORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  int64_t emax = 1, amax = 1, bmax = 1, xmax = 1;
-  for (int i = 0; i < L; ++i) {
-    emax = std::max(emax, h_bonds_a[i + 1] * h_bonds_b[i + 1]);
-    amax = std::max(amax, h_bonds_a[i] * h_dims[i] * h_bonds_a[i + 1]);
-    bmax = std::max(bmax, h_bonds_b[i] * h_dims[i] * h_bonds_b[i + 1]);
-    xmax = std::max(xmax, h_bonds_b[i] * h_dims[i] * h_bonds_a[i + 1]);
-  }
   Arena ar(d_ws, ws_bytes);
-  double* E[2] = {ar.take<double>(emax), ar.take<double>(emax)};
-  double* A = ar.take<double>(amax);
-  double* B = ar.take<double>(bmax);
-  double* X = ar.take<double>(xmax);
-  NDMPS_REQUIRE(E[0] && E[1] && A && B && X, "workspace carve failed");
+  OverlapBuffers o;
+  carve_overlap(ar, L, h_dims, h_bonds_a, h_bonds_b, o);
+  NDMPS_REQUIRE(ar.fits(), "workspace carve failed");
+  double *const *E = o.E, *A = o.A, *B = o.B, *X = o.X;
 
   hipLaunchKernelGGL(set_scalar_f64_kernel, dim3(1), dim3(1), 0, s, E[0], 1.0);  // no copy from pageable host memory
   int cur = 0;
