@@ -69,6 +69,31 @@ __device__ __forceinline__ T from_f64(double x) { return (T)(float)x; }
 template <>
 __device__ __forceinline__ double from_f64<double>(double x) { return x; }
 
+// accumulator of v_mfma_f64_16x16x4_f64
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+// four consecutive elements as fp32 (16-byte load for fp32 input, 8-byte load for bf16 input)
+__device__ __forceinline__ float4 load4_as_f32(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 load4_as_f32(const __bf16* p) {
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+  const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+// read-once streams: non-temporal (the lines are not kept in the caches in front of data that is read again)
+__device__ __forceinline__ float4 load4_stream_f32(const float* p) {
+  typedef float f32x4_t __attribute__((ext_vector_type(4)));
+  const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ float4 load4_stream_f32(const __bf16* p) {
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+  const bf16x4 v = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(p));
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+
+// upper bound of the Gram workspace of a matrix of at most n columns, or of `batch` of them in one launch (gram.hip)
+int64_t gram_ws_bound(int64_t n, int batch = 1);
+
 // launch spans for bench.py's roofline (util.hip); slot ids
 constexpr int kSpanTridiagColumns = 1;
 constexpr int kSpanTridiagTeam = 2;

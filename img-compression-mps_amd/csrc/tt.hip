@@ -47,6 +47,7 @@ inline double sweep_eig_tol(bool f64_storage = false) {
 
 using ndmps::Arena;
 using ndmps::ceil_div;
+using ndmps::gram_ws_bound;
 
 inline int grid1d(int64_t n) {
   return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
@@ -403,24 +404,6 @@ inline bool direct_rank_is_safe(const double* w_desc, int64_t n, double c) {  //
   for (int64_t i = 0; i < n; ++i)
     if (fabs(w_desc[i] - thr) <= delta) return false;
   return true;
-}
-
-// upper bound of ndmps_gram_workspace_bytes(m, n') over every n' <= n (the actual bond may
-// come out smaller than the worst case the layout is sized for): slabs * tiles <=
-// max(1024, tiles(n)), 64 x 64 doubles each.
-int64_t gram_ws_bound(int64_t n, int batch = 1) {
-  const int64_t t1 = ceil_div(n, 64);
-  // (slabs + slabs/16 + 2) * tiles tiles of 64 x 64 doubles, slabs * tiles <= max(512, tiles(n))
-  const int64_t nt1 = t1 * (t1 + 1) / 2;
-  const int64_t narrow = (std::max<int64_t>(512, nt1) * 17 / 16 + 3 * nt1) * 4096 * 8 + 256;
-  // 128-wide path: same bound with 128 x 128 tiles
-  const int64_t t2 = ceil_div(n, 128);
-  const int64_t nt2 = t2 * (t2 + 1) / 2;
-  const int64_t wide = (std::max<int64_t>(512, nt2) * 17 / 16 + 3 * nt2) * 16384 * 8 + 256;
-  // a lockstep group in one launch (ndmps_gram_batched_*): ~12 rounds of 512 partial tiles in total, plus the
-  // rounding of the slab counts per matrix
-  const int64_t batched = batch > 1 ? (12 * 512 + 3 * nt2 * batch + 64) * 16384 * 8 + 256 : 0;
-  return std::max(std::max(narrow, wide), batched);
 }
 
 // ------------------------------------------------------------------ sweep layout (worst case)
