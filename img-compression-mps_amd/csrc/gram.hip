@@ -1268,6 +1268,20 @@ extern "C" int64_t ndmps_gram_batched_workspace_bytes(int batch, int64_t m, int6
   return gram_plan(GramElem::F32, batch, m, n, false, true).workspace_bytes;
 }
 
+// The plan of a call, for tests and tools (slot order: include/ndmps_hip.h).  Host arithmetic only: no GPU call, and
+// no launcher goes through it.
+extern "C" int ndmps_gram_plan_query(int elem, int batch, int64_t m, int64_t n, int gathered, int batched, int64_t* h_out) {
+  NDMPS_REQUIRE(h_out && elem >= 0 && elem <= 2, "bad Gram plan query (elem=%d)", elem);
+  const GramPlan p = gram_plan(elem == 0 ? GramElem::F32 : (elem == 1 ? GramElem::BF16 : GramElem::F64), batch, m, n,
+                               gathered != 0, batched != 0);
+  const int64_t out[NDMPS_GRAM_PLAN_SLOTS] = {
+      (int64_t)p.route,    p.small_blocks,    p.slabs.T,        p.slabs.n_tiles, p.slabs.n_slabs, p.slabs.rows_per_slab,
+      p.g128.tiles_1d,     p.g128.slabs_off,  p.g128.slabs_diag, p.g128.rows_off, p.g128.rows_diag, p.g128.xcd,
+      p.g128.slots,        p.workspace_bytes};
+  std::copy(out, out + NDMPS_GRAM_PLAN_SLOTS, h_out);
+  return NDMPS_OK;
+}
+
 extern "C" int ndmps_gram_f32(const float* d_A, int64_t m, int64_t n, int64_t lda, double* d_G,
                               void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
   return gram_single<float>(d_A, m, n, lda, d_G, d_ws, ws_bytes, stream);

@@ -213,6 +213,17 @@ int ndmps_gram_batched_indexed_f32(int batch, const float* const* h_base, int64_
                                    const int64_t* d_row_off, const int64_t* d_col_off,
                                    const int32_t* d_col_perm, double* d_G, int64_t stride_G, void* d_ws,
                                    int64_t ws_bytes, ndmps_stream_t stream);
+/* The plan a Gram call would run by, for tests and tools: host arithmetic only, no GPU call, no effect on any launch.
+ * elem: 0 fp32, 1 bf16, 2 fp64; gathered: the operand comes through offset tables; batched: the call comes through
+ * an ndmps_gram_batched_* entry.  The NDMPS_GRAM_* switches are read as a launch would read them.  h_out receives
+ * NDMPS_GRAM_PLAN_SLOTS values (fields of routes the plan does not take are 0):
+ *    0 route: 0 none, 1 Small, 2 Tiles16, 3 Tiles64, 4 Tiles128, 5 Tiles64Batched, 6 Stream64
+ *    1 small_blocks                                     (Small: workgroups of the launch)
+ *    2 T   3 n_tiles   4 n_slabs   5 rows_per_slab      (Tiles16, Tiles64, Tiles64Batched, Stream64: tiles of (16 T)^2)
+ *    6 tiles_1d   7 slabs_off   8 slabs_diag   9 rows_off   10 rows_diag   11 xcd   12 slots      (Tiles128)
+ *   13 workspace_bytes                                  (what the size query of the entry returns) */
+#define NDMPS_GRAM_PLAN_SLOTS 14
+int ndmps_gram_plan_query(int elem, int batch, int64_t m, int64_t n, int gathered, int batched, int64_t* h_out);
 
 /* G = A^T A for a bf16 matrix A (products exact, fp64 accumulation); workspace as ndmps_gram_f32 */
 int ndmps_gram_bf16(const void* d_A, int64_t m, int64_t n, int64_t lda, double* d_G, void* d_ws,

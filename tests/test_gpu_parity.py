@@ -1518,15 +1518,19 @@ def test_gemm_bf16_against_fp32_products(m, n, k, transB):
 
 
 def test_gram_bf16_is_exact_in_fp64():
+    """Integers up to 255 are bf16 numbers; their products and every partial sum of 5000 of them are integers below
+    2**53, so the fp64 accumulation is exact in any order: G is the integer matrix, bit for bit."""
     lib = _lib.load()
     for m, n in ((5000, 8), (4096, 40), (3000, 512), (700, 130)):
-        a = torch.randn((m, n), device=DEV).to(torch.bfloat16)
-        g = torch.empty((n, n), dtype=torch.float64, device=DEV)
+        a = torch.randint(-255, 256, (m, n), device=DEV, generator=torch.Generator(device=DEV).manual_seed(m + n))
+        ab = a.to(torch.bfloat16)
+        assert torch.equal(ab.to(torch.int64), a)
+        g = torch.full((n, n), float("nan"), dtype=torch.float64, device=DEV)
         nbytes = lib.ndmps_gram_workspace_bytes(m, n)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
-        _lib.check(lib.ndmps_gram_bf16(a.data_ptr(), m, n, n, g.data_ptr(), ws.data_ptr(), nbytes, sp()))
-        ref = a.double().T @ a.double()
-        assert float((g - ref).abs().max()) <= 1e-13 * float(ref.abs().max())
+        _lib.check(lib.ndmps_gram_bf16(ab.data_ptr(), m, n, n, g.data_ptr(), ws.data_ptr(), nbytes, sp()))
+        a64 = a.cpu().numpy().astype(np.float64)
+        assert np.array_equal(g.cpu().numpy(), a64.T @ a64)   # exact in NumPy's order of summation as well
 
 
 def test_bf16_and_fp32_sweep_on_a_4d_sample_with_three_capped_bonds_match_the_oracle():

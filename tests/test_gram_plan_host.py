@@ -3,6 +3,8 @@ was answered from, and callers allocate by the query: a changed number here is a
 was recorded from the build before the queries were moved onto the plan; it hits every route and every boundary
 between two routes (n = 8/9, 16/17, 32/33, 63/64/65, 127/128; m = 255/256; one matrix / two; the 48/49 matrices of a
 launch of the 128-wide kernel; more than 64 matrices of the 64-wide ones)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -59,6 +61,20 @@ def test_gram_size_queries_are_pinned(lib):
     assert len(PINNED) >= 60
     got = [(which, batch, m, n, _query(lib, which, batch, m, n)) for which, batch, m, n, _ in PINNED]
     assert got == PINNED
+
+
+def test_plan_query_reports_the_size_the_size_queries_return(lib):
+    """ndmps_gram_plan_query answers from the same GramPlan: slot 13 is the size query's number on every pinned row
+    (fp32 and bf16 share a plan), and the route slot is 0 exactly where there is nothing to run."""
+    for which, batch, m, n, nbytes in PINNED:
+        for elem in ((2,) if which == "f64" else (0, 1)):
+            out = (C.c_int64 * 14)()
+            assert lib.ndmps_gram_plan_query(elem, batch, m, n, 0, int(which == "batched"), out) == 0
+            assert out[13] == nbytes, (which, elem, batch, m, n)
+            assert (out[0] == 0) == (nbytes == 0)
+            assert 0 <= out[0] <= 6
+    assert lib.ndmps_gram_plan_query(3, 1, 64, 8, 0, 0, out) == _lib.EINVAL
+    assert lib.ndmps_gram_plan_query(0, 1, 64, 8, 0, 0, None) == _lib.EINVAL
 
 
 def test_shapes_without_a_route_need_no_workspace(lib):
