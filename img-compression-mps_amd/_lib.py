@@ -94,6 +94,9 @@ SIGNATURES = {
     "ndmps_lincomb_layout": (i64, [C.c_int, C.c_int, p_i64, p_i64, i64, p_i64, p_i64, p_i64]),
     "ndmps_lincomb_round": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_f64, C.c_double, i64,
                                       C.c_int, C.c_double, vp, i64, p_i64, p_f64, i64, vp, i64, vp]),
+    "ndmps_axisop_layout": (i64, [C.c_int, p_i64, p_i64, p_i64, p_i64, p_i64, p_i64]),
+    "ndmps_axisop_apply": (C.c_int, [C.c_int, p_i64, p_i64, C.c_int, C.POINTER(vp), p_i64, p_i64, p_i64, p_f64, i64, vp, i64,
+                                     vp, i64, vp]),
     "ndmps_series_gram_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_series_gram_route": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_series_gram": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_i64, p_int,

@@ -1011,7 +1011,6 @@ class NDMPS:
         objects that differ in qubit_size, shape, mode or device, or a summed bond above 4096.
         """
         torch = _torch()
-        lib = _lib.load()
         from . import lincomb as _lc
 
         objs = list(objs)
@@ -1023,16 +1022,26 @@ class NDMPS:
             raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
         _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
                                    dims=o.mps.dims) for o in objs])
-        bond_lists = [o.mps.bonds for o in objs]
-        _lc.check_summed_bonds(bond_lists)
-        codes = [_lc.dtype_code(o.mps.dtype) for o in objs]
+        _lc.check_summed_bonds([o.mps.bonds for o in objs])
+        scale = _lc.scale_of(w, [o.norm_value for o in objs])
+        return objs[0]._round_chains([o.mps for o in objs], w, cutoff, max_bond, dtype, scale)
+
+    def _round_chains(self, chains, w, cutoff, max_bond, dtype, scale) -> "NDMPS":
+        """The TT-SVD rounding of ``sum_a w[a] * chains[a]`` (DeviceMPS over this object's site dims, arguments already
+        checked) through ndmps_lincomb_round, as a new object like this one: ``norm=False``, boundary_list, norm_value
+        and sweep_spectra set.  ``scale`` is the absolute scale of the storage floor."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import lincomb as _lc
+
+        bond_lists = [m.bonds for m in chains]
+        codes = [_lc.dtype_code(m.dtype) for m in chains]
         f64 = dtype == torch.float64 or (dtype != torch.float32 and _lc.work_is_f64(codes))
         work = torch.float64 if f64 else torch.float32
-        scale = _lc.scale_of(w, [o.norm_value for o in objs])
-        first = objs[0]
-        device = first.mps.device
-        K, L = len(objs), first.mps.L
-        dims = first.mps.dims
+        first = chains[0]
+        device = first.device
+        K, L = len(chains), first.L
+        dims = first.dims
         mb = int(max_bond) if max_bond is not None else 0
         c_dims = _lib.i64_array(dims)
         c_bonds = _lib.i64_array([b for bl in bond_lists for b in bl])
@@ -1040,7 +1049,7 @@ class NDMPS:
         ws_bytes, stride = C.c_int64(0), C.c_int64(0)
         total = _lib.check(lib.ndmps_lincomb_layout(K, L, c_dims, c_bonds, mb, out_off, C.byref(ws_bytes),
                                                     C.byref(stride)))
-        ptrs = (C.c_void_p * (K * L))(*[c.data_ptr() for o in objs for c in o.mps.cores])
+        ptrs = (C.c_void_p * (K * L))(*[c.data_ptr() for m in chains for c in m.cores])
         out_bonds = (C.c_int64 * (L + 1))()
         spectra = np.zeros(L * max(int(stride.value), 1), dtype=np.float64)
         with torch.cuda.device(device):
@@ -1057,7 +1066,7 @@ class NDMPS:
                  for j in range(L)]
         if dtype == torch.bfloat16:
             cores = [c.to(torch.bfloat16) for c in cores]
-        out = first._like(cores, norm=False)
+        out = self._like(cores, norm=False)
         out.update_boundary_list()
         out.update_norm()
         st = int(stride.value)
@@ -1073,6 +1082,151 @@ class NDMPS:
         ``from_tensor(x, max_bond=chi)`` makes.  ``compress()`` (the reference's left-to-right two-site truncation)
         is unchanged."""
         return NDMPS.linear_combination([self], [1.0], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
+
+    # ------------------------------------------------------- axis operators on the cores (core/axisop.py)
+    def _axis_plan(self, axis):
+        """(axis as a non-negative int, the factor array, the axis length) for an operator along ``axis``; ValueError
+        without a known shape, for the last axis of a DCT-mode object, or for cores that are not over the shape's own
+        factor array."""
+        from . import axisop as _ax
+
+        shape = self._require_shape()
+        axis = _ax.normalize_axis(axis, len(shape))
+        _ax.check_data_axis(self.mode, axis, len(shape))
+        fa = _core.get_factorlist(tuple(shape))[0]
+        if self.mps.dims != [int(v) for v in np.prod(fa, axis=1)]:
+            raise ValueError("the cores are not over the site dims of this object's shape")
+        return axis, fa, int(shape[axis])
+
+    def _axis_apply(self, mpo, axis) -> DeviceMPS:
+        """The unrounded wide chain of the operator ``mpo`` (core/axisop.py AxisMPO) applied along ``axis``: bonds
+        ``D_k chi_k``, fp64 cores for fp64 storage and fp32 otherwise, computed by one launch (csrc/axisop.hip)."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import axisop as _ax
+        from . import lincomb as _lc
+
+        axis, fa, _ = self._axis_plan(axis)
+        mps = self.mps
+        _ax.check_plan(mpo, fa, axis, mps.dims)
+        _ax.check_wide_bonds(mpo.bonds, mps.bonds)
+        code = _lc.dtype_code(mps.dtype)
+        L, dims, device = mps.L, mps.dims, mps.device
+        c_dims, c_bonds = _lib.i64_array(dims), _lib.i64_array(mps.bonds)
+        c_f = _lib.i64_array(mpo.factors)
+        c_post = _lib.i64_array([post for _, _, post in _ax.site_split(fa, axis)])
+        c_D = _lib.i64_array(mpo.bonds)
+        table = np.concatenate([m.ravel() for m in mpo.cores])
+        out_off = (C.c_int64 * (L + 1))()
+        ws_bytes = C.c_int64(0)
+        total = _lib.check(lib.ndmps_axisop_layout(L, c_dims, c_bonds, c_f, c_D, out_off, C.byref(ws_bytes)))
+        with torch.cuda.device(device):
+            arena = torch.empty(int(total), dtype=torch.float64 if code == 2 else torch.float32, device=device)
+            ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=device)
+            with _span("axisop"):
+                _lib.check(lib.ndmps_axisop_apply(L, c_dims, c_bonds, code, mps._core_ptrs(), c_f, c_post, c_D,
+                                                  table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(),
+                                                  arena.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            del ws
+        wide = [d * b for d, b in zip(mpo.bonds, mps.bonds)]
+        return DeviceMPS([arena[out_off[j]: out_off[j + 1]].view(wide[j], dims[j], wide[j + 1]) for j in range(L)],
+                         _trusted=True)
+
+    def _axis_rounded(self, mpo, axis, cutoff, max_bond, dtype) -> "NDMPS":
+        """The operator applied along ``axis`` and rounded like ``recompress``; the storage floor is relative to
+        ``mpo.opnorm * norm_value``, a bound on the result's norm."""
+        torch = _torch()
+        from . import lincomb as _lc
+
+        _lc.check_args(1, [1.0], cutoff, max_bond)
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
+            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
+        wide = self._axis_apply(mpo, axis)
+        return self._round_chains([wide], [1.0], cutoff, max_bond, dtype, mpo.opnorm * float(self.norm_value))
+
+    def roll(self, shift, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
+        """
+        ``np.roll(to_tensor(), shift, axis)`` as a new object, computed on the cores: the shift is digit-wise addition
+        with a carry along the chain, an operator of bond 2 (core/axisop.py) that is applied to the cores in one launch
+        and rounded like ``recompress`` (same ``cutoff`` / ``max_bond`` / ``dtype``); no volume is formed.  ``axis`` is
+        required; tuples of shifts and axes are applied axis after axis, each with its own rounding (an int shift goes
+        with every axis of a tuple).  The result's bonds are at most twice the input's before ``max_bond``.
+
+        Raises TypeError for a non-integer shift or axis, ValueError (numpy's AxisError) for an axis out of range, for
+        tuples of different lengths, for the last axis of a DCT-mode object (its digits index DCT coefficients; the
+        other axes are fine) and for ``linear_combination``'s argument errors.  No counterpart in the reference.
+        """
+        from . import axisop as _ax
+
+        if isinstance(axis, tuple):
+            shifts = shift if isinstance(shift, tuple) else (shift,) * len(axis)
+            if len(shifts) != len(axis):
+                raise ValueError("shift and axis must have the same length")
+            plans = [(_ax.check_shift(s), self._axis_plan(a)[0]) for s, a in zip(shifts, axis)]  # every check first
+            if not plans:
+                return self.recompress(cutoff, max_bond, dtype)
+            out = self
+            for s, a in plans:
+                out = out.roll(s, a, cutoff, max_bond, dtype)
+            return out
+        shift = _ax.check_shift(shift)
+        axis, fa, _ = self._axis_plan(axis)
+        return self._axis_rounded(_ax.roll_mpo(fa[:, axis], shift), axis, cutoff, max_bond, dtype)
+
+    def shift(self, shift, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
+        """The volume moved by ``shift`` voxels along ``axis`` with zeros shifted in (``out[i] = x[i - shift]`` inside
+        the volume); ``abs(shift) >= n`` gives the zero MPS, as ``linear_combination`` returns it.  Otherwise as
+        ``roll`` with a single axis."""
+        from . import axisop as _ax
+
+        shift = _ax.check_shift(shift)
+        axis, fa, n = self._axis_plan(axis)
+        if abs(shift) >= n:
+            return NDMPS.linear_combination([self], [0.0], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
+        return self._axis_rounded(_ax.shift_mpo(fa[:, axis], shift), axis, cutoff, max_bond, dtype)
+
+    def correlate1d(self, weights, axis=-1, mode: str = "constant", origin: int = 0, cutoff: float = 0.0,
+                    max_bond=None, dtype=None) -> "NDMPS":
+        """
+        ``scipy.ndimage.correlate1d(to_tensor(), weights, axis, mode=mode, cval=0, origin=origin)`` on the cores:
+        ``out[i] = sum_j weights[j] * x[i + j - len(weights) // 2 - origin]`` with ``x`` zero outside the volume
+        (``mode="constant"``) or periodic (``"wrap"``).  The stencil is an operator of bond 3 (wider only at the finest
+        bond when the radius exceeds the finest digit), rounded like ``recompress`` with the storage floor relative to
+        ``sum |weights| * norm_value``.  Raises ValueError for weights that are not a non-empty 1-D array of finite
+        numbers, another ``mode``, an origin scipy refuses or a radius ``>= n``; axis errors as ``roll``.
+        """
+        from . import axisop as _ax
+
+        _ax.check_taps(weights)
+        _ax.check_mode(mode)
+        axis, fa, n = self._axis_plan(axis)
+        taps = _ax.correlate_taps(weights, origin, n)
+        return self._axis_rounded(_ax.offsets_mpo(fa[:, axis], taps, mode), axis, cutoff, max_bond, dtype)
+
+    def cumsum(self, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
+        """``np.cumsum(to_tensor(), axis)`` on the cores: an operator of bond 2, rounded like ``recompress``.  The
+        operator's norm is bounded by n, so the absolute storage floor is ``1e-6 * n * norm_value`` (1e-8 for fp64
+        work): directions of the result below that are dropped.  Axis errors as ``roll``."""
+        from . import axisop as _ax
+
+        axis, fa, _ = self._axis_plan(axis)
+        return self._axis_rounded(_ax.cumsum_mpo(fa[:, axis]), axis, cutoff, max_bond, dtype)
+
+    def flip(self, axis) -> "NDMPS":
+        """``np.flip(to_tensor(), axis)``: every digit of the axis reversed, a site-local permutation.  The cores are
+        permuted copies in the same storage type; bonds, gauge, ``norm``, ``norm_value``, ``boundary_list`` and
+        ``sweep_spectra`` are those of this object and nothing is rounded.  Axis errors as ``roll``."""
+        from . import axisop as _ax
+
+        axis, fa, _ = self._axis_plan(axis)
+        cores = [c.view(c.shape[0], pre, f, post, c.shape[2]).flip(2).reshape(c.shape).contiguous()
+                 for c, (pre, f, post) in zip(self.mps.cores, _ax.site_split(fa, axis))]
+        out = self._like(cores)
+        out.boundary_list = None if self.boundary_list is None else np.array(self.boundary_list, copy=True)
+        out.norm_value = self.norm_value
+        spec = self.sweep_spectra
+        out.sweep_spectra = None if spec is None else [None if s is None else np.array(s, copy=True) for s in spec]
+        return out
 
     # ------------------------------------------------------- Gram matrix and PCA of a series (core/series.py)
     @staticmethod

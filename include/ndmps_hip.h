@@ -558,6 +558,26 @@ int ndmps_lincomb_round(int K, int L, const int64_t* h_dims, const int64_t* h_bo
                         int64_t spec_stride, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Axis operators (no reference counterpart; core/axisop.py, csrc/axisop.hip): a matrix-product operator that acts on
+ * one axis's digit per site, applied to a chain of L sites in one launch.  Site j of the input is (chi_j, d_j,
+ * chi_{j+1}) with d_j = pre_j f_j post_j and the physical index (p f_j + digit) post_j + q; h_factors: the L radices
+ * f_j; h_strides: the L strides post_j; h_mpo_bonds: the L + 1 operator bonds D_j (outer ones 1); h_mpo: the cores
+ * M_j (D_j, f_j, f_j, D_{j+1}) indexed [c, o, i, c'], one after the other, mpo_len doubles in all.  Site j of the
+ * result is
+ *     Z_j[c chi_j + a, (p f_j + o) post_j + q, c' chi_{j+1} + a'] = sum_i M_j[c, o, i, c'] X_j[a, (p f_j + i) post_j + q, a']
+ * a (D_j chi_j, d_j, D_{j+1} chi_{j+1}) core; every widened bond must be <= 4096.  code: storage of the input (0 fp32,
+ * 1 bf16, 2 fp64); Z is fp64 for code 2 and fp32 otherwise, summed in fp64 over the entries of M that are not 0.
+ * ndmps_axisop_layout: returns the element count of the result; h_out_off (L + 1): site j starts at element
+ * h_out_off[j] of d_out; *h_ws_bytes: workspace.  ndmps_axisop_apply synchronises the stream.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_axisop_layout(int L, const int64_t* h_dims, const int64_t* h_bonds, const int64_t* h_factors,
+                            const int64_t* h_mpo_bonds, int64_t* h_out_off, int64_t* h_ws_bytes);
+int ndmps_axisop_apply(int L, const int64_t* h_dims, const int64_t* h_bonds, int code, const void* const* h_cores,
+                       const int64_t* h_factors, const int64_t* h_strides, const int64_t* h_mpo_bonds,
+                       const double* h_mpo, int64_t mpo_len, void* d_out, int64_t out_elems, void* d_ws,
+                       int64_t ws_bytes, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Gram matrix of a series (no reference counterpart; core/series.py, csrc/series.hip): d_G[a, b] = <X^a, X^b> for
  * every pair of two lists of chains with the same L site dims, fp64, row-major Ka x Kb on the device.
  * h_bonds_*: K x (L + 1) (outer bonds 1); h_codes_*: storage codes (0 fp32, 1 bf16, 2 fp64); h_cores_*: K x L device
