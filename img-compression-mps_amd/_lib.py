@@ -139,6 +139,7 @@ SIGNATURES = {
     "ndmps_syevd_topk_team_fallbacks": (i64, []),
     "ndmps_syevd_topk_team_slots": (C.c_int, [i64]),
     "ndmps_syevd_topk_note_team_fallback": (C.c_int, []),
+    "ndmps_syevd_topk_route_query": (C.c_int, [C.c_int, p_i64, i64, C.c_int, C.c_int, p_int, p_i64]),
     "ndmps_debug_inject_team_abort": (C.c_int, [C.c_int]),
     "ndmps_debug_lane_sums_f64": (C.c_int, [vp, vp, vp]),
     "ndmps_tt_sweep_pads_cores": (C.c_int, [C.c_int, p_i64, i64]),

@@ -2310,72 +2310,162 @@ __global__ void trd_inject_abort_kernel(TrdDesc* __restrict__ desc, int batch) {
 }
 
 // ------------------------------------------------------------------------------------------ host side
+// Every exported call (1) reads the environment once (trd_switches), (2) carves the workspace (trd_layout: offsets and
+// pointers from ONE list of buffers), (3) plans its launches (trd_route: a pure function of the sizes, the switches, the
+// thread's settings and the device's resident slots) and (4) launches what the plan says.  Nothing below trd_route
+// decides anything: a new route is an edit of trd_route and a row of tests/test_eig_route_host.py.
 constexpr bool kTeamXcdDefault = true;   // teams placed XCD by XCD (team_place) when NDMPS_TRD_XCD is not set
 constexpr bool kSymDefault = false;  // half-storage team kernel (batches beyond half the workgroup slots) when NDMPS_TRD_SYM is not set
 constexpr int kWideOrthoMinOrder = 1024;  // chip-wide orthonormalisation of <= 128 vectors: from this order on ...
 constexpr int kWideOrthoMaxBatch = 2;      // ... for at most this many matrices (they go one after the other)
 constexpr int kBandDefault = 0;  // semi-bandwidth of the two-stage reduction when NDMPS_TRD_BAND is not set (0: off)
 
-struct TrdLayout {
-  int64_t n_max, lda, kp;
-  int64_t off_a, off_vh, off_y, off_xc, off_yr, off_xr, off_sync, off_tau, off_d, off_e, off_lam, off_mu, off_bound, off_z, off_lu, off_piv, off_desc, off_desc2, off_stamps, off_tw, t_stride, off_yb, off_xb, off_band, off_qlog, q_stride, off_yrow, total;
-  int64_t off_pv, off_pw, off_ypart, off_spart, off_ucol, off_napart, pnl_blocks, pnl_tiles;
-  int64_t off_ws, off_wlinv, off_wgram, off_wt, wt_stride, kw, wgram_bytes, off_wpart, wpart_stride;  // more than kMaxK vectors (eig_wide.inc)
+// NDMPS_INVIT_CB=16|32|64|128 forces the width of the inverse iteration's column blocks.  Unlike every other switch it
+// is LATCHED by its first use (a tuning aid of tools/, set before the process starts): flipping it later does nothing.
+int invit_cb_forced() {
+  static const int forced = [] {
+    const char* e = getenv("NDMPS_INVIT_CB");
+    const int v = e ? atoi(e) : 0;
+    return (v == 16 || v == 32 || v == 64 || v == 128) ? v : 0;
+  }();
+  return forced;
+}
+
+// The switches of the solver, read afresh by every exported call (tests flip them inside one process) and nowhere
+// else: the only getenv of this file besides the latched NDMPS_INVIT_CB above.  A/B timing and tests of the routes
+// that are not the default; tools/README.md lists what each is for.
+struct TrdSwitches {
+  int band;            // NDMPS_TRD_BAND: the layout reserves the two-stage buffers for any non-zero value, the route takes 2 and 4
+  bool sym;            // NDMPS_TRD_SYM != 0: half-storage team kernel for batches beyond half the slots
+  bool no_team;        // NDMPS_TRD_NO_TEAM: no resident launches in the whole process
+  int64_t team_max;    // NDMPS_TRD_TEAM_MAX (at least 512): largest order the resident kernel takes; 2048 when not set
+  bool no_hybrid;      // NDMPS_TRD_NO_HYBRID: the panels run to the last kTail columns
+  int64_t panel_min;   // NDMPS_TRD_PANEL_MIN (at least 513: the workspace holds the panel arrays from there on); 0: not set
+  bool no_panel;       // NDMPS_TRD_NO_PANEL: column launches instead
+  bool panel_graph;    // NDMPS_TRD_PANEL_GRAPH: the panel launches replayed from a cached graph
+  bool team_narrow;    // NDMPS_TRD_TEAM_NARROW: a streamed caller is treated as one that is alone on the GPU
+  bool team_wide;      // NDMPS_TRD_TEAM_WIDE: 32-column blocks whatever fits
+  bool team_half;      // NDMPS_TRD_TEAM_HALF: launches of half the slots
+  bool xcd;            // NDMPS_TRD_XCD != 0 (kTeamXcdDefault): teams placed XCD by XCD
+  int pair;            // NDMPS_TRD_PAIR (1): second workgroup of a CU with its members in reverse order
+  bool wide;           // NDMPS_TRD_WIDE: 32-column blocks of the column launches
+  int tail;            // NDMPS_TRD_TAIL: -1 not set (by the batch), 1 "regs", 0 anything else (LDS)
+  bool full_turn;      // NDMPS_TEAM_FULL_TURN: no half turns
+  int invit_cb;        // NDMPS_INVIT_CB, latched (invit_cb_forced); 0: by the sizes
+  int invit_dbg;       // NDMPS_INVIT_DBG: ablation bits of trd_invit_kernel (tools/scratch)
+  bool ortho_narrow;   // NDMPS_ORTHO_NARROW: one workgroup per matrix also for one or two big matrices
+  bool ortho_columns;  // NDMPS_ORTHO_COLUMNS: column-by-column Gram-Schmidt for 65 .. 128 vectors
+  bool back_narrow;    // NDMPS_BACK_NARROW: the lane-dealt back-transformation also where a blocked one applies
+  bool no_side_stream; // NDMPS_NO_SIDE_STREAM: the T factors on the solve's own stream
 };
 
-TrdLayout trd_layout(int64_t n_max, int64_t batch, int64_t k_max) {
+TrdSwitches trd_switches() {
+  auto set = [](const char* name) { return getenv(name) != nullptr; };
+  auto as_int = [](const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+  };
+  auto as_i64 = [](const char* name) {
+    const char* e = getenv(name);
+    return e ? (int64_t)atoll(e) : 0;
+  };
+  TrdSwitches sw;
+  sw.band = as_int("NDMPS_TRD_BAND", kBandDefault);
+  sw.sym = as_int("NDMPS_TRD_SYM", kSymDefault) != 0;
+  sw.no_team = set("NDMPS_TRD_NO_TEAM");
+  sw.team_max = set("NDMPS_TRD_TEAM_MAX") ? std::max<int64_t>(as_i64("NDMPS_TRD_TEAM_MAX"), 512) : 2048;
+  sw.no_hybrid = set("NDMPS_TRD_NO_HYBRID");
+  sw.panel_min = set("NDMPS_TRD_PANEL_MIN") ? std::max<int64_t>(as_i64("NDMPS_TRD_PANEL_MIN"), 513) : 0;
+  sw.no_panel = set("NDMPS_TRD_NO_PANEL");
+  sw.panel_graph = set("NDMPS_TRD_PANEL_GRAPH");
+  sw.team_narrow = set("NDMPS_TRD_TEAM_NARROW");
+  sw.team_wide = set("NDMPS_TRD_TEAM_WIDE");
+  sw.team_half = set("NDMPS_TRD_TEAM_HALF");
+  sw.xcd = as_int("NDMPS_TRD_XCD", kTeamXcdDefault) != 0;
+  sw.pair = as_int("NDMPS_TRD_PAIR", 1);
+  sw.wide = set("NDMPS_TRD_WIDE");
+  const char* tail = getenv("NDMPS_TRD_TAIL");
+  sw.tail = tail ? (strcmp(tail, "regs") == 0 ? 1 : 0) : -1;
+  sw.full_turn = set("NDMPS_TEAM_FULL_TURN");
+  sw.invit_cb = invit_cb_forced();
+  sw.invit_dbg = as_int("NDMPS_INVIT_DBG", 0);
+  sw.ortho_narrow = set("NDMPS_ORTHO_NARROW");
+  sw.ortho_columns = set("NDMPS_ORTHO_COLUMNS");
+  sw.back_narrow = set("NDMPS_BACK_NARROW");
+  sw.no_side_stream = set("NDMPS_NO_SIDE_STREAM");
+  return sw;
+}
+
+// The workspace of a solve: offsets, and -- given the workspace -- the pointers, from one walk over one list of
+// buffers.  A function of the sizes and of the switches NDMPS_TRD_BAND / _SYM alone, never of the thread's settings:
+// every call of a solve, a recovery with the resident launches off included, sees the same one.
+struct TrdLayout {
+  int64_t n_max, lda, kp, total;
+  int64_t off_stamps, off_desc, off_desc2;  // what the size queries report
+  TrdWork w;                                // the buffers the kernels see
+  TrdDesc *desc, *desc2;  // desc2: the trailing blocks the resident kernel finishes behind the panels
+  // more than kMaxK vectors, or one or two big matrices (eig_wide.inc)
+  double *ws, *wlinv, *wt, *wpart;
+  char* wgram;
+  int64_t wt_stride, kw, wgram_bytes, wpart_stride;
+};
+
+TrdLayout trd_layout(int64_t n_max, int64_t batch, int64_t k_max, const TrdSwitches& sw, void* d_ws = nullptr) {
   TrdLayout l;
+  TrdWork& w = l.w;
   l.n_max = n_max;
   l.lda = ndmps::round_up(n_max, 2);
   l.kp = ndmps::round_up(std::max<int64_t>(k_max, 1), 16);
+  char* const base = (char*)d_ws;
   int64_t used = 0;
-  auto take = [&](int64_t bytes) {
+  auto take = [&](auto*& ptr, int64_t bytes) {
     const int64_t off = ndmps::round_up(used, 256);
     used = off + bytes;
+    ptr = base ? reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + off) : nullptr;
     return off;
   };
-  l.off_a = take(batch * n_max * l.lda * 8);
-  l.off_vh = take(batch * n_max * l.lda * 8);
-  l.off_y = take(batch * 2 * l.lda * 8);
-  l.off_xc = take(batch * 2 * l.lda * 8);
-  l.off_yr = take(batch * 2 * l.lda * 16);
-  l.off_xr = take(batch * 2 * l.lda * 16);
-  l.off_sync = take(batch * (int64_t)sizeof(TeamSync));
-  l.off_tau = take(batch * n_max * 8);
-  l.off_d = take(batch * n_max * 8);
-  l.off_e = take(batch * n_max * 8);
-  l.off_lam = take(batch * n_max * 8);
-  l.off_mu = take(batch * n_max * 8);
-  l.off_bound = take(batch * 8);
-  l.off_z = take(batch * n_max * l.kp * 8);
-  l.off_lu = take(batch * 4 * n_max * l.kp * 8);
-  l.off_piv = take(batch * n_max * l.kp);
-  l.off_desc = take(batch * (int64_t)sizeof(TrdDesc));
-  l.off_desc2 = take(batch * (int64_t)sizeof(TrdDesc));  // the trailing blocks the resident kernel finishes behind the panels
-  l.off_stamps = take(batch * 16 * 8);
-  l.t_stride = (n_max + 8) * 4;  // groups of WYB reflectors, WYB^2 doubles each, WYB <= 4
-  l.off_tw = take(batch * l.t_stride * 8);
+  take(w.A, batch * n_max * l.lda * 8);
+  take(w.Vh, batch * n_max * l.lda * 8);
+  take(w.y, batch * 2 * l.lda * 8);
+  take(w.xc, batch * 2 * l.lda * 8);
+  take(w.yr, batch * 2 * l.lda * 16);
+  take(w.xr, batch * 2 * l.lda * 16);
+  take(w.sync, batch * (int64_t)sizeof(TeamSync));
+  take(w.tau, batch * n_max * 8);
+  take(w.d, batch * n_max * 8);
+  take(w.e, batch * n_max * 8);
+  take(w.lam, batch * n_max * 8);
+  take(w.mu, batch * n_max * 8);
+  take(w.bound, batch * 8);
+  take(w.Z, batch * n_max * l.kp * 8);
+  take(w.lu, batch * 4 * n_max * l.kp * 8);
+  take(w.piv, batch * n_max * l.kp);
+  l.off_desc = take(l.desc, batch * (int64_t)sizeof(TrdDesc));
+  l.off_desc2 = take(l.desc2, batch * (int64_t)sizeof(TrdDesc));
+  l.off_stamps = take(w.stamps, batch * 16 * 8);
+  w.t_stride = (n_max + 8) * 4;  // groups of WYB reflectors, WYB^2 doubles each, WYB <= 4
+  take(w.Tw, batch * w.t_stride * 8);
   // two-stage reduction (orders <= 512, eig_band.inc): exchange vectors, the band, the log of the bulge chase -- 2 MB per
-  // order-512 matrix, reserved only when the environment (or the built-in default) selects that route.  The layout is a
-  // function of its arguments and the environment alone: every call of a solve sees the same one.
-  const bool band_ok = n_max <= 512 && (getenv("NDMPS_TRD_BAND") ? atoi(getenv("NDMPS_TRD_BAND")) != 0 : kBandDefault != 0);
-  const bool sym_ok = n_max <= 512 && (getenv("NDMPS_TRD_SYM") ? atoi(getenv("NDMPS_TRD_SYM")) != 0 : kSymDefault);
-  l.off_yb = take(band_ok ? batch * 2 * kBandMax * l.lda * 8 : 0);
-  l.off_xb = take(band_ok ? batch * 2 * kBandMax * l.lda * 8 : 0);
-  l.off_band = take(band_ok ? batch * n_max * 2 * kBandMax * 8 : 0);
-  l.q_stride = band_ok ? n_max * (n_max + 2 * kBandMax) : 0;
-  l.off_qlog = take(batch * l.q_stride * 8);
-  l.off_yrow = take(sym_ok ? batch * 2 * 8 * l.lda * 8 : 0);
+  // order-512 matrix, reserved only when the environment (or the built-in default) selects that route
+  const bool band_ok = n_max <= 512 && sw.band != 0;
+  const bool sym_ok = n_max <= 512 && sw.sym;
+  take(w.yb, band_ok ? batch * 2 * kBandMax * l.lda * 8 : 0);
+  take(w.xb, band_ok ? batch * 2 * kBandMax * l.lda * 8 : 0);
+  take(w.band, band_ok ? batch * n_max * 2 * kBandMax * 8 : 0);
+  w.q_stride = band_ok ? n_max * (n_max + 2 * kBandMax) : 0;
+  take(w.qlog, batch * w.q_stride * 8);
+  take(w.yrow, sym_ok ? batch * 2 * 8 * l.lda * 8 : 0);
   // panel-blocked reduction (orders above 512, eig_panel.inc)
   const bool panel_ok = n_max > 512;
-  l.pnl_blocks = ndmps::ceil_div(n_max, kPnlTB);
-  l.pnl_tiles = l.pnl_blocks * (l.pnl_blocks + 1) / 2;
-  l.off_pv = take(panel_ok ? batch * n_max * kPnlNB * 8 : 0);
-  l.off_pw = take(panel_ok ? batch * n_max * kPnlNB * 8 : 0);
-  l.off_ypart = take(panel_ok ? batch * l.pnl_blocks * l.lda * 8 : 0);
-  l.off_spart = take(panel_ok ? batch * l.pnl_tiles * 8 : 0);
-  l.off_ucol = take(panel_ok ? batch * 2 * l.lda * 8 : 0);
-  l.off_napart = take(panel_ok ? batch * 2 * l.pnl_blocks * kPnlNa * 8 : 0);
+  const int64_t pnl_blocks = ndmps::ceil_div(n_max, kPnlTB);
+  w.pnl_blocks_max = (int)pnl_blocks;
+  w.pnl_tiles_max = (int)(pnl_blocks * (pnl_blocks + 1) / 2);
+  take(w.pv, panel_ok ? batch * n_max * kPnlNB * 8 : 0);
+  take(w.pw, panel_ok ? batch * n_max * kPnlNB * 8 : 0);
+  take(w.ypart, panel_ok ? batch * pnl_blocks * l.lda * 8 : 0);
+  take(w.spart, panel_ok ? batch * (int64_t)w.pnl_tiles_max * 8 : 0);
+  take(w.ucol, panel_ok ? batch * 2 * l.lda * 8 : 0);
+  take(w.napart, panel_ok ? batch * 2 * pnl_blocks * kPnlNa * 8 : 0);
   // more than kMaxK eigenvectors (eig_wide.inc): Gram matrix, L^-1 and the Gram kernel's partial tiles, one set for
   // the whole batch (its matrices are orthonormalised one after the other)
   // ... and one or two big matrices with up to kMaxK vectors: the single workgroup per matrix of trd_ortho_*_kernel
@@ -2383,60 +2473,21 @@ TrdLayout trd_layout(int64_t n_max, int64_t batch, int64_t k_max) {
   const bool wide_small = n_max >= kWideOrthoMinOrder && batch <= kWideOrthoMaxBatch;
   l.kw = (k_max > kMaxK || wide_small) ? ndmps::round_up(l.kp, kWB) : 0;
   l.wgram_bytes = l.kw ? ndmps_gram_f64_workspace_bytes(n_max, l.kp) : 0;
-  l.off_ws = take(l.kw * l.kw * 8);
-  l.off_wlinv = take(l.kw * l.kw * 8);
-  l.off_wgram = take(l.wgram_bytes);
+  take(l.ws, l.kw * l.kw * 8);
+  take(l.wlinv, l.kw * l.kw * 8);
+  take(l.wgram, l.wgram_bytes);
   l.wt_stride = l.kw ? ndmps::ceil_div(n_max, kBwB) * kBwB * kBwB : 0;  // T factors of the blocked back-transformation
-  l.off_wt = take(batch * l.wt_stride * 8);
+  take(l.wt, batch * l.wt_stride * 8);
   // partial products of the row-dealt back-transformation (back_rows_step_kernel): [2][chunks][64][kp] per matrix
   l.wpart_stride = wide_small ? 2 * ndmps::ceil_div(n_max, kBrR) * kBwB * l.kp : 0;
-  l.off_wpart = take(batch * l.wpart_stride * 8);
+  take(l.wpart, batch * l.wpart_stride * 8);
   l.total = ndmps::round_up(used, 256);
-  return l;
-}
-
-TrdWork trd_work(const TrdLayout& l, void* d_ws) {
-  char* base = (char*)d_ws;
-  TrdWork w;
-  w.A = (double*)(base + l.off_a);
-  w.Vh = (double*)(base + l.off_vh);
-  w.y = (double*)(base + l.off_y);
-  w.xc = (double*)(base + l.off_xc);
-  w.yr = (TeamRec*)(base + l.off_yr);
-  w.xr = (TeamRec*)(base + l.off_xr);
-  w.sync = (TeamSync*)(base + l.off_sync);
-  w.tau = (double*)(base + l.off_tau);
-  w.d = (double*)(base + l.off_d);
-  w.e = (double*)(base + l.off_e);
-  w.lam = (double*)(base + l.off_lam);
-  w.mu = (double*)(base + l.off_mu);
-  w.bound = (double*)(base + l.off_bound);
-  w.Z = (double*)(base + l.off_z);
-  w.lu = (double*)(base + l.off_lu);
-  w.piv = (unsigned char*)(base + l.off_piv);
-  w.stamps = (long long*)(base + l.off_stamps);
-  w.Tw = (double*)(base + l.off_tw);
-  w.t_stride = l.t_stride;
-  w.yb = (double*)(base + l.off_yb);
-  w.xb = (double*)(base + l.off_xb);
-  w.band = (double*)(base + l.off_band);
-  w.qlog = (double*)(base + l.off_qlog);
-  w.q_stride = l.q_stride;
-  w.yrow = (double*)(base + l.off_yrow);
-  w.pv = (double*)(base + l.off_pv);
-  w.pw = (double*)(base + l.off_pw);
-  w.ypart = (double*)(base + l.off_ypart);
-  w.spart = (double*)(base + l.off_spart);
-  w.ucol = (double*)(base + l.off_ucol);
-  w.napart = (double*)(base + l.off_napart);
-  w.pnl_blocks_max = (int)l.pnl_blocks;
-  w.pnl_tiles_max = (int)l.pnl_tiles;
   w.tail_lower = 0;
   w.xcd_team = w.xcd_count = w.xcd_pair = 0;
   w.n_max = (int)l.n_max;
   w.lda = (int)l.lda;
   w.kp = (int)l.kp;
-  return w;
+  return l;
 }
 
 // inverse-iteration kernel: Cholesky factor [128][129], aliased by the scaled tridiagonal as (d, e) pairs
@@ -2454,6 +2505,13 @@ thread_local int g_team_streamed = 0;
 std::atomic<long long> g_team_fallbacks{0};
 std::atomic<int> g_inject_abort{0};
 
+// ndmps_debug_inject_team_abort: true if this resident launch is one of those to be replaced
+bool take_injected_abort() {
+  int left = g_inject_abort.load();
+  while (left > 0 && !g_inject_abort.compare_exchange_weak(left, left - 1)) {
+  }
+  return left > 0;
+}
 
 // kernels that need more than 64 KB of dynamic LDS are opted in once per device
 int trd_opt_in() {
@@ -2489,8 +2547,6 @@ int trd_opt_in() {
   return NDMPS_OK;
 }
 
-// Semi-bandwidth of the two-stage reduction for a batch whose largest order is n_max, 0 = one-stage paths.  A pure
-// function of its arguments and the environment: phase 1 and phase 2 of a solve must agree on it.
 // The route phase 1 took on a workspace (semi-bandwidth of the two-stage reduction, 0: one-stage): phase 2 replays
 // the reflector logs of THAT route, whatever the thread's switches say by then (a recovery redoes phase 1 with the
 // resident launches off, i.e. one-stage; phase 2 then must not apply the bulge chase's reflectors).
@@ -2507,45 +2563,35 @@ int route_load(const void* ws, int fallback) {
   return it == g_route.end() ? fallback : it->second;
 }
 
-int band_width_for(int64_t n_max) {
-  if (n_max > 512 || n_max <= kTail || getenv("NDMPS_TRD_NO_TEAM") || g_team_off) return 0;
-  const char* e = getenv("NDMPS_TRD_BAND");
-  const int bw = e ? atoi(e) : kBandDefault;
-  return (bw == 2 || bw == 4) ? bw : 0;
+// Semi-bandwidth of the two-stage reduction for a batch whose largest order is n_max, 0 = one-stage paths.  A pure
+// function of its arguments: phase 1 and phase 2 of a solve must agree on it.
+int band_width_for(int64_t n_max, const TrdSwitches& sw, bool team_off) {
+  if (n_max > 512 || n_max <= kTail || sw.no_team || team_off) return 0;
+  return (sw.band == 2 || sw.band == 4) ? sw.band : 0;
 }
 
-// workgroups of trd_team_kernel the current device keeps resident at once (occupancy x compute units); rows_per_thread:
-// 2 (orders <= 512), 4 (<= 1024) or 8 (<= 2048: one workgroup per CU)
-int team_slots(int& slots, int rows_per_thread = 2) {
+// Workgroups of trd_team_kernel the current device keeps resident at once (occupancy x compute units), for the kernels
+// with 2 (orders <= 512), 4 (<= 1024) and 8 (<= 2048: one workgroup per CU) rows per thread.  Asked once per device,
+// after the opt-in (the occupancy of the 8-row kernel is asked with its opted-in LDS).
+int trd_device_slots(int slots[3]) {
   static std::mutex mu;
-  static int cached[3][64] = {};
+  static int cached[64][3] = {};
   int dev = 0;
   NDMPS_CHECK_HIP(hipGetDevice(&dev));
   NDMPS_REQUIRE(dev >= 0 && dev < 64, "device index %d outside [0, 64)", dev);
-  const int cls = rows_per_thread <= 2 ? 0 : rows_per_thread <= 4 ? 1 : 2;
   std::lock_guard<std::mutex> lock(mu);
-  if (cached[cls][dev] == 0) {
-    int per_cu = 0, cus = 0;
-    if (cls == 0) NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trd_team_kernel<2, false>, 256, 512 * sizeof(RowVec)));
-    else if (cls == 1) NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trd_team_kernel<4, true, 8>, 256, 1024 * sizeof(RowVec)));
-    else NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trd_team_kernel<8, true, 8>, 256, 2048 * sizeof(RowVec)));
+  if (cached[dev][0] == 0) {
+    NDMPS_TRY(trd_opt_in());
+    int per_cu[3] = {}, cus = 0;
+    NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[0], trd_team_kernel<2, false>, 256, 512 * sizeof(RowVec)));
+    NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[1], trd_team_kernel<4, true, 8>, 256, 1024 * sizeof(RowVec)));
+    NDMPS_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[2], trd_team_kernel<8, true, 8>, 256, 2048 * sizeof(RowVec)));
     NDMPS_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     // the register budget allows two 256-thread workgroups per CU (one of the 8-row kernel); never count on more
-    cached[cls][dev] = std::max(1, std::min(per_cu, cls == 2 ? 1 : 2)) * std::max(cus, 1);
+    for (int cls = 2; cls >= 0; --cls) cached[dev][cls] = std::max(1, std::min(per_cu[cls], cls == 2 ? 1 : 2)) * std::max(cus, 1);
   }
-  slots = cached[cls][dev];
+  std::copy(cached[dev], cached[dev] + 3, slots);
   return NDMPS_OK;
-}
-
-// At most one team kernel in flight per device (see trd_team_kernel); the turn is taken on the device
-// (ndmps::Turn, util.hip).
-template <typename F>
-int team_launch(hipStream_t s, F&& launch, bool half = false) {
-  // a launch that fills one workgroup slot per CU takes half the turn: two of them fit the GPU together
-  ndmps::Turn turn(s, ndmps::kTurnTeam, half && !getenv("NDMPS_TEAM_FULL_TURN") ? 1u : 2u, 2u);
-  NDMPS_TRY(turn.begin());
-  launch();
-  return turn.end();
 }
 
 int trd_check_sizes(int batch, const int64_t* h_n, int64_t& n_max) {
@@ -2559,16 +2605,250 @@ int trd_check_sizes(int batch, const int64_t* h_n, int64_t& n_max) {
   return NDMPS_OK;
 }
 
-// Smallest order that takes the panel-blocked reduction.  A dependent launch costs ~5 us here whatever it does: two of
-// them per column (10.7 us at any order) beat the column launch -- one launch, but the trailing matrix read and
-// written, 7.6 us per column at order 1024, 13.5 at 2048, 35 at 4096 -- from about order 1500 on
+// ---- the plan of a solve
+enum class TrdReduce { Columns, Band2, Band4, Team, BigTeam, Panel, PanelHybrid };  // NDMPS_EIG_ROUTE_SLOTS, slot 0
+enum class TeamKernel {  // slot 2
+  None,
+  Tagged2,  // trd_team_kernel<2, true, 8>: 8-column blocks, tagged records (orders <= 512)
+  Meet2,    // trd_team_kernel<2, false>: 32-column blocks that meet at a counter
+  Sym,      // trd_sym_kernel: half storage, 32-column blocks
+  Tagged4,  // trd_team_kernel<4, true, 8>: orders 513 .. 1024
+  Tagged8,  // trd_team_kernel<8, true, 8>: orders 1025 .. 2048
+  Band2,    // trd_band_kernel<2> / <4>: dense -> band, 32-column blocks
+  Band4,
+};
+enum class TrdTail { None, Registers, Lds };                      // slot 15; None: the bulge chase ends at T
+enum class TrdOrtho { WideAuto, Wide, Small, Blocks, Columns };  // slot 19
+enum class TrdBack { Lanes, Rows, Wide };                         // slot 20
+
+// A resident launch sequence: `per_launch` teams of `team_size` workgroups at a time under one device-side turn.  A
+// launch never holds more workgroups than the device keeps resident at once: no team then depends on the order in
+// which the dispatcher places workgroups (larger batches go in several launches).
+struct TeamGeom {
+  TeamKernel kernel = TeamKernel::None;
+  int order = 0;  // what the kernel reduces: the batch's largest order, or the hand-over width behind the panels
+  int team_size = 0, per_launch = 0, lds_bytes = 0;
+  bool xcd_placed = false;  // 1-D grid placed team by team on the XCDs (team_place)
+  int xcd_pair = 0;
+  bool half_turn = false;  // a launch that fills one workgroup slot per CU takes half the turn: two of them fit the GPU together
+};
+
+// rows of the lane-dealt back-transformation (trd_back_kernel<SEG, R, RB, WYB>): n <= SEG * R rows per column, RB
+// reflectors of SEG * R doubles per LDS block, WY groups of WYB reflectors; the first class that holds the order
+constexpr int kBackLanes[6][4] = {{32, 4, 8, 4}, {32, 8, 8, 4}, {32, 16, 8, 4}, {32, 32, 4, 2}, {64, 32, 2, 2}, {64, 64, 1, 1}};
+
+struct TrdRoute {
+  // phase 1
+  TrdReduce reduce = TrdReduce::Columns;
+  int band = 0;     // semi-bandwidth of the two-stage reduction, 0: one-stage
+  int handover = 0; // PanelHybrid: the last columns the resident kernel takes (2048, 1024 or 512)
+  TeamGeom team;    // Band2 / Band4 / Team / BigTeam / PanelHybrid
+  int col_width = 0, col_rows = 0, col_launches = 0;  // Columns: trd_column_kernel<col_rows, col_width>
+  int tail_cols = 0;       // Panel / PanelHybrid: columns the panels leave
+  bool panel_graph = false;
+  int tail_lower = 0;      // the tail kernel finds only the stored half of the trailing block
+  TrdTail tail = TrdTail::None;
+  // phase 2
+  int invit_cb = 0, invit_dbg = 0;
+  TrdOrtho ortho = TrdOrtho::Small;
+  TrdBack back = TrdBack::Lanes;
+  int back_class = 0;       // Lanes: row of kBackLanes
+  bool side_stream = false;  // Rows / Wide: their T factors are formed on the side stream, beside everything up to the orthonormalisation
+};
+
+// What trd_route is a function of.  `kk`: the largest rank phase 2 is asked for (phase 1 and the query: min(k_max, n_max)).
+struct TrdCase {
+  int batch;
+  const int64_t* h_n;
+  int64_t n_max;
+  int kk;
+  TrdSwitches sw;
+  bool team_off, streamed;  // the thread's settings (ndmps_syevd_topk_set_team / _set_streamed)
+  int slots[3];             // resident workgroups of the team kernels with 2, 4 and 8 rows per thread
+};
+
+int slot_class(int64_t order) { return order <= 512 ? 0 : order <= 1024 ? 1 : 2; }
+
+// Resident tridiagonalisation (trd_team_kernel and variants) of `batch` matrices of order <= 2048, all columns up to the
+// last kTail.  Used for whole matrices and for the last columns behind the panel-blocked reduction.
+TeamGeom team_geometry(int batch, int64_t order, const TrdCase& c) {
+  const TrdSwitches& sw = c.sw;
+  const int slots = c.slots[slot_class(order)];
+  TeamGeom g;
+  g.order = (int)order;
+  if (order > 512) {
+    // orders 513 .. 2048: 8-column blocks, 4 or 8 rows per thread, tagged records; 128 / 256 workgroups per matrix,
+    // so a team spans XCDs whatever the placement (the exchange is agent-scope: MALL, not an XCD's L2)
+    g.kernel = order <= 1024 ? TeamKernel::Tagged4 : TeamKernel::Tagged8;
+    g.team_size = (int)ndmps::ceil_div(order, 8);
+    g.per_launch = std::max(1, slots / g.team_size);
+    g.lds_bytes = (order <= 1024 ? 1024 : 2048) * (int)sizeof(RowVec);
+    return g;
+  }
+  // 8-column blocks (64 workgroups per order-512 matrix, one per CU) while they fit the slots -- HALF the slots when the
+  // caller keeps several batches in flight (a narrow launch that takes half a turn leaves room for its neighbours' as
+  // well; measured on three lanes, ms per batch of 256^3 volumes, narrow / wide: 1 volume 2.8 / 3.2, 2: 3.2 / 3.4,
+  // 4: 3.8 / 3.9, 8: 6.0 / 5.0).  NDMPS_TRD_TEAM_NARROW=1: A/B.
+  // 8-column blocks exchange without meetings (tagged records), 32-column blocks meet at a counter: a tagged
+  // 32-column kernel was 3 % faster for 9 .. 16 order-512 matrices (1.84 vs 1.90 ms) and as fast for 32, but its 128
+  // registers of matrix per thread leave no room for the records in flight (round 4: spills, removed)
+  const bool streamed = c.streamed && !sw.team_narrow;
+  const bool narrow = (int64_t)batch * ndmps::ceil_div(order, 8) <= (streamed ? slots / 2 : slots) && !sw.team_wide;
+  // opt-in, batches that fill more than half the slots (17 order-512 matrices and more): half storage (eig_sym.inc),
+  // 8 workgroups per order-512 matrix -- a group of 32 takes one workgroup slot per CU and shares the GPU with the
+  // other group's reduction or kernels
+  const bool sym = !narrow && sw.sym && (int64_t)batch * ndmps::ceil_div(order, 32) > slots / 2;
+  g.kernel = sym ? TeamKernel::Sym : narrow ? TeamKernel::Tagged2 : TeamKernel::Meet2;
+  g.team_size = sym ? (int)ndmps::ceil_div(ndmps::ceil_div(order, 32), 2) : (int)ndmps::ceil_div(order, narrow ? 8 : 32);
+  // NDMPS_TRD_TEAM_HALF=1 (A/B): launches of half the slots (16 order-512 matrices, one workgroup per CU) under a half turn,
+  // so that the reductions of two batches in flight run side by side instead of alternating
+  const bool half_launches = sw.team_half && !narrow && !sym;
+  g.per_launch = std::max(1, (half_launches ? slots / 2 : slots) / g.team_size);
+  g.lds_bytes = sym ? 0 : 512 * (int)sizeof(RowVec);
+  g.xcd_placed = sw.xcd;
+  // early leavers (low block-columns) beside late ones: needs whole teams on either side of every 32nd workgroup
+  const bool pairable = 32 % g.team_size == 0 || g.team_size % 32 == 0;
+  g.xcd_pair = g.xcd_placed && !sym && pairable ? sw.pair : 0;
+  // half a turn only for what fits half the slots
+  g.half_turn = (int64_t)std::min(g.per_launch, batch) * g.team_size <= slots / 2 && !sw.full_turn;
+  return g;
+}
+
+// The launches of a solve.  PURE: no environment, no HIP call, no thread-local -- everything it depends on is in `c`
+// and in the layout (itself a function of the sizes and the switches).  The kinds of reduction, in the order tried:
+//   Band2 / Band4   orders kTail+1 .. 512 with NDMPS_TRD_BAND=2|4 and the resident launches on (eig_band.inc)
+//   Team            orders kTail+1 .. 512 with the resident launches on: one resident launch for all columns (2.2 ms for
+//                   1 .. 16 matrices of order 512, 2.5 ms for 32, against 2.4 / 3.8 / 5.7 ms of column launches)
+//   BigTeam         orders 513 .. min(NDMPS_TRD_TEAM_MAX, 2048) whose teams (n / 8 workgroups each) are all resident at
+//                   once: 3 - 5 us per column against 11 us of the two panel launches
+//   PanelHybrid     even orders above 512, one order for the whole batch: panels, then the resident kernel for the last
+//                   2048 / 1024 / 512 columns -- the widest the switches allow that leaves a panel tile (kPnlTB columns)
+//                   and whose teams are all resident in one launch; only from panel_min on
+//   Panel           orders from panel_min on (eig_panel.inc): two launches per column down to the last kTail
+//   Columns         everything else: one launch per column down to the last kTail (none for orders <= kTail)
+// panel_min: NDMPS_TRD_PANEL_MIN, else 1024 behind a hand-over and 1536 without.  A dependent launch costs ~5 us here
+// whatever it does: two of them per column (10.7 us at any order) beat the column launch -- one launch, but the trailing
+// matrix read and written, 7.6 us per column at order 1024, 13.5 at 2048, 35 at 4096 -- from about order 1500 on
 // (profiles/r04_f_panel_probe.txt: 9.6 vs 6.8 ms at 1024, 22.2 vs 26.2 at 2048, 63 vs 140 at 4096).  When the last
-// 512 columns go to the resident kernel (`hybrid` below) the break-even is order 1024 for one matrix (6.9 vs 6.8 ms)
-// and far below for a batch (8 of order 1024: 8.8 vs 12.6 ms; profiles/r04_w_panel_probe.txt).
-int64_t panel_min_order(bool hybrid) {
-  const char* e = getenv("NDMPS_TRD_PANEL_MIN");
-  const int64_t v = e ? atoll(e) : hybrid ? 1024 : 1536;
-  return std::max<int64_t>(v, 513);  // the workspace holds the panel arrays from order 513 on
+// 512 columns go to the resident kernel the break-even is order 1024 for one matrix (6.9 vs 6.8 ms) and far below for a
+// batch (8 of order 1024: 8.8 vs 12.6 ms; profiles/r04_w_panel_probe.txt).
+TrdRoute trd_route(const TrdCase& c, const TrdLayout& l) {
+  const TrdSwitches& sw = c.sw;
+  const int batch = c.batch;
+  const int64_t n_max = c.n_max;
+  TrdRoute r;
+  // ---- phase 1
+  const bool team_on = !sw.no_team && !c.team_off;
+  r.band = band_width_for(n_max, sw, c.team_off);
+  auto team_fits = [&](int64_t order) { return (int64_t)batch * ndmps::ceil_div(order, 8) <= c.slots[slot_class(order)]; };
+  // Hand-over of a panel-blocked reduction to the resident kernel.  Needs one order for the whole batch (the view is
+  // one offset into the workspace), an even one (the parity of a column selects its exchange buffer on both sides), the
+  // resident launches switched on, and every team of the batch resident in one launch.
+  auto handover = [&]() {
+    if (n_max % 2 != 0 || sw.no_hybrid) return 0;
+    for (int b = 0; b < batch; ++b)
+      if (c.h_n[b] != n_max) return 0;
+    for (int h = 2048; h >= 512; h /= 2)
+      if (h <= sw.team_max && n_max - h >= kPnlTB && team_fits(h)) return h;
+    return 0;
+  };
+  if (r.band) {
+    r.reduce = r.band == 2 ? TrdReduce::Band2 : TrdReduce::Band4;
+    r.team.kernel = r.band == 2 ? TeamKernel::Band2 : TeamKernel::Band4;
+    r.team.order = (int)n_max;
+    r.team.team_size = (int)ndmps::ceil_div(n_max, 32);
+    r.team.per_launch = std::max(1, c.slots[0] / r.team.team_size);
+  } else if (team_on && n_max <= 512 && n_max > kTail) {
+    r.reduce = TrdReduce::Team;
+    r.team = team_geometry(batch, n_max, c);
+    r.tail_lower = r.team.kernel == TeamKernel::Sym ? 1 : 0;
+  } else if (team_on && n_max > 512 && n_max <= std::min<int64_t>(sw.team_max, 2048) && team_fits(n_max)) {
+    r.reduce = TrdReduce::BigTeam;
+    r.team = team_geometry(batch, n_max, c);
+  } else {
+    r.handover = team_on && n_max > 512 ? handover() : 0;
+    const int64_t panel_min = sw.panel_min ? sw.panel_min : r.handover ? 1024 : 1536;
+    if (n_max >= panel_min && !sw.no_panel) {
+      r.reduce = r.handover ? TrdReduce::PanelHybrid : TrdReduce::Panel;
+      r.tail_cols = r.handover ? r.handover : kTail;
+      r.panel_graph = sw.panel_graph;
+      // the panels leave the stored half; the resident kernel hands the trailing block over in full storage
+      r.tail_lower = r.handover ? 0 : 1;
+      if (r.handover) r.team = team_geometry(batch, r.handover, c);
+    } else {
+      r.handover = 0;
+      // narrow column blocks while the grid stays below ~2 workgroups per CU (see trd_column_kernel)
+      r.col_width = (int64_t)batch * ndmps::ceil_div(n_max, 8) <= 2 * ndmps::kNumCU && !sw.wide ? 8 : 32;
+      r.col_rows = n_max <= 512 ? 2 : n_max <= 1024 ? 4 : n_max <= 2048 ? 8 : 16;
+      r.col_launches = (int)std::max<int64_t>(n_max - kTail, 0);
+    }
+  }
+  // small batches (nothing else on the GPU): the tail in registers, two barriers per column; lockstep groups: the tail
+  // in LDS -- 70 registers per thread, it starts beside the resident kernel's last workgroups (158 would wait)
+  if (!r.band) r.tail = (sw.tail >= 0 ? sw.tail == 1 : batch < 16) ? TrdTail::Registers : TrdTail::Lds;
+  // ---- phase 2
+  // Width of the column blocks of the inverse iteration.  The recurrences of a column are a dependent chain over the rows
+  // whatever the width; what a block's ONE CU adds is the traffic of its helpers -- three operand arrays in, one out per sweep
+  // and column, 8.4 MB per sweep at order 2048 with 128 columns, at the 30 - 60 GB/s a single CU gets.  From order 1024 on the
+  // columns go to as many CUs as the launch leaves free (blocks of 16 at least); lockstep groups of order <= 512 keep one
+  // block per matrix (their CUs are wanted by the other group's kernels).
+  r.invit_cb = kMaxK;
+  if (sw.invit_cb) r.invit_cb = sw.invit_cb;
+  else if (n_max >= 1024)
+    while (r.invit_cb > 16 && (int64_t)batch * ndmps::ceil_div(l.kp, r.invit_cb / 2) <= 256) r.invit_cb /= 2;
+  r.invit_dbg = sw.invit_dbg;
+  const int k16 = (c.kk + 15) & ~15;
+  // one or two big matrices: Cholesky-QR across the chip with the rank read on the device; more than kMaxK vectors:
+  // Cholesky-QR across the chip, matrix by matrix (eig_wide.inc); else one workgroup per matrix
+  if (l.kp <= kMaxK && l.kw > 0 && !sw.ortho_narrow) r.ortho = TrdOrtho::WideAuto;
+  else if (l.kp > kMaxK) r.ortho = TrdOrtho::Wide;
+  else if (k16 <= 64) r.ortho = TrdOrtho::Small;
+  else r.ortho = sw.ortho_columns ? TrdOrtho::Columns : TrdOrtho::Blocks;  // Blocks: column blocks of 64 (block Gram-Schmidt + blocked Cholesky-QR)
+  // one or two big matrices, at most 128 columns: rows dealt to the chip, one launch per block of 64 reflectors; many
+  // columns: the reflectors in blocks of 64 on the MFMA, one workgroup per 16 columns; else rows dealt to the lanes
+  if (r.ortho == TrdOrtho::WideAuto && l.wpart_stride > 0 && !sw.back_narrow) r.back = TrdBack::Rows;
+  else if (l.kp > kMaxK && !sw.back_narrow) r.back = TrdBack::Wide;
+  else
+    while (n_max > (int64_t)kBackLanes[r.back_class][0] * kBackLanes[r.back_class][1] && r.back_class < 5) ++r.back_class;
+  r.side_stream = r.back != TrdBack::Lanes && !sw.no_side_stream;
+  return r;
+}
+
+// At most one team kernel in flight per device (see trd_team_kernel); the turn is taken on the device
+// (ndmps::Turn, util.hip).
+std::atomic<unsigned> g_team_epoch{1};  // names a launch in the tags of its exchange records
+int trd_team_launch(const TeamGeom& g, int batch, TrdDesc* desc, const TrdWork& w, hipStream_t s) {
+  if (take_injected_abort()) {
+    hipLaunchKernelGGL(trd_inject_abort_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch);
+    return NDMPS_OK;
+  }
+  ndmps::Turn turn(s, ndmps::kTurnTeam, g.half_turn ? 1u : 2u, 2u);
+  NDMPS_TRY(turn.begin());
+  for (int b0 = 0; b0 < batch; b0 += g.per_launch) {
+    const int count = std::min(g.per_launch, batch - b0);
+    TrdWork wl = w;
+    dim3 grid((unsigned)g.team_size, (unsigned)count);
+    if (g.xcd_placed) {
+      wl.xcd_team = g.team_size;
+      wl.xcd_count = count;
+      wl.xcd_pair = g.xcd_pair;
+      grid = dim3((unsigned)(g.team_size * count));
+    }
+    const size_t lds = (size_t)g.lds_bytes;
+    // the band kernels carry no launch tag
+    const unsigned epoch = g.kernel == TeamKernel::Band2 || g.kernel == TeamKernel::Band4 ? 0u : g_team_epoch.fetch_add(1);
+    switch (g.kernel) {
+      case TeamKernel::Tagged2: hipLaunchKernelGGL((trd_team_kernel<2, true, 8>), grid, dim3(256), lds, s, desc, wl, b0, epoch); break;
+      case TeamKernel::Meet2: hipLaunchKernelGGL((trd_team_kernel<2, false>), grid, dim3(256), lds, s, desc, wl, b0, epoch); break;
+      case TeamKernel::Sym: hipLaunchKernelGGL(trd_sym_kernel, grid, dim3(256), lds, s, desc, wl, b0); break;
+      case TeamKernel::Tagged4: hipLaunchKernelGGL((trd_team_kernel<4, true, 8>), grid, dim3(256), lds, s, desc, wl, b0, epoch); break;
+      case TeamKernel::Tagged8: hipLaunchKernelGGL((trd_team_kernel<8, true, 8>), grid, dim3(256), lds, s, desc, wl, b0, epoch); break;
+      case TeamKernel::Band2: hipLaunchKernelGGL(trd_band_kernel<2>, grid, dim3(256), lds, s, desc, wl, b0); break;
+      case TeamKernel::Band4: hipLaunchKernelGGL(trd_band_kernel<4>, grid, dim3(256), lds, s, desc, wl, b0); break;
+      case TeamKernel::None: break;
+    }
+  }
+  return turn.end();
 }
 
 // ---- launch sequence of the panel-blocked reduction, eager (default) or as a cached graph
@@ -2590,8 +2870,8 @@ struct PnlGraph {
 };
 constexpr size_t kPnlGraphs = 8;  // least recently used beyond that is destroyed
 
-int pnl_run(const std::vector<PnlLaunch>& seq, int batch, const int64_t* h_n, int64_t n_max, int tail_cols, TrdDesc* desc,
-            const TrdWork& w, hipStream_t s) {
+int pnl_run(const std::vector<PnlLaunch>& seq, int batch, const int64_t* h_n, int64_t n_max, int tail_cols, bool graph,
+            TrdDesc* desc, const TrdWork& w, hipStream_t s) {
   const unsigned B = (unsigned)batch;
   void (*const vec)(const TrdDesc*, TrdWork, int, int, int) =
       n_max <= 1024 ? pnl_vec_kernel<4> : (n_max <= 2048 ? pnl_vec_kernel<8> : pnl_vec_kernel<16>);
@@ -2603,7 +2883,7 @@ int pnl_run(const std::vector<PnlLaunch>& seq, int batch, const int64_t* h_n, in
   // (the sequence is bound by the dependent launches, not by the host: 24.7 ms either way at order 2048) and only frees
   // the host thread -- but a graph holds the workspace addresses, and instantiating one (3900 nodes) costs about a
   // second: a caller whose workspace moves between calls would pay that every time.
-  if (!getenv("NDMPS_TRD_PANEL_GRAPH")) {
+  if (!graph) {
     for (const PnlLaunch& q : seq)
       hipLaunchKernelGGL(kernels[q.kind], dim3(q.grid_x, B), dim3(256), 0, s, (const TrdDesc*)desc, w, q.j, n_uniform, tail_cols);
     NDMPS_LAUNCH_CHECK();
@@ -2675,262 +2955,112 @@ int pnl_run(const std::vector<PnlLaunch>& seq, int batch, const int64_t* h_n, in
   return NDMPS_OK;
 }
 
-// Resident tridiagonalisation (trd_team_kernel and variants) of `batch` matrices of order <= 512 named by `desc`, all
-// columns up to the last kTail in one launch (or a few, by the resident slots); takes the device-side turn.  Used for
-// orders <= 512 and for the last 512 columns behind the panel-blocked reduction (a view of the workspace).
-std::atomic<unsigned> g_team_epoch{1};  // names a launch in the tags of its exchange records
-int trd_team_reduce(int batch, int64_t n_max, TrdDesc* desc, TrdWork& w, hipStream_t s) {
-    if (n_max > 512) {
-      // orders 513 .. 2048: 8-column blocks, 4 or 8 rows per thread, tagged records; 128 / 256 workgroups per matrix,
-      // so a team spans XCDs whatever the placement (the exchange is agent-scope: MALL, not an XCD's L2)
-      NDMPS_REQUIRE(n_max <= 2048, "resident reduction of order %lld > 2048", (long long)n_max);
-      const int nr = n_max <= 1024 ? 4 : 8;
-      int slots = 0;
-      NDMPS_TRY(team_slots(slots, nr));
-      const int team_size = (int)ndmps::ceil_div(n_max, 8);
-      const int per_launch = std::max(1, slots / team_size);
-      w.tail_lower = 0;
-      int inject = g_inject_abort.load();
-      while (inject > 0 && !g_inject_abort.compare_exchange_weak(inject, inject - 1)) {
-      }
-      if (inject > 0) {
-        hipLaunchKernelGGL(trd_inject_abort_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch);
-        return NDMPS_OK;
-      }
-      return team_launch(s, [&]() {
-        for (int b0 = 0; b0 < batch; b0 += per_launch) {
-          const unsigned epoch = g_team_epoch.fetch_add(1);
-          const dim3 grid((unsigned)team_size, (unsigned)std::min(per_launch, batch - b0));
-          TrdWork wl = w;
-          wl.xcd_count = 0;
-          if (nr == 4) hipLaunchKernelGGL((trd_team_kernel<4, true, 8>), grid, dim3(256), 1024 * sizeof(RowVec), s, desc, wl, b0, epoch);
-          else hipLaunchKernelGGL((trd_team_kernel<8, true, 8>), grid, dim3(256), 2048 * sizeof(RowVec), s, desc, wl, b0, epoch);
-        }
-      });
-    }
-    // a launch never holds more workgroups than the device keeps resident at once: no team then depends on the
-    // order in which the dispatcher places workgroups (larger batches go in several launches)
-    int slots = 0;
-    NDMPS_TRY(team_slots(slots));
-    // one to four matrices: 8-column blocks (64 workgroups per order-512 matrix, one per CU)
-    // 8-column blocks while they fit the slots -- HALF the slots when the caller keeps several batches in flight (a narrow
-    // launch that takes half a turn leaves room for its neighbours' as well; measured on three lanes, ms per batch of 256^3
-    // volumes, narrow / wide: 1 volume 2.8 / 3.2, 2: 3.2 / 3.4, 4: 3.8 / 3.9, 8: 6.0 / 5.0).  NDMPS_TRD_TEAM_NARROW=1: A/B.
-    const bool streamed = g_team_streamed && !getenv("NDMPS_TRD_TEAM_NARROW");
-    const bool narrow_team = (int64_t)batch * ndmps::ceil_div(n_max, 8) <= (streamed ? slots / 2 : slots) &&
-                             !getenv("NDMPS_TRD_TEAM_WIDE");
-    // opt-in, batches that fill more than half the slots (17 order-512 matrices and more): half storage (eig_sym.inc),
-    // 8 workgroups per order-512 matrix -- a group of 32 takes one workgroup slot per CU and shares the GPU with the
-    // other group's reduction or kernels
-    const char* sym_env = getenv("NDMPS_TRD_SYM");
-    const bool sym = !narrow_team && n_max <= 512 && (sym_env ? atoi(sym_env) != 0 : kSymDefault) &&
-                     (int64_t)batch * ndmps::ceil_div(n_max, 32) > slots / 2;
-    w.tail_lower = sym ? 1 : 0;
-    const int team_size = sym ? (int)ndmps::ceil_div(ndmps::ceil_div(n_max, 32), 2) : (int)ndmps::ceil_div(n_max, narrow_team ? 8 : 32);
-    // NDMPS_TRD_TEAM_HALF=1 (A/B): launches of half the slots (16 order-512 matrices, one workgroup per CU) under a half turn,
-    // so that the reductions of two batches in flight run side by side instead of alternating
-    const bool half_launches = getenv("NDMPS_TRD_TEAM_HALF") != nullptr && !narrow_team && !sym;
-    const int per_launch = std::max(1, (half_launches ? slots / 2 : slots) / team_size);
-    const char* xcd_env = getenv("NDMPS_TRD_XCD");
-    const bool xcd_placed = xcd_env ? atoi(xcd_env) != 0 : kTeamXcdDefault;
-    int inject = g_inject_abort.load();
-    while (inject > 0 && !g_inject_abort.compare_exchange_weak(inject, inject - 1)) {
-    }
-    if (inject > 0) {
-      hipLaunchKernelGGL(trd_inject_abort_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch);
-    } else
-    NDMPS_TRY(team_launch(s, [&]() {
-      // 8-column blocks exchange without meetings (tagged records), 32-column blocks meet at a counter: a tagged
-      // 32-column kernel was 3 % faster for 9 .. 16 order-512 matrices (1.84 vs 1.90 ms) and as fast for 32, but its 128
-      // registers of matrix per thread leave no room for the records in flight (round 4: spills, removed)
-      for (int b0 = 0; b0 < batch; b0 += per_launch) {
-        const unsigned epoch = g_team_epoch.fetch_add(1);
-        const int count = std::min(per_launch, batch - b0);
-        TrdWork wl = w;
-        dim3 grid((unsigned)team_size, (unsigned)count);
-        if (xcd_placed) {
-          wl.xcd_team = team_size;
-          wl.xcd_count = count;
-          // early leavers (low block-columns) beside late ones: needs whole teams on either side of every 32nd workgroup
-          const bool pairable = 32 % team_size == 0 || team_size % 32 == 0;
-          wl.xcd_pair = sym || !pairable ? 0 : getenv("NDMPS_TRD_PAIR") ? atoi(getenv("NDMPS_TRD_PAIR")) : 1;
-          grid = dim3((unsigned)(team_size * count));
-        }
-        if (sym) hipLaunchKernelGGL(trd_sym_kernel, grid, dim3(256), 0, s, desc, wl, b0);
-        else if (narrow_team) hipLaunchKernelGGL((trd_team_kernel<2, true, 8>), grid, dim3(256), 512 * sizeof(RowVec), s, desc, wl, b0, epoch);
-        else hipLaunchKernelGGL((trd_team_kernel<2, false>), grid, dim3(256), 512 * sizeof(RowVec), s, desc, wl, b0, epoch);
-      }
-    }, (int64_t)std::min(per_launch, batch) * team_size <= slots / 2));  // half a turn only for what fits half the slots
-  return NDMPS_OK;
-}
-
-// Tridiagonalisation of every matrix named by the descriptors (resident launch for orders <= 512 unless switched
-// off, column launches otherwise), the last kTail columns in LDS, then the min(k_max, n) largest eigenvalues.
-int trd_reduce_and_values(int batch, const int64_t* h_n, int64_t n_max, int64_t k_max, const TrdLayout& l, const TrdWork& w_in,
-                          TrdDesc* desc, hipStream_t s) {
-  TrdWork w = w_in;  // tail_lower is decided here
+// Phase 1 as planned by `r`: tridiagonalisation of every matrix named by the descriptors, the last kTail columns in one
+// workgroup, then the min(k_max, n) largest eigenvalues.
+int trd_reduce_and_values(int batch, const int64_t* h_n, int64_t n_max, int64_t k_max, const TrdLayout& l, const TrdRoute& r,
+                          hipStream_t s) {
+  TrdWork w = l.w;
+  TrdDesc* desc = l.desc;
   const unsigned B = (unsigned)batch;
   const int load_grid = (int)std::min<int64_t>(ndmps::ceil_div(n_max * l.lda, 256), 512);
   hipLaunchKernelGGL(trd_load_kernel, dim3(load_grid, B), dim3(256), 0, s, desc, w);
-  // narrow column blocks while the grid stays below ~2 workgroups per CU (see trd_column_kernel)
-  const bool narrow = (int64_t)batch * ndmps::ceil_div(n_max, 8) <= 2 * ndmps::kNumCU && !getenv("NDMPS_TRD_WIDE");
-  const int W = (int)ndmps::ceil_div(n_max, narrow ? 8 : 32);
-  const size_t col_lds = (size_t)n_max * sizeof(RowVec);
-  void (*column)(const TrdDesc*, TrdWork, int);
-  if (narrow)
-    column = n_max <= 512    ? trd_column_kernel<2, 8>
-             : n_max <= 1024 ? trd_column_kernel<4, 8>
-             : n_max <= 2048 ? trd_column_kernel<8, 8>
-                             : trd_column_kernel<16, 8>;
-  else
-    column = n_max <= 512    ? trd_column_kernel<2, 32>
-             : n_max <= 1024 ? trd_column_kernel<4, 32>
-             : n_max <= 2048 ? trd_column_kernel<8, 32>
-                             : trd_column_kernel<16, 32>;
-  // orders <= 512: one resident launch for all columns (trd_team_kernel; 2.2 ms for 1 .. 16 matrices of order
-  // 512, 2.5 ms for 32, against 2.4 / 3.8 / 5.7 ms of column launches); NDMPS_TRD_NO_TEAM=1 keeps the column
-  // launches (A/B timing, tests of that path)
-  const int bw = band_width_for(n_max);
-  route_store(w_in.A, bw);
-  const bool team = !bw && n_max <= 512 && n_max > kTail && !getenv("NDMPS_TRD_NO_TEAM") && !g_team_off;
-  if (bw) {
-    // two-stage reduction (eig_band.inc): dense -> band with one exchange per panel, then the bulge chase
-    int slots = 0;
-    NDMPS_TRY(team_slots(slots));
-    const int team_size = (int)ndmps::ceil_div(n_max, 32);
-    const int per_launch = std::max(1, slots / team_size);
-    int inject = g_inject_abort.load();
-    while (inject > 0 && !g_inject_abort.compare_exchange_weak(inject, inject - 1)) {
-    }
-    void* span = ndmps::span_begin(s);
-    if (inject > 0) {
-      hipLaunchKernelGGL(trd_inject_abort_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch);
-    } else {
-      NDMPS_TRY(team_launch(s, [&]() {
-        for (int b0 = 0; b0 < batch; b0 += per_launch) {
-          const dim3 grid((unsigned)team_size, (unsigned)std::min(per_launch, batch - b0));
-          if (bw == 2) hipLaunchKernelGGL(trd_band_kernel<2>, grid, dim3(256), 0, s, desc, w, b0);
-          else hipLaunchKernelGGL(trd_band_kernel<4>, grid, dim3(256), 0, s, desc, w, b0);
-        }
-      }));
-    }
-    int64_t bytes = 0;
-    for (int b = 0; b < batch; ++b) bytes += 2 * 8 * h_n[b] * h_n[b];
-    ndmps::span_end(span, s, ndmps::kSpanTridiagTeam, 1, bytes);
-    const size_t chase_lds = (size_t)n_max * 2 * bw * sizeof(double);
-    if (bw == 2) hipLaunchKernelGGL(trd_chase_kernel<2>, dim3(1, B), dim3(1024), chase_lds, s, desc, w);
-    else hipLaunchKernelGGL(trd_chase_kernel<4>, dim3(1, B), dim3(1024), chase_lds, s, desc, w);
-    const int kk = (int)std::min(k_max, n_max);
-    hipLaunchKernelGGL(trd_bisect_kernel, dim3(ndmps::ceil_div(kk, 4), B), dim3(256),
-                       (size_t)ndmps::round_up(n_max, 16) * 16, s, desc, w, kk);
-    NDMPS_LAUNCH_CHECK();
-    return NDMPS_OK;
-  }
-  // Orders 513 .. 2048 whose teams (n / 8 workgroups each) are all resident at once: the whole reduction in the
-  // resident kernel (3 - 5 us per column against 11 us of the two panel launches).  NDMPS_TRD_TEAM_MAX=512 keeps it
-  // to the orders of the lockstep groups (A/B timing, tests of the other routes).
-  const bool team_on = !bw && !g_team_off && !getenv("NDMPS_TRD_NO_TEAM");
-  const int64_t team_max = getenv("NDMPS_TRD_TEAM_MAX") ? std::max<int64_t>(atoll(getenv("NDMPS_TRD_TEAM_MAX")), 512) : 2048;
-  auto team_fits = [&](int64_t order, bool& fits) -> int {
-    int slots = 0;
-    NDMPS_TRY(team_slots(slots, order <= 512 ? 2 : order <= 1024 ? 4 : 8));
-    fits = (int64_t)batch * ndmps::ceil_div(order, 8) <= slots;
-    return NDMPS_OK;
-  };
-  bool big_team = false;
-  if (team_on && n_max > 512 && n_max <= std::min<int64_t>(team_max, 2048)) NDMPS_TRY(team_fits(n_max, big_team));
-  // Hand-over of a panel-blocked reduction to the resident kernel for its last 2048 / 1024 / 512 columns.  Needs one
-  // order for the whole batch (the view below is one offset into the workspace), an even one (the parity of a column
-  // selects its exchange buffer on both sides), the resident launches switched on, and every team of the batch
-  // resident in one launch.
-  int hybrid = 0;
-  if (team_on && !big_team && n_max > 512 && n_max % 2 == 0 && !getenv("NDMPS_TRD_NO_HYBRID")) {
-    bool uniform = true;
-    for (int b = 0; b < batch && uniform; ++b) uniform = h_n[b] == n_max;
-    for (int h = 2048; h >= 512 && uniform && !hybrid; h /= 2) {
-      bool fits = false;
-      if (h > team_max || n_max - h < kPnlTB) continue;
-      NDMPS_TRY(team_fits(h, fits));
-      if (fits) hybrid = h;
-    }
-  }
+  w.tail_lower = r.tail_lower;
+  route_store(w.A, r.band);
+  const int kk = (int)std::min(k_max, n_max);
   void* span = ndmps::span_begin(s);
   int64_t span_bytes = 0;  // algorithmic: every trailing element read once and written once per column
-  if (team || big_team) {
-    NDMPS_TRY(trd_team_reduce(batch, n_max, desc, w, s));
-    // algorithmic traffic of the resident reduction: the matrix in, the reflectors out
-    for (int b = 0; b < batch; ++b) span_bytes += 2 * 8 * h_n[b] * h_n[b];
-    ndmps::span_end(span, s, ndmps::kSpanTridiagTeam, 1, span_bytes);
-  } else if (n_max >= panel_min_order(hybrid != 0) && !getenv("NDMPS_TRD_NO_PANEL")) {
-    // panel-blocked reduction (eig_panel.inc): two launches per column, one update per panel of kPnlNB columns
-    NDMPS_CHECK_HIP(hipMemsetAsync(w.Vh, 0, (size_t)batch * n_max * l.lda * 8, s));
-    NDMPS_CHECK_HIP(hipMemsetAsync(w.pv, 0, (size_t)batch * n_max * kPnlNB * 8, s));
-    NDMPS_CHECK_HIP(hipMemsetAsync(w.pw, 0, (size_t)batch * n_max * kPnlNB * 8, s));
-    const int tail_cols = hybrid ? hybrid : kTail;
-    w.tail_lower = hybrid ? 0 : 1;
-    const int J_max = (int)n_max - tail_cols;
-    std::vector<char> ends((size_t)J_max + 1, 0);
-    for (int b = 0; b < batch; ++b) ends[(size_t)std::max<int64_t>(h_n[b] - tail_cols, 0)] = 1;
-    const int nbm = (int)l.pnl_blocks;
-    auto tiles = [&](int first_col) {
-      const int nblk = nbm - first_col / kPnlTB;
-      return (unsigned)(nblk * (nblk + 1) / 2);
-    };
-    // the launch sequence: (kernel, grid.x, column)
-    std::vector<PnlLaunch> seq;
-    seq.reserve((size_t)2 * J_max + J_max / kPnlNB + 4);
-    for (int j = 0; j <= J_max; ++j) {
-      seq.push_back({0, (unsigned)(nbm - j / kPnlTB), j});
-      if (j >= 1 && (j % kPnlNB == 0 || ends[(size_t)j])) seq.push_back({1, tiles(j), j});
-      if (j < J_max) seq.push_back({2, tiles(j + 1), j});
-      if (span)
-        for (int b = 0; b < batch; ++b)
-          if (j < h_n[b] - tail_cols) span_bytes += 4 * (h_n[b] - j - 1) * (h_n[b] - j - 1);  // the lower half, read once
+  switch (r.reduce) {
+    case TrdReduce::Band2:
+    case TrdReduce::Band4: {
+      // two-stage reduction (eig_band.inc): dense -> band with one exchange per panel, then the bulge chase
+      NDMPS_TRY(trd_team_launch(r.team, batch, desc, w, s));
+      for (int b = 0; b < batch; ++b) span_bytes += 2 * 8 * h_n[b] * h_n[b];
+      ndmps::span_end(span, s, ndmps::kSpanTridiagTeam, 1, span_bytes);
+      const size_t chase_lds = (size_t)n_max * 2 * r.band * sizeof(double);
+      if (r.band == 2) hipLaunchKernelGGL(trd_chase_kernel<2>, dim3(1, B), dim3(1024), chase_lds, s, desc, w);
+      else hipLaunchKernelGGL(trd_chase_kernel<4>, dim3(1, B), dim3(1024), chase_lds, s, desc, w);
+      break;
     }
-    NDMPS_TRY(pnl_run(seq, batch, h_n, n_max, tail_cols, desc, w, s));
-    if (hybrid) {
-      // the trailing 512 x 512 block in full storage, then the resident kernel on a VIEW of the workspace: matrix,
-      // reflector rows, T's diagonals and the pending product of its last column all sit at offset J0 of the big
-      // arrays, so the tail kernel finds everything where the column launches would have left it
-      const int64_t J0 = n_max - hybrid;
-      TrdDesc* sub = (TrdDesc*)((char*)w_in.A - l.off_a + l.off_desc2);
-      hipLaunchKernelGGL(pnl_mirror_kernel, dim3(256, B), dim3(256), 0, s, w, (int)n_max, hybrid);
-      hipLaunchKernelGGL(pnl_subdesc_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, (const TrdDesc*)desc, sub, batch, hybrid);
-      TrdWork v = w;
-      v.A = w.A + J0 * l.lda + J0;
-      v.Vh = w.Vh + J0 * l.lda + J0;
-      v.y = w.y + J0;
-      v.tau = w.tau + J0;
-      v.d = w.d + J0;
-      v.e = w.e + J0;
-      NDMPS_TRY(trd_team_reduce(batch, hybrid, sub, v, s));
-      hipLaunchKernelGGL(pnl_substatus_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, (const TrdDesc*)sub, batch);
-      w.tail_lower = 0;  // the resident kernel hands the trailing block over in full storage
-    } else {
-      // nothing is pending when the tail kernel takes over: its update of "the last column launch" must vanish
-      NDMPS_CHECK_HIP(hipMemsetAsync(w.y, 0, (size_t)batch * 2 * l.lda * 8, s));
+    case TrdReduce::Team:
+    case TrdReduce::BigTeam:
+      NDMPS_TRY(trd_team_launch(r.team, batch, desc, w, s));
+      // algorithmic traffic of the resident reduction: the matrix in, the reflectors out
+      for (int b = 0; b < batch; ++b) span_bytes += 2 * 8 * h_n[b] * h_n[b];
+      ndmps::span_end(span, s, ndmps::kSpanTridiagTeam, 1, span_bytes);
+      break;
+    case TrdReduce::Panel:
+    case TrdReduce::PanelHybrid: {
+      // panel-blocked reduction (eig_panel.inc): two launches per column, one update per panel of kPnlNB columns
+      NDMPS_CHECK_HIP(hipMemsetAsync(w.Vh, 0, (size_t)batch * n_max * l.lda * 8, s));
+      NDMPS_CHECK_HIP(hipMemsetAsync(w.pv, 0, (size_t)batch * n_max * kPnlNB * 8, s));
+      NDMPS_CHECK_HIP(hipMemsetAsync(w.pw, 0, (size_t)batch * n_max * kPnlNB * 8, s));
+      const int tail_cols = r.tail_cols;
+      const int J_max = (int)n_max - tail_cols;
+      std::vector<char> ends((size_t)J_max + 1, 0);
+      for (int b = 0; b < batch; ++b) ends[(size_t)std::max<int64_t>(h_n[b] - tail_cols, 0)] = 1;
+      const int nbm = w.pnl_blocks_max;
+      auto tiles = [&](int first_col) {
+        const int nblk = nbm - first_col / kPnlTB;
+        return (unsigned)(nblk * (nblk + 1) / 2);
+      };
+      // the launch sequence: (kernel, grid.x, column)
+      std::vector<PnlLaunch> seq;
+      seq.reserve((size_t)2 * J_max + J_max / kPnlNB + 4);
+      for (int j = 0; j <= J_max; ++j) {
+        seq.push_back({0, (unsigned)(nbm - j / kPnlTB), j});
+        if (j >= 1 && (j % kPnlNB == 0 || ends[(size_t)j])) seq.push_back({1, tiles(j), j});
+        if (j < J_max) seq.push_back({2, tiles(j + 1), j});
+        if (span)
+          for (int b = 0; b < batch; ++b)
+            if (j < h_n[b] - tail_cols) span_bytes += 4 * (h_n[b] - j - 1) * (h_n[b] - j - 1);  // the lower half, read once
+      }
+      NDMPS_TRY(pnl_run(seq, batch, h_n, n_max, tail_cols, r.panel_graph, desc, w, s));
+      if (r.reduce == TrdReduce::PanelHybrid) {
+        // the trailing block in full storage, then the resident kernel on a VIEW of the workspace: matrix, reflector
+        // rows, T's diagonals and the pending product of its last column all sit at offset J0 of the big arrays, so
+        // the tail kernel finds everything where the column launches would have left it
+        const int64_t J0 = n_max - r.handover;
+        hipLaunchKernelGGL(pnl_mirror_kernel, dim3(256, B), dim3(256), 0, s, w, (int)n_max, r.handover);
+        hipLaunchKernelGGL(pnl_subdesc_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, (const TrdDesc*)desc, l.desc2, batch, r.handover);
+        TrdWork v = w;
+        v.A = w.A + J0 * l.lda + J0;
+        v.Vh = w.Vh + J0 * l.lda + J0;
+        v.y = w.y + J0;
+        v.tau = w.tau + J0;
+        v.d = w.d + J0;
+        v.e = w.e + J0;
+        NDMPS_TRY(trd_team_launch(r.team, batch, l.desc2, v, s));
+        hipLaunchKernelGGL(pnl_substatus_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, (const TrdDesc*)l.desc2, batch);
+      } else {
+        // nothing is pending when the tail kernel takes over: its update of "the last column launch" must vanish
+        NDMPS_CHECK_HIP(hipMemsetAsync(w.y, 0, (size_t)batch * 2 * l.lda * 8, s));
+      }
+      ndmps::span_end(span, s, ndmps::kSpanTridiagPanel, (int64_t)seq.size(), span_bytes);
+      break;
     }
-    ndmps::span_end(span, s, ndmps::kSpanTridiagPanel, (int64_t)seq.size(), span_bytes);
-  } else {
-    for (int j = 0; j < n_max - kTail; ++j) {
-      hipLaunchKernelGGL(column, dim3(W, B), dim3(256), col_lds, s, desc, w, j);
-      if (span)
-        for (int b = 0; b < batch; ++b)
-          if (j < h_n[b] - kTail) span_bytes += 2 * 8 * (h_n[b] - j - 1) * (h_n[b] - j - 1);
+    case TrdReduce::Columns: {
+      static void (*const kColumn[2][4])(const TrdDesc*, TrdWork, int) = {
+          {trd_column_kernel<2, 8>, trd_column_kernel<4, 8>, trd_column_kernel<8, 8>, trd_column_kernel<16, 8>},
+          {trd_column_kernel<2, 32>, trd_column_kernel<4, 32>, trd_column_kernel<8, 32>, trd_column_kernel<16, 32>}};
+      const auto column = kColumn[r.col_width == 32][r.col_rows == 2 ? 0 : r.col_rows == 4 ? 1 : r.col_rows == 8 ? 2 : 3];
+      const int W = (int)ndmps::ceil_div(n_max, r.col_width);
+      const size_t col_lds = (size_t)n_max * sizeof(RowVec);
+      for (int j = 0; j < r.col_launches; ++j) {
+        hipLaunchKernelGGL(column, dim3(W, B), dim3(256), col_lds, s, desc, w, j);
+        if (span)
+          for (int b = 0; b < batch; ++b)
+            if (j < h_n[b] - kTail) span_bytes += 2 * 8 * (h_n[b] - j - 1) * (h_n[b] - j - 1);
+      }
+      ndmps::span_end(span, s, ndmps::kSpanTridiagColumns, r.col_launches, span_bytes);
+      break;
     }
-    ndmps::span_end(span, s, ndmps::kSpanTridiagColumns, std::max<int64_t>(n_max - kTail, 0), span_bytes);
   }
-  // small batches (nothing else on the GPU): the tail in registers, two barriers per column; lockstep groups: the tail
-  // in LDS -- 70 registers per thread, it starts beside the resident kernel's last workgroups (158 would wait)
-  const char* tail_env = getenv("NDMPS_TRD_TAIL");
-  const bool tail_regs = tail_env ? !strcmp(tail_env, "regs") : batch < 16;
-  void* tail_span = ndmps::span_begin(s);
-  if (tail_regs) hipLaunchKernelGGL(trd_tail_reg_kernel, dim3(1, B), dim3(512), 0, s, desc, w);
-  else hipLaunchKernelGGL(trd_tail_kernel, dim3(1, B), dim3(512), kTailLds, s, desc, w);
-  const int kk = (int)std::min(k_max, n_max);
+  void* tail_span = r.tail == TrdTail::None ? nullptr : ndmps::span_begin(s);
+  if (r.tail == TrdTail::Registers) hipLaunchKernelGGL(trd_tail_reg_kernel, dim3(1, B), dim3(512), 0, s, desc, w);
+  if (r.tail == TrdTail::Lds) hipLaunchKernelGGL(trd_tail_kernel, dim3(1, B), dim3(512), kTailLds, s, desc, w);
   hipLaunchKernelGGL(trd_bisect_kernel, dim3(ndmps::ceil_div(kk, 4), B), dim3(256),
                      (size_t)ndmps::round_up(n_max, 16) * 16, s, desc, w, kk);
-  ndmps::span_end(tail_span, s, ndmps::kSpanTridiagTail, 2, 0);
+  if (r.tail != TrdTail::None) ndmps::span_end(tail_span, s, ndmps::kSpanTridiagTail, 2, 0);
   NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
@@ -2973,10 +3103,40 @@ extern "C" int ndmps_potrf_lower_f64(double* d_S, int64_t n, double* d_scratch, 
   return NDMPS_OK;
 }
 
+namespace {
+struct TrdCall {
+  int64_t n_max = 0;
+  TrdLayout l;
+  TrdRoute r;
+};
+// What the four calls of a solve share: the sizes checked, the switches read, the workspace checked and carved, the
+// launches planned.  h_k: the ranks phase 2 is asked for (NULL: up to min(k_max, n_max)); team_off: the thread's
+// setting, or true for a recovery.
+int trd_prepare(int batch, const int64_t* h_n, const int64_t* h_k, int64_t k_max, int64_t k_limit, bool team_off, void* d_ws,
+                int64_t ws_bytes, TrdCall& call) {
+  NDMPS_TRY(trd_check_sizes(batch, h_n, call.n_max));
+  NDMPS_REQUIRE(k_max >= 1 && k_max <= k_limit, "k_max=%lld outside [1, %lld]", (long long)k_max, (long long)k_limit);
+  TrdCase c;
+  c.batch = batch, c.h_n = h_n, c.n_max = call.n_max;
+  c.kk = h_k ? 1 : (int)std::min(k_max, call.n_max);
+  for (int b = 0; h_k && b < batch; ++b) c.kk = (int)std::max<int64_t>(c.kk, h_k[b]);
+  c.sw = trd_switches();
+  c.team_off = team_off, c.streamed = g_team_streamed != 0;
+  call.l = trd_layout(call.n_max, batch, std::min(k_max, call.n_max), c.sw, d_ws);
+  if (d_ws == nullptr || ws_bytes < call.l.total) {
+    ndmps::set_error("syevd_topk workspace too small: %lld < %lld", (long long)ws_bytes, (long long)call.l.total);
+    return NDMPS_EWORKSPACE;
+  }
+  NDMPS_TRY(trd_device_slots(c.slots));
+  call.r = trd_route(c, call.l);
+  return NDMPS_OK;
+}
+}  // namespace
+
 // phase marks of the inverse-iteration kernel of matrix b (16 x int64, 100 MHz): profiling aid
 extern "C" int64_t ndmps_syevd_topk_stamps_offset(int64_t n_max, int batch, int64_t k_max) {
   if (n_max <= 0 || n_max > kMaxN || batch <= 0 || k_max <= 0 || k_max > kMaxN) return -1;
-  return trd_layout(n_max, batch, std::min(k_max, n_max)).off_stamps;
+  return trd_layout(n_max, batch, std::min(k_max, n_max), trd_switches()).off_stamps;
 }
 extern "C" int64_t ndmps_syevd_topk_max_n(void) { return kMaxN; }
 extern "C" int64_t ndmps_syevd_topk_max_k(void) { return kMaxK; }
@@ -2988,7 +3148,37 @@ extern "C" int64_t ndmps_syevd_topk_max_k_wide(void) { return kMaxN; }
 
 extern "C" int64_t ndmps_syevd_topk_workspace_bytes(int64_t n_max, int batch, int64_t k_max) {
   if (n_max <= 0 || n_max > kMaxN || batch <= 0 || k_max <= 0 || k_max > kMaxN) return 0;
-  return trd_layout(n_max, batch, std::min(k_max, n_max)).total;
+  return trd_layout(n_max, batch, std::min(k_max, n_max), trd_switches()).total;
+}
+
+// The plan of a solve of `batch` matrices of the orders h_n with k_max eigenpairs, answered from trd_route itself
+// (ndmps_hip.h names the NDMPS_EIG_ROUTE_SLOTS values).  team_enabled / streamed: the thread's settings, -1: as they are
+// now.  h_slots: resident workgroups of the team kernels with 2, 4 and 8 rows per thread; NULL asks the device.  With
+// h_slots given the call touches no GPU.
+extern "C" int ndmps_syevd_topk_route_query(int batch, const int64_t* h_n, int64_t k_max, int team_enabled, int streamed,
+                                            const int* h_slots, int64_t* h_out) {
+  TrdCase c;
+  NDMPS_TRY(trd_check_sizes(batch, h_n, c.n_max));
+  NDMPS_REQUIRE(h_out && k_max >= 1 && k_max <= kMaxN, "NULL output or k_max=%lld outside [1, %d]", (long long)k_max, kMaxN);
+  c.batch = batch, c.h_n = h_n, c.kk = (int)std::min(k_max, c.n_max);
+  c.sw = trd_switches();
+  c.team_off = team_enabled < 0 ? g_team_off != 0 : team_enabled == 0;
+  c.streamed = streamed < 0 ? g_team_streamed != 0 : streamed != 0;
+  if (h_slots) std::copy(h_slots, h_slots + 3, c.slots);
+  else NDMPS_TRY(trd_device_slots(c.slots));
+  NDMPS_REQUIRE(c.slots[0] > 0 && c.slots[1] > 0 && c.slots[2] > 0, "resident slots must be positive");
+  const TrdLayout l = trd_layout(c.n_max, batch, c.kk, c.sw);
+  const TrdRoute r = trd_route(c, l);
+  const int* lanes = kBackLanes[r.back_class];
+  const bool lane_back = r.back == TrdBack::Lanes;
+  const int64_t out[NDMPS_EIG_ROUTE_SLOTS] = {
+      (int64_t)r.reduce, r.handover, (int64_t)r.team.kernel, r.team.order, r.team.team_size, r.team.per_launch,
+      r.team.lds_bytes, r.team.xcd_placed, r.team.xcd_pair, r.team.half_turn, r.col_width, r.col_rows, r.col_launches,
+      r.tail_cols, r.tail_lower, (int64_t)r.tail, r.panel_graph, r.invit_cb, r.invit_dbg, (int64_t)r.ortho, (int64_t)r.back,
+      lane_back ? lanes[0] : 0, lane_back ? lanes[1] : 0, lane_back ? lanes[2] : 0, lane_back ? lanes[3] : 0,
+      lane_back ? 0 : r.side_stream ? 2 : 1, l.total, l.off_stamps, l.off_desc, l.off_desc2, l.kw, l.wpart_stride};
+  std::copy(out, out + NDMPS_EIG_ROUTE_SLOTS, h_out);
+  return NDMPS_OK;
 }
 
 // Phase 1: tridiagonalise and deliver the min(k_max, n) largest eigenvalues (descending) in d_w, zeros behind
@@ -2996,22 +3186,13 @@ extern "C" int64_t ndmps_syevd_topk_workspace_bytes(int64_t n_max, int batch, in
 extern "C" int ndmps_syevd_topk_values_f64(int batch, const double* d_G, int64_t stride_G, const int64_t* h_n,
                                            double* d_V, int64_t stride_V, double* d_w, int64_t stride_w,
                                            int64_t k_max, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
-  int64_t n_max = 0;
-  NDMPS_TRY(trd_check_sizes(batch, h_n, n_max));
   NDMPS_REQUIRE(d_G && d_V && d_w, "NULL eigen operand");
-  NDMPS_REQUIRE(k_max >= 1 && k_max <= kMaxN, "k_max=%lld outside [1, %d]", (long long)k_max, kMaxN);
+  TrdCall call;
+  NDMPS_TRY(trd_prepare(batch, h_n, nullptr, k_max, kMaxN, g_team_off != 0, d_ws, ws_bytes, call));
   for (int b = 0; b < batch; ++b)
     NDMPS_REQUIRE(stride_G >= h_n[b] * h_n[b] && stride_V >= h_n[b] * h_n[b] && stride_w >= h_n[b],
                   "batch stride smaller than a matrix");
-  const TrdLayout l = trd_layout(n_max, batch, std::min(k_max, n_max));
-  if (d_ws == nullptr || ws_bytes < l.total) {
-    ndmps::set_error("syevd_topk workspace too small: %lld < %lld", (long long)ws_bytes, (long long)l.total);
-    return NDMPS_EWORKSPACE;
-  }
-  NDMPS_TRY(trd_opt_in());
   hipStream_t s = (hipStream_t)stream;
-  TrdWork w = trd_work(l, d_ws);
-  TrdDesc* desc = (TrdDesc*)((char*)d_ws + l.off_desc);
   for (int base = 0; base < batch; base += kDescChunk) {
     DescChunk chunk;
     const int count = std::min(kDescChunk, batch - base);
@@ -3025,9 +3206,9 @@ extern "C" int ndmps_syevd_topk_values_f64(int batch, const double* d_G, int64_t
       chunk.v[t].status = 0;
       chunk.v[t].pad = 0;
     }
-    hipLaunchKernelGGL(trd_setdesc_kernel, dim3(1), dim3(kDescChunk), 0, s, desc, chunk, base, count, w.sync);
+    hipLaunchKernelGGL(trd_setdesc_kernel, dim3(1), dim3(kDescChunk), 0, s, call.l.desc, chunk, base, count, call.l.w.sync);
   }
-  return trd_reduce_and_values(batch, h_n, n_max, k_max, l, w, desc, s);
+  return trd_reduce_and_values(batch, h_n, call.n_max, k_max, call.l, call.r, s);
 }
 
 namespace {
@@ -3050,7 +3231,6 @@ int side_stream(hipStream_t& out) {
   return NDMPS_OK;
 }
 int side_fork(hipStream_t s, SideFork& f) {
-  if (getenv("NDMPS_NO_SIDE_STREAM")) return NDMPS_OK;  // f.side stays null: the caller launches on `s`
   hipStream_t side = nullptr;
   NDMPS_TRY(side_stream(side));
   hipEvent_t here = nullptr;
@@ -3071,125 +3251,105 @@ int side_join(hipStream_t s, SideFork& f) {
   return NDMPS_OK;
 }
 
-// Width of the column blocks of the inverse iteration.  The recurrences of a column are a dependent chain over the rows
-// whatever the width; what a block's ONE CU adds is the traffic of its helpers -- three operand arrays in, one out per sweep
-// and column, 8.4 MB per sweep at order 2048 with 128 columns, at the 30 - 60 GB/s a single CU gets.  From order 1024 on the
-// columns go to as many CUs as the launch leaves free (blocks of 16 at least); lockstep groups of order <= 512 keep one
-// block per matrix (their CUs are wanted by the other group's kernels).  NDMPS_INVIT_CB=16|32|64|128 forces a width.
-int invit_block_width(int batch, int64_t n_max, int kp) {
-  static const int forced = [] {
-    const char* e = getenv("NDMPS_INVIT_CB");
-    const int v = e ? atoi(e) : 0;
-    return (v == 16 || v == 32 || v == 64 || v == 128) ? v : 0;
-  }();
-  if (forced) return forced;
-  if (n_max < 1024) return kMaxK;
-  int cb = kMaxK;
-  while (cb > 16 && (int64_t)batch * ndmps::ceil_div(kp, cb / 2) <= 256) cb /= 2;
-  return cb;
-}
-
-// inverse iteration + back-transformation for ranks already stored in the descriptors; kk: largest rank any
-// matrix may have (sizes the launches), k_fill: columns zero-filled beyond a matrix's rank
-int trd_launch_vectors(int batch, int64_t n_max, int kk, int k_fill, TrdDesc* desc, const TrdWork& w, hipStream_t s,
-                       const TrdLayout* wide_layout = nullptr, void* d_ws = nullptr, const int64_t* h_n = nullptr,
-                       const int64_t* h_k = nullptr) {
+// Phase 2 as planned by `r`: inverse iteration + back-transformation for ranks already stored in the descriptors; kk:
+// largest rank any matrix may have (sizes the launches), k_fill: columns zero-filled beyond a matrix's rank; h_k: the
+// ranks on the host (NULL: decided on the device, at most kMaxK)
+int trd_launch_vectors(int batch, const int64_t* h_n, const int64_t* h_k, int64_t n_max, int kk, int k_fill, const TrdLayout& l,
+                       const TrdRoute& r, hipStream_t s) {
+  const TrdWork& w = l.w;
+  TrdDesc* desc = l.desc;
   const unsigned B = (unsigned)batch;
   const int k16 = (kk + 15) & ~15;
+  const int cols = std::max(kk, k_fill);
   void* vec_span = ndmps::span_begin(s);
   // the T factors of a blocked back-transformation need the reflectors only: on the side stream, beside everything up to
   // the orthonormalisation
-  const bool blocked_back = wide_layout && d_ws && wide_layout->kw > 0 && !getenv("NDMPS_BACK_NARROW") &&
-                            (w.kp > kMaxK || (h_n && wide_layout->wpart_stride > 0 && !getenv("NDMPS_ORTHO_NARROW")));
-  SideFork fork;
-  if (blocked_back) {
-    NDMPS_TRY(side_fork(s, fork));
+  SideFork fork;  // fork.side stays null without a side stream: everything on `s`
+  if (r.back != TrdBack::Lanes) {
+    if (r.side_stream) NDMPS_TRY(side_fork(s, fork));
     hipLaunchKernelGGL(back_wide_t_kernel, dim3((unsigned)ndmps::ceil_div(std::max<int64_t>(n_max - 1, 1), kBwB), B), dim3(256), 0,
-                       fork.side ? fork.side : s, (const TrdDesc*)desc, w, (double*)((char*)d_ws + wide_layout->off_wt),
-                       wide_layout->wt_stride);
+                       fork.side ? fork.side : s, (const TrdDesc*)desc, w, l.wt, l.wt_stride);
   }
   hipLaunchKernelGGL(trd_shift_kernel, dim3((unsigned)ndmps::ceil_div(batch, 64)), dim3(64), 0, s, desc, w, batch);
-  // inverse iteration in column blocks (invit_block_width: one block of up to 128 vectors per matrix of a lockstep group,
-  // narrow blocks on their own CUs for one or a few big matrices)
-  const int cb = invit_block_width(batch, n_max, w.kp);
-  const int kb = std::min<int>(w.kp, cb);
+  // inverse iteration in column blocks (one block of up to 128 vectors per matrix of a lockstep group, narrow blocks on
+  // their own CUs for one or a few big matrices)
+  const int cb = r.invit_cb, kb = std::min<int>(w.kp, cb);
   hipLaunchKernelGGL(trd_invit_kernel, dim3((unsigned)ndmps::ceil_div(w.kp, cb), B), dim3(512),
                      std::max((size_t)n_max * 16, (size_t)2 * 4 * invit_rows_per_block(kb) * kb * 8), s, desc, w,
-                     cb | ((getenv("NDMPS_INVIT_DBG") ? atoi(getenv("NDMPS_INVIT_DBG")) : 0) << 16));
-  const bool wide_small = w.kp <= kMaxK && wide_layout && d_ws && h_n && wide_layout->kw > 0 && !getenv("NDMPS_ORTHO_NARROW");
-  if (wide_small) {
-    // one or two big matrices: Cholesky-QR across the chip with the rank read on the device (eig_wide.inc)
-    char* base = (char*)d_ws;
-    for (int b = 0; b < batch; ++b)
-      NDMPS_TRY(wide_orthonormalise_auto(desc + b, w.Z + (int64_t)b * w.n_max * w.kp, (int)h_n[b], w.kp,
-                                         (double*)(base + wide_layout->off_ws), (double*)(base + wide_layout->off_wlinv),
-                                         (int)wide_layout->kw, base + wide_layout->off_wgram, wide_layout->wgram_bytes, s));
-  } else if (w.kp > kMaxK) {
-    // more than 128 vectors may be wanted: Cholesky-QR across the chip, matrix by matrix (eig_wide.inc)
-    NDMPS_REQUIRE(wide_layout && d_ws && h_n && h_k && wide_layout->kw > 0, "wide eigenvector block without its workspace");
-    char* base = (char*)d_ws;
-    for (int b = 0; b < batch; ++b)
-      NDMPS_TRY(wide_orthonormalise(desc + b, w.Z + (int64_t)b * w.n_max * w.kp, (int)h_n[b], (int)h_k[b], w.kp,
-                                    (double*)(base + wide_layout->off_ws), (double*)(base + wide_layout->off_wlinv),
-                                    (int)wide_layout->kw, base + wide_layout->off_wgram, wide_layout->wgram_bytes, s));
-  } else if (k16 <= 64)
-    hipLaunchKernelGGL(trd_ortho_kernel<true>, dim3(1, B), dim3(512), (size_t)2 * k16 * (k16 + 1) * 8, s, desc, w);
-  else if (!getenv("NDMPS_ORTHO_COLUMNS"))  // k > 64: column blocks of 64 (block Gram-Schmidt + blocked Cholesky-QR)
-    hipLaunchKernelGGL(trd_ortho_blocks_kernel, dim3(1, B), dim3(512), (size_t)3 * 64 * 65 * 8, s, desc, w);
-  else
-    hipLaunchKernelGGL(trd_ortho_kernel<false>, dim3(1, B), dim3(512), (size_t)k16 * (k16 + 1) * 8, s, desc, w);
-  if (wide_small && wide_layout->wpart_stride > 0 && !getenv("NDMPS_BACK_NARROW")) {
-    // one or two big matrices, at most 128 columns: rows dealt to the chip, one launch per block of 64 reflectors
-    double* Tw = (double*)((char*)d_ws + wide_layout->off_wt);
-    double* part = (double*)((char*)d_ws + wide_layout->off_wpart);
-    const int G = n_max >= 2 ? (int)((n_max - 2) / kBwB + 1) : 0;
-    const int chunks = (int)ndmps::ceil_div(n_max, kBrR);
-    const int cols = std::max(kk, k_fill);
-    NDMPS_TRY(side_join(s, fork));
-    hipLaunchKernelGGL(back_rows_init_kernel, dim3(256, B), dim3(256), 0, s, (const TrdDesc*)desc, w, k_fill);
-    const dim3 grid((unsigned)chunks, (unsigned)ndmps::ceil_div(cols, kBrC), B);
-    for (int g = G; g >= 0; --g)  // launch g: apply block g (none at first), form block g - 1 (none at last)
-      hipLaunchKernelGGL(back_rows_step_kernel, grid, dim3(256), 0, s, (const TrdDesc*)desc, w, (const double*)Tw,
-                         wide_layout->wt_stride, part, wide_layout->wpart_stride, chunks, g < G ? g : -1, g - 1);
-    hipLaunchKernelGGL(back_rows_sign_kernel, dim3((unsigned)ndmps::ceil_div(cols, 16), B), dim3(1024), 0, s, (const TrdDesc*)desc);
-    ndmps::span_end(vec_span, s, ndmps::kSpanEigenVectors, G + 8, 0);
-    NDMPS_LAUNCH_CHECK();
-    return NDMPS_OK;
+                     cb | (r.invit_dbg << 16));
+  switch (r.ortho) {
+    case TrdOrtho::WideAuto:
+      for (int b = 0; b < batch; ++b)
+        NDMPS_TRY(wide_orthonormalise_auto(desc + b, w.Z + (int64_t)b * w.n_max * w.kp, (int)h_n[b], w.kp, l.ws, l.wlinv, (int)l.kw,
+                                           l.wgram, l.wgram_bytes, s));
+      break;
+    case TrdOrtho::Wide:
+      NDMPS_REQUIRE(h_k && l.kw > 0, "wide eigenvector block without its ranks or workspace");
+      for (int b = 0; b < batch; ++b)
+        NDMPS_TRY(wide_orthonormalise(desc + b, w.Z + (int64_t)b * w.n_max * w.kp, (int)h_n[b], (int)h_k[b], w.kp, l.ws, l.wlinv,
+                                      (int)l.kw, l.wgram, l.wgram_bytes, s));
+      break;
+    case TrdOrtho::Small:
+      hipLaunchKernelGGL(trd_ortho_kernel<true>, dim3(1, B), dim3(512), (size_t)2 * k16 * (k16 + 1) * 8, s, desc, w);
+      break;
+    case TrdOrtho::Blocks:
+      hipLaunchKernelGGL(trd_ortho_blocks_kernel, dim3(1, B), dim3(512), (size_t)3 * 64 * 65 * 8, s, desc, w);
+      break;
+    case TrdOrtho::Columns:
+      hipLaunchKernelGGL(trd_ortho_kernel<false>, dim3(1, B), dim3(512), (size_t)k16 * (k16 + 1) * 8, s, desc, w);
+      break;
   }
-  if (w.kp > kMaxK && !getenv("NDMPS_BACK_NARROW")) {
-    // many columns: the reflectors in blocks of 64 on the MFMA, one workgroup per 16 columns (eig_wide.inc)
-    double* Tw = (double*)((char*)d_ws + wide_layout->off_wt);
-    NDMPS_TRY(side_join(s, fork));
-    hipLaunchKernelGGL(back_wide_kernel, dim3((unsigned)ndmps::ceil_div(kk, kBwC), B), dim3(64 * kBwWaves), 0, s, (const TrdDesc*)desc, w,
-                       (const double*)Tw, wide_layout->wt_stride);
-    ndmps::span_end(vec_span, s, ndmps::kSpanEigenVectors, 4, 0);
-    NDMPS_LAUNCH_CHECK();
-    return NDMPS_OK;
+  int64_t span_launches = 4;
+  switch (r.back) {
+    case TrdBack::Rows: {
+      const int G = n_max >= 2 ? (int)((n_max - 2) / kBwB + 1) : 0;
+      const int chunks = (int)ndmps::ceil_div(n_max, kBrR);
+      NDMPS_TRY(side_join(s, fork));
+      hipLaunchKernelGGL(back_rows_init_kernel, dim3(256, B), dim3(256), 0, s, (const TrdDesc*)desc, w, k_fill);
+      const dim3 grid((unsigned)chunks, (unsigned)ndmps::ceil_div(cols, kBrC), B);
+      for (int g = G; g >= 0; --g)  // launch g: apply block g (none at first), form block g - 1 (none at last)
+        hipLaunchKernelGGL(back_rows_step_kernel, grid, dim3(256), 0, s, (const TrdDesc*)desc, w, (const double*)l.wt, l.wt_stride,
+                           l.wpart, l.wpart_stride, chunks, g < G ? g : -1, g - 1);
+      hipLaunchKernelGGL(back_rows_sign_kernel, dim3((unsigned)ndmps::ceil_div(cols, 16), B), dim3(1024), 0, s, (const TrdDesc*)desc);
+      span_launches = G + 8;
+      break;
+    }
+    case TrdBack::Wide:
+      NDMPS_TRY(side_join(s, fork));
+      hipLaunchKernelGGL(back_wide_kernel, dim3((unsigned)ndmps::ceil_div(kk, kBwC), B), dim3(64 * kBwWaves), 0, s, (const TrdDesc*)desc, w,
+                         (const double*)l.wt, l.wt_stride);
+      break;
+    case TrdBack::Lanes: {
+      // the reduction phase 1 actually took on this workspace, whatever the thread's settings say by now
+      const int bw = route_load(w.A, r.band);
+      if (bw) {  // eigenvectors of T -> eigenvectors of the band matrix: the bulge chase's reflectors, sweeps in reverse
+        const dim3 grid((unsigned)ndmps::ceil_div(std::min<int64_t>(k16, w.kp), 32), B);
+        if (bw == 2) hipLaunchKernelGGL(trd_back2_kernel<2>, grid, dim3(1024), (size_t)n_max * 32 * 8, s, desc, w, kk);
+        else hipLaunchKernelGGL(trd_back2_kernel<4>, grid, dim3(1024), (size_t)n_max * 32 * 8, s, desc, w, kk);
+      }
+#define NDMPS_BACK(CLASS, SEG, R, RB, WYB)                                                                        \
+  case CLASS: {                                                                                                   \
+    static_assert(kBackLanes[CLASS][0] == SEG && kBackLanes[CLASS][1] == R && kBackLanes[CLASS][2] == RB &&       \
+                  kBackLanes[CLASS][3] == WYB, "kBackLanes is what the route reports");                           \
+    const int groups = (int)ndmps::ceil_div(std::max<int64_t>(n_max - 1, 1), WYB);                                 \
+    hipLaunchKernelGGL((trd_wy_kernel<WYB>), dim3(groups, B), dim3(64), 0, s, desc, w, w.Tw, w.t_stride);          \
+    hipLaunchKernelGGL((trd_back_kernel<SEG, R, RB, WYB>), dim3(ndmps::ceil_div(cols, 256 / SEG), B), dim3(256),   \
+                       (size_t)2 * RB * SEG * R * sizeof(double), s, desc, w, k_fill, w.Tw, w.t_stride);          \
+    break;                                                                                                        \
   }
-  const int bw = route_load(w.A, band_width_for(n_max));
-  if (bw) {  // eigenvectors of T -> eigenvectors of the band matrix: the bulge chase's reflectors, sweeps in reverse
-    const dim3 grid((unsigned)ndmps::ceil_div(std::min<int64_t>(k16, w.kp), 32), B);
-    if (bw == 2) hipLaunchKernelGGL(trd_back2_kernel<2>, grid, dim3(1024), (size_t)n_max * 32 * 8, s, desc, w, kk);
-    else hipLaunchKernelGGL(trd_back2_kernel<4>, grid, dim3(1024), (size_t)n_max * 32 * 8, s, desc, w, kk);
-  }
-  const int cols = std::max(kk, k_fill);
-  // rows per lane of the back-transform: n <= SEG * R; RB reflectors of SEG * R doubles per LDS block
-  const int per32 = (int)ndmps::ceil_div(n_max, 32), per64 = (int)ndmps::ceil_div(n_max, 64);
-#define NDMPS_BACK(SEG, R, RB, WYB)                                                                            \
-  do {                                                                                                          \
-    const int groups = (int)ndmps::ceil_div(std::max<int64_t>(n_max - 1, 1), WYB);                               \
-    hipLaunchKernelGGL((trd_wy_kernel<WYB>), dim3(groups, B), dim3(64), 0, s, desc, w, w.Tw, w.t_stride);         \
-    hipLaunchKernelGGL((trd_back_kernel<SEG, R, RB, WYB>), dim3(ndmps::ceil_div(cols, 256 / SEG), B), dim3(256), \
-                       (size_t)2 * RB * SEG * R * sizeof(double), s, desc, w, k_fill, w.Tw, w.t_stride);         \
-  } while (0)
-  if (per32 <= 4) NDMPS_BACK(32, 4, 8, 4);
-  else if (per32 <= 8) NDMPS_BACK(32, 8, 8, 4);
-  else if (per32 <= 16) NDMPS_BACK(32, 16, 8, 4);
-  else if (per32 <= 32) NDMPS_BACK(32, 32, 4, 2);
-  else if (per64 <= 32) NDMPS_BACK(64, 32, 2, 2);
-  else NDMPS_BACK(64, 64, 1, 1);
+      switch (r.back_class) {
+        NDMPS_BACK(0, 32, 4, 8, 4)
+        NDMPS_BACK(1, 32, 8, 8, 4)
+        NDMPS_BACK(2, 32, 16, 8, 4)
+        NDMPS_BACK(3, 32, 32, 4, 2)
+        NDMPS_BACK(4, 64, 32, 2, 2)
+        NDMPS_BACK(5, 64, 64, 1, 1)
+      }
 #undef NDMPS_BACK
-  ndmps::span_end(vec_span, s, ndmps::kSpanEigenVectors, 4, 0);
+      break;
+    }
+  }
+  ndmps::span_end(vec_span, s, ndmps::kSpanEigenVectors, span_launches, 0);
   NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
@@ -3203,25 +3363,16 @@ int trd_launch_vectors(int batch, int64_t n_max, int kk, int k_fill, TrdDesc* de
 extern "C" int ndmps_syevd_topk_vectors_auto_f64(int batch, const int64_t* h_n, int64_t k_cap, double cutoff,
                                                  int* d_ranks, double* d_spectra, int64_t spectra_stride,
                                                  int* d_status, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
-  int64_t n_max = 0;
-  NDMPS_TRY(trd_check_sizes(batch, h_n, n_max));
-  NDMPS_REQUIRE(d_ranks, "NULL rank output");
-  NDMPS_REQUIRE(k_cap >= 1 && k_cap <= kMaxK && cutoff >= 0.0, "k_cap=%lld outside [1, %d] or negative cutoff",
-                (long long)k_cap, kMaxK);
-  const TrdLayout l = trd_layout(n_max, batch, std::min(k_cap, n_max));
-  if (d_ws == nullptr || ws_bytes < l.total) {
-    ndmps::set_error("syevd_topk workspace too small: %lld < %lld", (long long)ws_bytes, (long long)l.total);
-    return NDMPS_EWORKSPACE;
-  }
+  NDMPS_REQUIRE(d_ranks && cutoff >= 0.0, "NULL rank output or negative cutoff");
+  TrdCall call;
+  NDMPS_TRY(trd_prepare(batch, h_n, nullptr, k_cap, kMaxK, g_team_off != 0, d_ws, ws_bytes, call));
   hipStream_t s = (hipStream_t)stream;
-  TrdWork w = trd_work(l, d_ws);
-  TrdDesc* desc = (TrdDesc*)((char*)d_ws + l.off_desc);
-  const int kk = (int)std::min(k_cap, n_max);
-  hipLaunchKernelGGL(trd_rank_kernel, dim3(batch), dim3(128), 0, s, desc, kk, cutoff, d_ranks, d_spectra, spectra_stride);
+  const int kk = (int)std::min(k_cap, call.n_max);
+  hipLaunchKernelGGL(trd_rank_kernel, dim3(batch), dim3(128), 0, s, call.l.desc, kk, cutoff, d_ranks, d_spectra, spectra_stride);
   NDMPS_LAUNCH_CHECK();
-  NDMPS_TRY(trd_launch_vectors(batch, n_max, kk, kk, desc, w, s, &l, d_ws, h_n));
+  NDMPS_TRY(trd_launch_vectors(batch, h_n, nullptr, call.n_max, kk, kk, call.l, call.r, s));
   if (d_status) {
-    hipLaunchKernelGGL(trd_status_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch, d_status);
+    hipLaunchKernelGGL(trd_status_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, call.l.desc, batch, d_status);
     NDMPS_LAUNCH_CHECK();
   }
   return NDMPS_OK;
@@ -3232,21 +3383,14 @@ extern "C" int ndmps_syevd_topk_vectors_auto_f64(int batch, const int64_t* h_n, 
 // synchronises, i.e. when h_status is given.
 extern "C" int ndmps_syevd_topk_vectors_f64(int batch, const int64_t* h_n, const int64_t* h_k, int64_t k_max,
                                             void* d_ws, int64_t ws_bytes, int* h_status, ndmps_stream_t stream) {
-  int64_t n_max = 0;
-  NDMPS_TRY(trd_check_sizes(batch, h_n, n_max));
   NDMPS_REQUIRE(h_k, "NULL rank array");
-  NDMPS_REQUIRE(k_max >= 1 && k_max <= kMaxN, "k_max=%lld outside [1, %d]", (long long)k_max, kMaxN);
-  const TrdLayout l = trd_layout(n_max, batch, std::min(k_max, n_max));
-  if (d_ws == nullptr || ws_bytes < l.total) {
-    ndmps::set_error("syevd_topk workspace too small: %lld < %lld", (long long)ws_bytes, (long long)l.total);
-    return NDMPS_EWORKSPACE;
-  }
+  TrdCall call;
+  NDMPS_TRY(trd_prepare(batch, h_n, h_k, k_max, kMaxN, g_team_off != 0, d_ws, ws_bytes, call));
   hipStream_t s = (hipStream_t)stream;
-  TrdWork w = trd_work(l, d_ws);
-  TrdDesc* desc = (TrdDesc*)((char*)d_ws + l.off_desc);
+  TrdDesc* desc = call.l.desc;
   int kk = 1;
   for (int b = 0; b < batch; ++b) {
-    NDMPS_REQUIRE(h_k[b] >= 1 && h_k[b] <= h_n[b] && h_k[b] <= std::min(k_max, n_max), "k[%d]=%lld out of range", b,
+    NDMPS_REQUIRE(h_k[b] >= 1 && h_k[b] <= h_n[b] && h_k[b] <= std::min(k_max, call.n_max), "k[%d]=%lld out of range", b,
                   (long long)h_k[b]);
     kk = std::max(kk, (int)h_k[b]);
   }
@@ -3256,7 +3400,7 @@ extern "C" int ndmps_syevd_topk_vectors_f64(int batch, const int64_t* h_n, const
     for (int t = 0; t < count; ++t) chunk.v[t] = (int)h_k[base + t];
     hipLaunchKernelGGL(trd_setk_kernel, dim3(1), dim3(256), 0, s, desc, chunk, base, count);
   }
-  NDMPS_TRY(trd_launch_vectors(batch, n_max, kk, 0, desc, w, s, &l, d_ws, h_n, h_k));
+  NDMPS_TRY(trd_launch_vectors(batch, h_n, h_k, call.n_max, kk, 0, call.l, call.r, s));
   if (h_status) {
     std::vector<TrdDesc> host(batch);
     NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), desc, sizeof(TrdDesc) * batch, hipMemcpyDeviceToHost, s));
@@ -3277,17 +3421,10 @@ extern "C" int ndmps_syevd_topk_vectors_f64(int batch, const int64_t* h_n, const
 // d_status at the end and repeat their sequence after ndmps_syevd_topk_set_team(0) (the sweep does: tt.hip).
 extern "C" int ndmps_syevd_topk_recover_f64(int batch, const int64_t* h_n, int64_t k_max, void* d_ws, int64_t ws_bytes,
                                             int* h_recovered, ndmps_stream_t stream) {
-  int64_t n_max = 0;
-  NDMPS_TRY(trd_check_sizes(batch, h_n, n_max));
-  NDMPS_REQUIRE(k_max >= 1 && k_max <= kMaxN, "k_max=%lld outside [1, %d]", (long long)k_max, kMaxN);
-  const TrdLayout l = trd_layout(n_max, batch, std::min(k_max, n_max));
-  if (d_ws == nullptr || ws_bytes < l.total) {
-    ndmps::set_error("syevd_topk workspace too small: %lld < %lld", (long long)ws_bytes, (long long)l.total);
-    return NDMPS_EWORKSPACE;
-  }
+  TrdCall call;  // planned with the resident launches off: what the redone phase 1 takes
+  NDMPS_TRY(trd_prepare(batch, h_n, nullptr, k_max, kMaxN, true, d_ws, ws_bytes, call));
   hipStream_t s = (hipStream_t)stream;
-  TrdWork w = trd_work(l, d_ws);
-  TrdDesc* desc = (TrdDesc*)((char*)d_ws + l.off_desc);
+  TrdDesc* desc = call.l.desc;
   std::vector<TrdDesc> host(batch);
   NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), desc, sizeof(TrdDesc) * batch, hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
@@ -3296,11 +3433,8 @@ extern "C" int ndmps_syevd_topk_recover_f64(int batch, const int64_t* h_n, int64
   if (h_recovered) *h_recovered = aborted ? 1 : 0;
   if (!aborted) return NDMPS_OK;
   g_team_fallbacks.fetch_add(1);
-  hipLaunchKernelGGL(trd_clear_status_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch, w.sync);
-  g_team_off += 1;
-  const int rc = trd_reduce_and_values(batch, h_n, n_max, k_max, l, w, desc, s);
-  g_team_off -= 1;
-  return rc;
+  hipLaunchKernelGGL(trd_clear_status_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, desc, batch, call.l.w.sync);
+  return trd_reduce_and_values(batch, h_n, call.n_max, k_max, call.l, call.r, s);
 }
 // Per host thread: 0 switches the resident launch off (column launches for every order), 1 back on; returns the
 // previous setting.  NDMPS_TRD_NO_TEAM=1 in the environment does the same for the whole process.
@@ -3320,16 +3454,13 @@ extern "C" int ndmps_syevd_topk_set_streamed(int streamed) {
 // number of times a resident launch was given up and its work redone on the column launches (whole process)
 extern "C" int64_t ndmps_syevd_topk_team_fallbacks(void) { return g_team_fallbacks.load(); }
 extern "C" int ndmps_syevd_topk_team_slots(int64_t order) {
-  int slots = 0;
-  if (trd_opt_in() != NDMPS_OK || team_slots(slots, order <= 512 ? 2 : order <= 1024 ? 4 : 8) != NDMPS_OK) return 0;
-  return slots;
+  int slots[3] = {};
+  return trd_device_slots(slots) == NDMPS_OK ? slots[slot_class(order)] : 0;
 }
 extern "C" int ndmps_syevd_topk_note_team_fallback(void) {  // for callers that redo their own sequence
   g_team_fallbacks.fetch_add(1);
   return NDMPS_OK;
 }
-// Test hook: the next `launches` resident launches are replaced by what an aborted one leaves behind (status 2 in
-// every descriptor, the reduction not done), without the 3 s wait.
 namespace {
 __global__ void lane_sums_kernel(const double* __restrict__ in, double* __restrict__ out) {
   const int l = threadIdx.x;
@@ -3359,6 +3490,8 @@ extern "C" int ndmps_debug_lane_sums_f64(const double* d_in, double* d_out, void
   return NDMPS_OK;
 }
 
+// Test hook: the next `launches` resident launches are replaced by what an aborted one leaves behind (status 2 in
+// every descriptor, the reduction not done), without the 3 s wait.
 extern "C" int ndmps_debug_inject_team_abort(int launches) {
   g_inject_abort.store(launches > 0 ? launches : 0);
   return NDMPS_OK;

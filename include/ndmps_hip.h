@@ -317,6 +317,33 @@ int ndmps_syevd_topk_set_streamed(int streamed);
 int64_t ndmps_syevd_topk_team_fallbacks(void);
 int ndmps_syevd_topk_team_slots(int64_t order);
 int ndmps_syevd_topk_note_team_fallback(void);
+/* The launches a solve of `batch` matrices of the orders h_n with k_max eigenpairs would make, for tests, tools and
+ * callers that must know which kernel ran: answered from the solver's own planning function (trd_route), host arithmetic
+ * only, no effect on any launch.  The NDMPS_TRD_* / NDMPS_ORTHO_* / NDMPS_BACK_* switches are read as a call would read
+ * them.  team_enabled, streamed: the settings of _set_team / _set_streamed to plan for, -1 = the calling thread's current
+ * ones (a recovery plans with team_enabled = 0).  h_slots[3]: the _team_slots of orders 512, 1024 and 2048; NULL asks the
+ * current device -- with h_slots given the call makes no GPU call.  Phase 2 is planned for ranks up to min(k_max, n).
+ * h_out receives NDMPS_EIG_ROUTE_SLOTS values (fields of routes the plan does not take are 0):
+ *    0 reduction: 0 Columns (one launch per column), 1 Band2, 2 Band4 (two-stage), 3 Team (resident, orders <= 512),
+ *      4 BigTeam (resident, orders 513 .. 2048), 5 Panel, 6 PanelHybrid (panels, then the resident kernel)
+ *    1 hand-over width of PanelHybrid (2048, 1024 or 512 last columns)
+ *    2 resident kernel: 0 none, 1 8-column tagged blocks with 2 rows per thread, 2 32-column blocks meeting at a counter,
+ *      3 half storage, 4 / 5 8-column tagged blocks with 4 / 8 rows per thread, 6 / 7 dense -> band of width 2 / 4
+ *    3 order the resident kernel reduces   4 workgroups per team   5 matrices per launch   6 dynamic LDS bytes
+ *    7 placed XCD by XCD   8 paired on the CUs   9 takes half the device-side turn (0: the whole turn)
+ *   10 column launches: columns per block (8 / 32)   11 rows per thread   12 number of launches
+ *   13 columns the panels leave (Panel: 128)   14 the tail finds the stored half only   15 tail: 0 none (bulge chase),
+ *      1 registers, 2 LDS   16 panel launches replayed from a cached graph
+ *   17 inverse iteration: columns per block   18 its ablation bits (NDMPS_INVIT_DBG)
+ *   19 orthonormalisation: 0 chip-wide with the rank read on the device, 1 chip-wide, 2 one workgroup (<= 64 vectors),
+ *      3 one workgroup in blocks of 64, 4 one workgroup column by column
+ *   20 back-transformation: 0 rows dealt to the lanes, 1 rows dealt to the chip, 2 blocks of 64 reflectors on the MFMA
+ *   21 SEG  22 R  23 RB  24 WYB of the lane-dealt kernel   25 T factors of 1 / 2: 1 on the caller's stream, 2 on the side stream
+ *   26 workspace bytes   27 stamps offset   28 / 29 offsets of the descriptors and of the hand-over's descriptors
+ *   30 padded vector count the chip-wide buffers hold (0: none)   31 doubles per matrix of the row-dealt partials */
+#define NDMPS_EIG_ROUTE_SLOTS 32
+int ndmps_syevd_topk_route_query(int batch, const int64_t* h_n, int64_t k_max, int team_enabled, int streamed,
+                                 const int* h_slots, int64_t* h_out);
 int ndmps_debug_inject_team_abort(int launches);
 /* TEST HOOK: the cross-lane sums the tridiagonalisation kernels fold with (csrc/lanes.h: DPP moves and permlane swaps in
  * place of ds_bpermute), on one wave: d_out[12][64] = the sums of d_in[64] over 2, 4, 8, 16, 32, 64 adjacent lanes, then

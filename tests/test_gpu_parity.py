@@ -32,6 +32,8 @@ from oracle import mps as omps  # noqa: E402
 from oracle.metrics import compute_ssim_by_dim, synthetic_mri  # noqa: E402
 from oracle.ndmps_oracle import OracleNDMPS  # noqa: E402
 
+import eig_routes as er  # noqa: E402  (tests/ is on the path: rootdir conftest)
+
 DEV = "cuda:0"
 
 
@@ -839,6 +841,8 @@ def test_topk_solver_batches_beyond_the_narrow_teams():
     rng = np.random.default_rng(21)
     for n, count, k in ((260, 20, 16), (512, 9, 32)):
         assert count * -(-n // 8) > lib.ndmps_syevd_topk_team_slots(n) > 0
+        plan = er.route(lib, [n] * count, k)
+        assert (plan["reduce"], plan["kernel"], plan["team_size"]) == (er.TEAM, er.K_MEET2, -(-n // 32))
         mats = []
         for _ in range(count):
             a = rng.standard_normal((n + 16, n)) * np.logspace(0, -4, n)[None, :]
@@ -848,11 +852,14 @@ def test_topk_solver_batches_beyond_the_narrow_teams():
 
 
 def test_topk_solver_orders_above_512_in_mixed_batches():
-    """Orders above 512 (BASELINE config 5: 2048; chi = 128 on a 256^3 volume: 1024) take the column launches;
-    batches mix big and small members."""
+    """Orders above 512 (BASELINE config 5: 2048; chi = 128 on a 256^3 volume: 1024) in batches that mix big and small
+    members: four of order <= 1024 take the resident kernel whole (4 x 128 workgroups fit the slots), 2048 with 1300
+    does not (2 x 256 workgroups) and, being mixed, has no resident end either: panel launches to the last 128 columns."""
     lib = _lib.load()
     rng = np.random.default_rng(11)
-    for sizes, ks in (([1024, 600, 100, 1000], [128, 64, 10, 128]), ([2048, 1300], [128, 100])):
+    for sizes, ks, kind in (([1024, 600, 100, 1000], [128, 64, 10, 128], er.BIG_TEAM), ([2048, 1300], [128, 100], er.PANEL)):
+        plan = er.route(lib, sizes, 128)
+        assert (plan["reduce"], plan["handover"]) == (kind, 0)
         mats = []
         for n in sizes:
             a = rng.standard_normal((n + 64, n)) * np.logspace(0, -5, n)[None, :]
@@ -873,6 +880,11 @@ def test_topk_solver_panel_blocked_reduction(n, team_max, monkeypatch):
     monkeypatch.setenv("NDMPS_TRD_PANEL_MIN", "513")
     if team_max:
         monkeypatch.setenv("NDMPS_TRD_TEAM_MAX", str(team_max))
+    handover = {(640, 512): 512, (1537, 512): 0, (3000, 512): 512, (4096, 512): 512, (2500, 1024): 1024, (3000, None): 2048,
+                (4096, None): 2048}[(n, team_max)]
+    plan = er.route(lib, [n], 128)
+    assert (plan["reduce"], plan["handover"], plan["tail_cols"]) == (er.PANEL_HYBRID if handover else er.PANEL, handover,
+                                                                     handover or 128)
     rng = np.random.default_rng(n)
     a = rng.standard_normal((n + 5, n)) * np.logspace(0, -5, n)[None, :]
     g = a.T @ a
@@ -903,6 +915,7 @@ def test_topk_solver_panel_blocked_reduction_degenerate_spectra(route, monkeypat
     step = len(mats) if route == "panel" else 3
     for at in range(0, len(mats), step):
         part, kpart = mats[at:at + step], ks[at:at + step]
+        assert er.route(lib, [g.shape[0] for g in part], 50)["reduce"] == (er.PANEL if route == "panel" else er.BIG_TEAM)
         for g, k, (w, v) in zip(part, kpart, _topk(lib, part, kpart, k_max=50)):
             _check_topk(g, w, v, k, tol_scale=4.0, k_max=50)
 
@@ -920,13 +933,16 @@ def test_topk_solver_panel_path_against_the_column_launches(monkeypatch):
         a = rng.standard_normal((n + 64, n)) * np.logspace(0, -5, n)[None, :]
         mats.append(a.T @ a)
     ks = [96, 64]
+    assert er.route(lib, [1100, 777], 128)["reduce"] == er.PANEL
     first = _topk(lib, mats, ks, k_max=128)
     again = _topk(lib, mats, ks, k_max=128)
     monkeypatch.setenv("NDMPS_TRD_PANEL_GRAPH", "1")  # the same launches replayed from a graph
+    assert er.route(lib, [1100, 777], 128)["graph"] == 1
     _topk(lib, mats, ks, k_max=128)
     eager = _topk(lib, mats, ks, k_max=128)  # replayed from the cached graph if the workspace came back at the same address
     monkeypatch.delenv("NDMPS_TRD_PANEL_GRAPH")
     monkeypatch.setenv("NDMPS_TRD_NO_PANEL", "1")
+    assert er.route(lib, [1100, 777], 128)["reduce"] == er.COLUMNS
     columns = _topk(lib, mats, ks, k_max=128)
     for g, k, (w, v), (w1, v1), (w2, v2), (w3, v3) in zip(mats, ks, first, again, eager, columns):
         assert np.array_equal(w, w1) and np.array_equal(v, v1)

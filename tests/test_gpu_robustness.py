@@ -21,6 +21,8 @@ from imgcompressionmps_amd.core import batch as batch_mod  # noqa: E402
 from oracle.metrics import synthetic_mri  # noqa: E402
 from oracle.ndmps_oracle import OracleNDMPS  # noqa: E402
 
+import eig_routes as er  # noqa: E402  (tests/ is on the path: rootdir conftest)
+
 DEV = "cuda:0"
 
 
@@ -47,10 +49,13 @@ def _spd(n, seed):
 
 @pytest.mark.parametrize("n,batch", [(256, 3), (900, 2), (1600, 1)])
 def test_solver_recovers_from_an_aborted_resident_launch(lib, n, batch):
-    """values -> recover -> vectors: with status 2 injected, recover redoes phase 1 on the column launches, says so,
-    and the eigenpairs are LAPACK's.  Orders up to 2048 take the resident launch whole (4 and 8 rows per thread above
-    512) when their teams fit the chip together."""
+    """values -> recover -> vectors: with status 2 injected, recover redoes phase 1 without the resident kernel (column
+    launches; the plain panels from order 1536 on), says so, and the eigenpairs are LAPACK's.  Orders up to 2048 take
+    the resident launch whole (4 and 8 rows per thread above 512) when their teams fit the chip together."""
     k = 32
+    assert er.route(lib, [n] * batch, k)["reduce"] in er.RESIDENT
+    redone = er.route(lib, [n] * batch, k, team=0)
+    assert (redone["reduce"], redone["kernel"]) == (er.COLUMNS if n < 1536 else er.PANEL, er.K_NONE)
     g = np.stack([_spd(n, 10 + b) for b in range(batch)])
     dg = torch.from_numpy(g).to(DEV)
     v = torch.empty_like(dg)
@@ -81,8 +86,8 @@ def test_solver_recovers_from_an_aborted_resident_launch(lib, n, batch):
 
 
 def test_solver_recovers_when_the_resident_end_of_a_panel_reduction_aborts(lib, monkeypatch):
-    """Even uniform orders above 512 hand the last 512 columns of the panel-blocked reduction to the resident kernel
-    (csrc/eig_tridiag.hip, `hybrid`).  With that launch replaced by an aborted one, recover redoes phase 1 on the
+    """Even uniform orders above 512 hand the last 2048 / 1024 / 512 columns of the panel-blocked reduction to the
+    resident kernel (csrc/eig_tridiag.hip, PanelHybrid; here two of order 1280: the last 1024).  With that launch replaced by an aborted one, recover redoes phase 1 on the
     panel launches alone; with NDMPS_TRD_NO_HYBRID the panel launches go to the end by themselves.  All three give
     LAPACK's eigenpairs, the first two agree to rounding."""
     n, k, batch = 1280, 96, 2
@@ -95,6 +100,9 @@ def test_solver_recovers_when_the_resident_end_of_a_panel_reduction_aborts(lib, 
     nbytes = int(lib.ndmps_syevd_topk_workspace_bytes(n, batch, k))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
     sizes = _lib.i64_array([n] * batch)
+    first, redone = er.route(lib, [n] * batch, k), er.route(lib, [n] * batch, k, team=0)
+    assert (first["reduce"], first["handover"], first["kernel"]) == (er.PANEL_HYBRID, 1024, er.K_TAGGED4)
+    assert (redone["reduce"], redone["kernel"]) == (er.PANEL, er.K_NONE)
     before = int(lib.ndmps_syevd_topk_team_fallbacks())
     got = {}
     for label, inject, expect, env in (("hybrid", 0, 0, None), ("aborted", 1, 1, None), ("panel", 1, 0, "NDMPS_TRD_NO_HYBRID")):
@@ -204,6 +212,8 @@ def test_two_stage_reduction_gives_lapacks_eigenpairs(lib, bw, monkeypatch):
     rng = np.random.default_rng(11)
     orders = [512, 384, 200, 137]
     n_max, k = max(orders), 24
+    plan = er.route(lib, orders, k)
+    assert (plan["reduce"], plan["kernel"]) == ((er.BAND2, er.K_BAND2) if bw == "2" else (er.BAND4, er.K_BAND4))
     g = np.zeros((len(orders), n_max, n_max))
     mats = []
     for b, n in enumerate(orders):
@@ -259,6 +269,8 @@ def test_half_storage_reduction_gives_lapacks_eigenpairs(lib, monkeypatch):
     rng = np.random.default_rng(17)
     orders = [512] * 6 + [500] * 4 + [480, 449, 384, 320, 257, 200, 137, 129, 96, 33]
     n_max, k = max(orders), 24
+    plan = er.route(lib, orders, k)
+    assert (plan["reduce"], plan["kernel"], plan["tail_lower"]) == (er.TEAM, er.K_SYM, 1)
     mats = []
     for n in orders:
         x = rng.standard_normal((2 * n, n)) * np.logspace(0, -5, n)
@@ -403,3 +415,9 @@ def test_a_pending_group_redoes_itself_when_a_resident_launch_gave_up(monkeypatc
             assert all(torch.equal(x, y) for x, y in zip(a.mps.cores, b.mps.cores))
             assert torch.equal(ra, rb)
     assert len(calls) == 2  # the redone group went through the one-call sweep, not through finish again
+
+
+def test_resident_slots_are_what_the_host_route_table_assumes(lib):
+    """tests/test_eig_route_host.py pins the solver's routes with the slot counts as inputs: they are this device's."""
+    assert tuple(lib.ndmps_syevd_topk_team_slots(n) for n in (512, 1024, 2048)) == er.MI355X_TEAM_SLOTS
+    assert er.route(lib, [512] * 8, 64, 1, 0) == er.route(lib, [512] * 8, 64, 1, 0, er.MI355X_TEAM_SLOTS)
