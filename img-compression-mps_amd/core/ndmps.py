@@ -340,9 +340,16 @@ class PendingGroup:
     front of them.  ``asynchronous`` is False when the group had to be encoded synchronously after all (storage types and
     shapes whose sweep decides ranks on the host): ``result()`` then only builds the objects."""
 
-    def __init__(self, finish, asynchronous=False, redo=None, wait=None):
-        self._finish, self._redo, self._value, self._wait = finish, redo, None, wait
+    def __init__(self, finish, asynchronous=False, redo=None, wait=None, arena=None):
+        self._finish, self._redo, self._value, self._wait, self._arena = finish, redo, None, wait, arena
         self.asynchronous = bool(asynchronous)
+
+    def arena_cores(self):
+        """Before ``result()``: [volume][site] views of the group's arena in the shape the sweep wrote them -- for a sweep
+        with device-side ranks the cap shape ``(cap_i, d_i, cap_{i+1})``, zeros beyond the ranks -- in the order of the
+        swept chain; ``None`` once ``result()`` has been called or when the cores are compact.  For tests of the layout:
+        the objects of ``result()`` hold the cores cut at their ranks."""
+        return None if self._arena is None else self._arena()
 
     def __del__(self):
         # dropped without result(): the copies of ranks and spectra into this group's pinned buffers may still be in
@@ -364,7 +371,7 @@ class PendingGroup:
                     raise
                 value = self._redo()
             self._value = (value,)
-            self._finish = self._redo = self._wait = None
+            self._finish = self._redo = self._wait = self._arena = None
         return self._value[0]
 
 
@@ -560,6 +567,15 @@ class _SweptGroup:
         """Until the copies into the pinned buffers have landed (nothing to wait for after a synchronous sweep)."""
         if self.done is not None:
             self.done.synchronize()
+
+    def arena_cores(self):
+        """[volume][site] cap-shaped views of the arena behind a sweep with device-side ranks, else None."""
+        if not self.padded:
+            return None
+        self.wait()
+        caps, offs, dims = self.caps, self.offs, self.dims
+        return [[self.arena_all[b, offs[i]: offs[i] + int(caps[i]) * dims[i] * int(caps[i + 1])]
+                 .view(int(caps[i]), dims[i], int(caps[i + 1])) for i in range(self.L)] for b in range(self.batch)]
 
     def finish(self):
         """Ranks and spectra to the host (asynchronous sweep: behind its event), objects, state launch."""
@@ -914,7 +930,7 @@ class NDMPS:
             group.ws = None
             group.mark_enqueued()
         if defer:
-            return PendingGroup(group.finish, asynchronous=group.use_async, wait=group.wait)
+            return PendingGroup(group.finish, asynchronous=group.use_async, wait=group.wait, arena=group.arena_cores)
         return group.finish()
 
     # ----------------------------------------------------------------- bookkeeping

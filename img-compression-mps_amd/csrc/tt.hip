@@ -112,13 +112,18 @@ template <typename T>
 __device__ __forceinline__ void f32_to_f64_body(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
 }
-// core (k x n) <- first k columns of V (n x n fp64), transposed
+// core (k x n) <- first k columns of V (n x n fp64), transposed.  rank_r (device, may be null): the rank of the right
+// bond where the sweep decides its ranks on the device and n = d x cap_r is laid out for the cap; the columns behind
+// that rank are rows and columns of zeros in the Gram matrix, where the solver's vectors carry rounding noise: the
+// padded core gets the exact zeros it is documented to hold.
 template <typename T>
-__device__ __forceinline__ void core_from_vectors_body(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core) {
+__device__ __forceinline__ void core_from_vectors_body(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core,
+                                                       const int* __restrict__ rank_r, int64_t cap_r) {
   const int64_t total = k * n;
+  const int64_t kr = rank_r ? (int64_t)*rank_r : cap_r;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t i = e / n, c = e % n;
-    core[e] = ndmps::from_f64<T>(V[c * n + i]);
+    core[e] = ndmps::from_f64<T>(c % cap_r < kr ? V[c * n + i] : 0.0);
   }
 }
 // s <- sqrt(max(w, 0))
@@ -153,8 +158,9 @@ __global__ void __launch_bounds__(256) f32_to_f64_kernel(const T* __restrict__ x
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
-core_from_vectors_kernel(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core) {
-  core_from_vectors_body(V, n, k, core);
+core_from_vectors_kernel(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core,
+                         const int* __restrict__ rank_r, int64_t cap_r) {
+  core_from_vectors_body(V, n, k, core, rank_r, cap_r);
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -198,8 +204,10 @@ __global__ void __launch_bounds__(256) f32_to_f64_batched_kernel(BatchOps ops, i
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
-core_from_vectors_batched_kernel(const double* __restrict__ V, int64_t v_stride, int64_t n, int64_t k, BatchOps ops) {
-  core_from_vectors_body(V + (int64_t)blockIdx.y * v_stride, n, k, static_cast<T*>(ops.out[blockIdx.y]));
+core_from_vectors_batched_kernel(const double* __restrict__ V, int64_t v_stride, int64_t n, int64_t k, BatchOps ops,
+                                 const int* __restrict__ rank_r, int64_t cap_r) {
+  core_from_vectors_body(V + (int64_t)blockIdx.y * v_stride, n, k, static_cast<T*>(ops.out[blockIdx.y]),
+                         rank_r ? rank_r + blockIdx.y : nullptr, cap_r);
 }
 __global__ void __launch_bounds__(256)
 sqrt_clamp_batched_kernel(const double* __restrict__ w, int64_t stride, int64_t n, double* __restrict__ sg) {
@@ -1076,12 +1084,12 @@ struct Sweep {
         BatchOps ops;
         for (int t = 0; t < count; ++t) ops.out[t] = core(base + t, i);
         hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(kept[0] * eig_n[0]), count), dim3(256), 0, s,
-                           Vb(base), sq, eig_n[0], kept[0], ops);
+                           Vb(base), sq, eig_n[0], kept[0], ops, right_ranks(i, base), chi_r[base]);
       }
     } else {
       for (int b = 0; b < batch; ++b)
         hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(kept[b] * eig_n[b])), dim3(256), 0, s,
-                           Vb(b), eig_n[b], kept[b], core(b, i));
+                           Vb(b), eig_n[b], kept[b], core(b, i), right_ranks(i, b), chi_r[b]);
     }
     NDMPS_LAUNCH_CHECK();
     for (int b = 0; b < batch; ++b) {
@@ -1176,6 +1184,12 @@ struct Sweep {
     return NDMPS_OK;
   }
 
+  // device ranks of the bond right of site i for the volumes from `base` on, where the cores are cap-shaped and that
+  // bond exists; null otherwise (compact cores: every column of the unfolding is inside the rank)
+  const int* right_ranks(int i, int base) const {
+    return lay.device_rank && ws.d_ranks && i + 1 < L ? ws.d_ranks + (int64_t)(i + 1) * batch + base : nullptr;
+  }
+
   // core of site i and the carried matrix of site i - 1: one launch per step for a uniform group, else volume by volume
   int site_core_and_carry(int i) {
     if (uniform_small() && uniform_kept()) {
@@ -1204,7 +1218,7 @@ struct Sweep {
     }
     if (n <= m) {  // core = V_k^T, carry = A V_k
       hipLaunchKernelGGL(core_from_vectors_batched_kernel<T>, dim3(grid1d(k * n), batch), dim3(256), 0, s,
-                         ws.V, sq, n, k, cores_out);
+                         ws.V, sq, n, k, cores_out, right_ranks(i, 0), chi_r[0]);
       NDMPS_LAUNCH_CHECK();
       int rc = NDMPS_OK;
       const bool grouped = gemm_batched_T(batch, 1, m, k, n, cur.data(), pcore.data(), n, nxt.data(), s, &rc);
@@ -1232,7 +1246,7 @@ struct Sweep {
     const double* sigb = ws.sig + (int64_t)b * lay.small_max;
     if (n <= m) {  // core = V_k^T, carry = A V_k
       hipLaunchKernelGGL(core_from_vectors_kernel<T>, dim3(grid1d(k * n)), dim3(256), 0, s, Vb(b), n, k,
-                         core(b, i));
+                         core(b, i), right_ranks(i, b), chi_r[b]);
       NDMPS_LAUNCH_CHECK();
       return gemm_T(1, m, k, n, cur[b], core(b, i), n, nxt[b], ws.tws, lay.transpose_bytes, s);
     }
