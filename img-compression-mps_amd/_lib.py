@@ -103,6 +103,7 @@ SIGNATURES = {
                                     C.POINTER(vp), vp, vp, i64, vp]),
     "ndmps_chain_contract_scatter_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, vp, i64, vp]),
     "ndmps_chain_batched_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64]),
+    "ndmps_chain_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,
                                                            i64, vp, i64, vp]),
     "ndmps_gemm_batched_max": (C.c_int, []),

@@ -59,6 +59,11 @@ struct Arena {
 };
 
 constexpr int kNumCU = 256;  // MI355X
+// workgroups of 256 threads for a grid-stride loop over n elements: at most 8 per CU
+static inline int grid1d(int64_t n) {
+  const int64_t g = ceil_div(n, 256), cap = (int64_t)kNumCU * 8;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 
 // element conversions of the storage types (fp32, bf16, fp64) to and from the fp64 side of the path
 __device__ __forceinline__ double to_f64(float x) { return (double)x; }

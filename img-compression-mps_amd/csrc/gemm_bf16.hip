@@ -156,9 +156,7 @@ __global__ void __launch_bounds__(256) convert_kernel(const TI* __restrict__ x, 
     y[i] = (TO)(float)x[i];
 }
 
-inline int grid1d(int64_t n) {
-  return (int)std::min<int64_t>(std::max<int64_t>(ndmps::ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
-}
+using ndmps::grid1d;
 
 }  // namespace
 

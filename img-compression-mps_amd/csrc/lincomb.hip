@@ -152,9 +152,7 @@ __global__ void __launch_bounds__(256) zero_kernel(T* __restrict__ out, int64_t 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = T(0);
 }
 
-inline int grid1d(int64_t n) {
-  return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
-}
+using ndmps::grid1d;
 
 // Host plan: bond sums, block offsets, output bounds and the workspace carve (a null arena counts bytes).
 struct Plan {

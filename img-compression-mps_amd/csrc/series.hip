@@ -168,9 +168,7 @@ __global__ void __launch_bounds__(256) mirror_kernel(double* __restrict__ G, int
     if (r > c) G[e] = G[c * K + r];
   }
 }
-inline int grid1d(int64_t n) {
-  return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
-}
+using ndmps::grid1d;
 
 enum { kRouteResident = 0, kRouteBatched = 1, kRoutePerPair = 2 };
 

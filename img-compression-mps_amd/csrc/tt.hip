@@ -1,9 +1,7 @@
-// MPS composites: the SVD sweep, bond truncation, chain contraction and overlap.
+// MPS composites: the SVD sweep and bond truncation.
 //
 //   ndmps_tt_sweep_f32        <- quimb MatrixProductState.from_dense   (core/ndmps.py:74)
 //   ndmps_compress_bond_f32   <- quimb tensor_compress_bond            (core/ndmps.py:104-106)
-//   ndmps_chain_contract_f32  <- `mps ^ ...`                           (core/ndmps.py:140)
-//   ndmps_overlap_f32         <- `mps @ mps`                           (core/ndmps.py:76,86)
 //
 // SVD strategy (per site, unfolding A of m rows x n cols, fp32 in HBM):
 //   n <= m : G = A^T A in fp64 (exact products), G = V diag(w) V^T by Jacobi; sigma = sqrt(w);
@@ -22,6 +20,7 @@
 
 #include "common.h"
 #include "trunc.h"
+#include "typed.h"
 
 namespace {
 
@@ -48,10 +47,6 @@ inline double sweep_eig_tol(bool f64_storage = false) {
 using ndmps::Arena;
 using ndmps::ceil_div;
 using ndmps::gram_ws_bound;
-
-inline int grid1d(int64_t n) {
-  return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), (int64_t)ndmps::kNumCU * 8);
-}
 
 // ----------------------------------------------------------------------------- small kernels
 // |A v_j|^2 for the eigenvectors v_j = V[:, i0 + j], j < t, of a Gram matrix of A: the singular values behind the SMALLEST
@@ -104,14 +99,8 @@ int tail_norms(const T* A, int64_t rs, int64_t cs, int64_t rows, int64_t cols, c
   return NDMPS_OK;
 }
 
-__global__ void set_scalar_f64_kernel(double* p, double v) { *p = v; }
-
 // ---- elementwise bodies: each is shared by a per-volume kernel and by its `_batched` twin, which resolves the volume's
-//      pointers from blockIdx.y first
-template <typename T>
-__device__ __forceinline__ void f32_to_f64_body(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
-}
+//      pointers from blockIdx.y first (f32_to_f64_body and its per-volume kernel: typed.h)
 // core (k x n) <- first k columns of V (n x n fp64), transposed.  rank_r (device, may be null): the rank of the right
 // bond where the sweep decides its ranks on the device and n = d x cap_r is laid out for the cap; the columns behind
 // that rank are rows and columns of zeros in the Gram matrix, where the solver's vectors carry rounding noise: the
@@ -152,10 +141,6 @@ __device__ __forceinline__ void scale_rows_body(const double* __restrict__ M, in
   }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) f32_to_f64_kernel(const T* __restrict__ x, int64_t n, double* y) {
-  f32_to_f64_body(x, n, y);
-}
 template <typename T>
 __global__ void __launch_bounds__(256)
 core_from_vectors_kernel(const double* __restrict__ V, int64_t n, int64_t k, T* __restrict__ core,
@@ -609,48 +594,7 @@ inline int gram_batched_src(int, const __bf16* const*, int64_t, int64_t, const S
   ndmps::set_error("the fused reshape stage is fp32 only");
   return NDMPS_EINVAL;
 }
-// C (m, n) = A (m, k) op(B);  tws: scratch of the bf16 path (transposed copy of a (k, n) right operand)
-inline int gemm_T(int transB, int64_t m, int64_t n, int64_t k, const float* A, const float* B, int64_t ldb, float* C,
-                  void*, int64_t, hipStream_t s) {
-  return ndmps_sgemm(0, transB, m, n, k, A, k, B, ldb, C, n, s);
-}
-inline int gemm_T(int transB, int64_t m, int64_t n, int64_t k, const __bf16* A, const __bf16* B, int64_t ldb, __bf16* C,
-                  void* tws, int64_t tws_bytes, hipStream_t s) {
-  return ndmps_gemm_bf16(transB, m, n, k, A, k, B, ldb, C, n, tws, tws_bytes, s);
-}
-
-inline int gemm_T(int transB, int64_t m, int64_t n, int64_t k, const double* A, const double* B, int64_t ldb, double* C,
-                  void*, int64_t, hipStream_t s) {
-  return ndmps_dgemm(0, transB, m, n, k, A, k, B, ldb, C, n, s);
-}
-
-// general product with explicit leading dimensions (fp32 / fp64)
-inline int gemm_any(int tA, int tB, int64_t m, int64_t n, int64_t k, const float* A, int64_t lda, const float* B, int64_t ldb,
-                    float* C, int64_t ldc, hipStream_t s) {
-  return ndmps_sgemm(tA, tB, m, n, k, A, lda, B, ldb, C, ldc, s);
-}
-inline int gemm_any(int tA, int tB, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
-                    int64_t ldb, double* C, int64_t ldc, hipStream_t s) {
-  return ndmps_dgemm(tA, tB, m, n, k, A, lda, B, ldb, C, ldc, s);
-}
-
-// products of a whole lockstep group in one launch (fp32 / fp64 storage; bf16 storage goes volume by volume)
-inline bool gemm_batched_T(int batch, int transB, int64_t m, int64_t n, int64_t k, double* const* A, double* const* B,
-                           int64_t ldb, double* const* C, hipStream_t s, int* rc) {
-  if (batch > ndmps_gemm_batched_max()) return false;
-  *rc = ndmps_dgemm_batched(batch, 0, transB, m, n, k, (const double* const*)A, k, (const double* const*)B, ldb, C, n, s);
-  return true;
-}
-inline bool gemm_batched_T(int batch, int transB, int64_t m, int64_t n, int64_t k, float* const* A, float* const* B,
-                           int64_t ldb, float* const* C, hipStream_t s, int* rc) {
-  if (batch > ndmps_gemm_batched_max()) return false;
-  *rc = ndmps_sgemm_batched(batch, 0, transB, m, n, k, (const float* const*)A, k, (const float* const*)B, ldb, C, n, s);
-  return true;
-}
-inline bool gemm_batched_T(int, int, int64_t, int64_t, int64_t, __bf16* const*, __bf16* const*, int64_t, __bf16* const*,
-                           hipStream_t, int*) {
-  return false;
-}
+// gemm_T, gemm_any, gemm_batched_T: typed.h
 // fp32 only: Gram and projection of the merged run through the permutation tables
 inline int gram_src(const float* vol, int64_t m, int64_t n, const SweepSource& src, double* G, void* ws, int64_t wsb,
                     hipStream_t s) {
@@ -1678,467 +1622,4 @@ extern "C" int ndmps_compress_bond_f64(const double* d_t1, const double* d_t2, i
                                        double* h_s, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
   return compress_bond_impl<double>(d_t1, d_t2, chi_l, d1, chi, d2, chi_r, cutoff, max_bond, d_new1, d_new2, h_new_chi, h_s,
                                     d_ws, ws_bytes, stream);
-}
-
-// =================================================================== chain contraction
-// Left->right like quimb's structured contraction (core/ndmps.py:140), with the tail pre-contracted: the
-// sites j0 .. L-1 whose physical dims multiply to N_{j0} <= 4096 are first contracted among themselves,
-// right to left, into R (k_{j0} x N_{j0}) -- GEMMs on matrices of at most a few MB -- so the tensor itself is
-// written ONCE, by the last GEMM  Left (M_{j0} x k_{j0}) R.  The cumulative chain alone would write an
-// N-element intermediate per trailing site and read it back (2 x 64 MB per site at 256^3 for multiplications
-// by 64 x 64 and 8 x 8 matrices).  Same fp32 products, different association.
-namespace {
-constexpr int64_t kChainTailMax = 4096;
-
-struct ChainPlan {
-  int j0 = 0;            // first site of the pre-contracted tail (== L: no tail, j0 == 0 never)
-  int64_t left_elems = 0, tail_elems = 0;
-};
-
-ChainPlan chain_plan(int L, const int64_t* dims, const int64_t* bonds) {
-  ChainPlan p;
-  p.j0 = L;
-  int64_t right = 1;
-  for (int i = L - 1; i >= 1; --i) {
-    if (right * dims[i] > kChainTailMax) break;
-    right *= dims[i];
-    p.j0 = i;
-  }
-  int64_t rows = 1;
-  for (int i = 0; i < p.j0 && i < L; ++i) {
-    rows *= dims[i];
-    p.left_elems = std::max(p.left_elems, rows * bonds[i + 1]);
-  }
-  int64_t n = 1;
-  for (int i = L - 1; i >= p.j0; --i) {
-    n *= dims[i];
-    p.tail_elems = std::max(p.tail_elems, bonds[i] * n);
-  }
-  return p;
-}
-}  // namespace
-
-namespace {
-int64_t chain_workspace(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes) {
-  if (L < 1 || !h_dims || !h_bonds) return 0;
-  const ChainPlan p = chain_plan(L, h_dims, h_bonds);
-  // + room for the transposed right operand of a bf16 product (a core or a tail matrix)
-  int64_t biggest_b = p.tail_elems;
-  for (int i = 0; i < L; ++i) biggest_b = std::max(biggest_b, h_bonds[i] * h_dims[i] * h_bonds[i + 1]);
-  return (ndmps::round_up(p.left_elems, 64) + 2 * ndmps::round_up(p.tail_elems, 64)) * elem_bytes +
-         ndmps::round_up(biggest_b * 2, 256) + 1024;
-}
-}  // namespace
-extern "C" int64_t ndmps_chain_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds) {
-  return chain_workspace(L, h_dims, h_bonds, sizeof(float));
-}
-extern "C" int64_t ndmps_chain_workspace_bytes_f64(int L, const int64_t* h_dims, const int64_t* h_bonds) {
-  return chain_workspace(L, h_dims, h_bonds, sizeof(double));
-}
-
-namespace {
-struct ChainScatter {          // inverse permutation in the epilogue of the last product (fp32 only)
-  const int64_t* row_off;      // [numel / n_cols] offset of tail-block r in the C-order volume
-  const int64_t* col_off;      // [n_cols] offsets inside a block, ASCENDING (memory order)
-  const int32_t* col_perm;     // [n_cols] site-order column of the c-th smallest offset
-  int64_t n_cols;
-};
-
-__global__ void __launch_bounds__(256)
-gather_cols_kernel(const float* __restrict__ in, int64_t rows, int64_t cols, const int32_t* __restrict__ perm,
-                   float* __restrict__ out) {
-  const int64_t total = rows * cols;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
-    out[e] = in[(e / cols) * cols + perm[e % cols]];
-}
-
-inline int final_product(int64_t rows, int64_t n_tail, int64_t k, const float* left, const float* R, float* spare,
-                         float* d_out, const ChainScatter* sc, void*, int64_t, hipStream_t s) {
-  if (!sc) return ndmps_sgemm(0, 0, rows, n_tail, k, left, k, R, n_tail, d_out, n_tail, s);
-  // columns of R in memory order of the volume, then every element goes straight to its voxel
-  hipLaunchKernelGGL(gather_cols_kernel, dim3(grid1d(k * n_tail)), dim3(256), 0, s, R, k, n_tail, sc->col_perm, spare);
-  NDMPS_LAUNCH_CHECK();
-  return ndmps_sgemm_indexed(rows, n_tail, k, left, k, nullptr, nullptr, 0, spare, n_tail, d_out, 0, sc->row_off,
-                             sc->col_off, s);
-}
-inline int final_product(int64_t rows, int64_t n_tail, int64_t k, const double* left, const double* R, double*,
-                         double* d_out, const ChainScatter*, void* tws, int64_t tws_bytes, hipStream_t s) {
-  return gemm_T(0, rows, n_tail, k, left, R, n_tail, d_out, tws, tws_bytes, s);
-}
-inline int final_product(int64_t rows, int64_t n_tail, int64_t k, const __bf16* left, const __bf16* R, __bf16*,
-                         __bf16* d_out, const ChainScatter*, void* tws, int64_t tws_bytes, hipStream_t s) {
-  return gemm_T(0, rows, n_tail, k, left, R, n_tail, d_out, tws, tws_bytes, s);
-}
-
-template <typename T>
-int chain_impl(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* const* h_cores, T* d_dense, void* d_ws,
-               int64_t ws_bytes, ndmps_stream_t stream, const ChainScatter* scatter = nullptr) {
-  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds && h_cores && d_dense, "bad chain argument");
-  NDMPS_REQUIRE(h_bonds[0] == 1 && h_bonds[L] == 1, "open boundary bonds must be 1");
-  int64_t numel = 1;
-  {
-    // every intermediate lands in d_ws or d_dense (N = prod(dims) elements): every bond must be at most the
-    // product of the site dims on either side of it, as any MPS of a dense tensor has
-    int64_t left = 1;
-    for (int i = 0; i < L; ++i) {
-      NDMPS_REQUIRE(h_dims[i] >= 1 && h_cores[i], "dims[%d] must be positive and core %d non-NULL", i, i);
-      numel *= h_dims[i];
-    }
-    for (int i = 0; i < L; ++i) {
-      left *= h_dims[i];
-      NDMPS_REQUIRE(h_bonds[i + 1] >= 1 && h_bonds[i + 1] <= left && h_bonds[i + 1] <= numel / left,
-                    "bond %d = %lld exceeds min(%lld, %lld), the rank any unfolding can have", i + 1,
-                    (long long)h_bonds[i + 1], (long long)left, (long long)(numel / left));
-    }
-  }
-  const int64_t need = chain_workspace(L, h_dims, h_bonds, sizeof(T) == 8 ? 8 : 4);
-  if (!d_ws || ws_bytes < need) {
-    ndmps::set_error("chain workspace too small: %lld < %lld", (long long)ws_bytes, (long long)need);
-    return NDMPS_EWORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (L == 1) {
-    NDMPS_CHECK_HIP(hipMemcpyAsync(d_dense, h_cores[0], numel * sizeof(T), hipMemcpyDeviceToDevice, s));
-    return NDMPS_OK;
-  }
-  const ChainPlan p = chain_plan(L, h_dims, h_bonds);
-  if (scatter) {
-    // refused before the first launch: the cumulative products below may already write d_dense
-    int64_t tail_cols = 1;
-    for (int i = p.j0; i < L; ++i) tail_cols *= h_dims[i];
-    NDMPS_REQUIRE(p.j0 < L && scatter->n_cols == tail_cols,
-                  "scatter tables are for %lld tail columns, the chain's tail has %lld", (long long)scatter->n_cols,
-                  (long long)(p.j0 < L ? tail_cols : 0));
-  }
-  T* ws_left = (T*)d_ws;
-  T* ws_tail[2] = {ws_left + ndmps::round_up(p.left_elems, 64),
-                   ws_left + ndmps::round_up(p.left_elems, 64) + ndmps::round_up(p.tail_elems, 64)};
-  // scratch behind the three buffers (bf16: transposed right operands)
-  char* tws = (char*)(ws_tail[1] + ndmps::round_up(p.tail_elems, 64));
-  tws += (256 - ((uintptr_t)tws & 255)) & 255;
-  const int64_t tws_bytes = ((char*)d_ws + ws_bytes) - tws;
-  const int j0 = p.j0;
-  // ---- tail, right to left: R_i (k_i x N_i) = [core_i as (k_i d_i) x k_{i+1}] R_{i+1}
-  const T* R = nullptr;
-  int64_t n_tail = 1;
-  if (j0 < L) {
-    R = h_cores[L - 1];
-    n_tail = h_dims[L - 1];
-    int t = 0;
-    for (int i = L - 2; i >= j0; --i) {
-      NDMPS_TRY(gemm_T(0, h_bonds[i] * h_dims[i], n_tail, h_bonds[i + 1], h_cores[i], R, n_tail, ws_tail[t], tws,
-                       tws_bytes, s));
-      R = ws_tail[t];
-      t ^= 1;
-      n_tail *= h_dims[i];
-    }
-  }
-  // ---- left part, cumulative: Left_i (rows_i x k_{i+1}); the last product of the whole chain writes d_dense,
-  //      the one before it must therefore land in the workspace
-  const int last_left = j0 < L ? j0 - 1 : L - 1;  // index of the last cumulative GEMM (site index), 0: none
-  const T* left = h_cores[0];
-  int64_t rows = h_dims[0];
-  for (int i = 1; i <= last_left; ++i) {
-    const int64_t chi = h_bonds[i], cols = h_dims[i] * h_bonds[i + 1];
-    // products remaining after this one (cumulative ones + the final Left R)
-    const int remaining = (last_left - i) + (j0 < L ? 1 : 0);
-    T* out = remaining % 2 == 0 ? d_dense : ws_left;
-    NDMPS_TRY(gemm_T(0, rows, cols, chi, left, h_cores[i], cols, out, tws, tws_bytes, s));
-    left = out;
-    rows *= h_dims[i];
-  }
-  if (j0 < L) {
-    // R sits in one tail buffer (or is the last core itself); the other one is free for its reordered copy
-    T* spare = (R == ws_tail[0]) ? ws_tail[1] : ws_tail[0];
-    NDMPS_TRY(final_product(rows, n_tail, h_bonds[j0], left, R, spare, d_dense, scatter, tws, tws_bytes, s));
-  }
-  NDMPS_REQUIRE(j0 < L || left == d_dense, "internal: chain result landed in the wrong buffer");
-  return NDMPS_OK;
-}
-}  // namespace
-
-extern "C" int ndmps_chain_contract_f32(int L, const int64_t* h_dims, const int64_t* h_bonds,
-                                        const float* const* h_cores, float* d_dense, void* d_ws,
-                                        int64_t ws_bytes, ndmps_stream_t stream) {
-  return chain_impl<float>(L, h_dims, h_bonds, h_cores, d_dense, d_ws, ws_bytes, stream);
-}
-
-// number of trailing columns the chain pre-contracts (product of the dims of the tail sites), 0 if none
-extern "C" int64_t ndmps_chain_tail_columns(int L, const int64_t* h_dims) {
-  if (L < 2 || !h_dims) return 0;
-  int64_t right = 1;
-  int taken = 0;
-  for (int i = L - 1; i >= 1; --i) {
-    if (right * h_dims[i] > kChainTailMax) break;
-    right *= h_dims[i];
-    ++taken;
-  }
-  return taken > 0 ? right : 0;
-}
-
-// Chain contraction that writes the C-order VOLUME: the inverse index permutation (core/ndmps.py:144-148) rides
-// on the last product, every element goes from the accumulator to its voxel (d_row_off / d_col_off /
-// d_col_perm: ndmps_plan_split_offsets for n_cols = ndmps_chain_tail_columns, columns sorted by offset).  The
-// site-order tensor is never written.
-extern "C" int ndmps_chain_contract_scatter_f32(int L, const int64_t* h_dims, const int64_t* h_bonds,
-                                                const float* const* h_cores, float* d_out,
-                                                const int64_t* d_row_off, const int64_t* d_col_off,
-                                                const int32_t* d_col_perm, int64_t n_cols, void* d_ws,
-                                                int64_t ws_bytes, ndmps_stream_t stream) {
-  NDMPS_REQUIRE(d_row_off && d_col_off && d_col_perm && n_cols >= 1, "NULL scatter table");
-  ChainScatter sc{d_row_off, d_col_off, d_col_perm, n_cols};
-  return chain_impl<float>(L, h_dims, h_bonds, h_cores, d_out, d_ws, ws_bytes, stream, &sc);
-}
-
-// The same for a list of MPS over the same sites (conv_to_tensors, evaluation/benchmark.py:80-100): volume b has
-// bonds h_bonds[b (L + 1) ..], cores h_cores[b L ..] and goes to h_out[b]; one workspace (sized for the largest
-// bonds) serves them in turn on `stream`.  The launches of all volumes are issued by this one call.
-namespace {
-struct PtrPairs {  // operands of a small per-volume kernel run for a whole batch (grid.y)
-  const void* in[64];
-  void* out[64];
-};
-__global__ void __launch_bounds__(256)
-gather_cols_batched_kernel(PtrPairs pp, int64_t rows, int64_t cols, const int32_t* __restrict__ perm) {
-  const float* in = static_cast<const float*>(pp.in[blockIdx.y]);
-  float* out = static_cast<float*>(pp.out[blockIdx.y]);
-  const int64_t total = rows * cols;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
-    out[e] = in[(e / cols) * cols + perm[e % cols]];
-}
-
-// chain_impl<float> with the scatter epilogue for `count` (<= 64) MPS that share their bonds: every stage is one
-// batched launch (ndmps_sgemm_batched); volume b works in its own slice of the workspace.  Same products in the
-// same order as chain_impl on each volume: bit-identical results.
-int chain_batched_same_bonds(int count, int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
-                             float* const* h_out, const ChainScatter& sc, char* d_ws, int64_t ws_each, hipStream_t s) {
-  const ChainPlan p = chain_plan(L, h_dims, h_bonds);
-  const int j0 = p.j0;
-  NDMPS_REQUIRE(L >= 2 && j0 < L, "internal: batched chain needs a pre-contracted tail");
-  {
-    // refused before the first launch: the cumulative products below may already write h_out
-    int64_t tail_cols = 1;
-    for (int i = j0; i < L; ++i) tail_cols *= h_dims[i];
-    NDMPS_REQUIRE(sc.n_cols == tail_cols, "scatter tables are for %lld tail columns, the chain's tail has %lld",
-                  (long long)sc.n_cols, (long long)tail_cols);
-  }
-  std::vector<const float*> A(count), B(count);
-  std::vector<float*> Cc(count);
-  std::vector<float*> ws_left(count), ws_tail0(count), ws_tail1(count);
-  for (int b = 0; b < count; ++b) {
-    ws_left[b] = (float*)(d_ws + (int64_t)b * ws_each);
-    ws_tail0[b] = ws_left[b] + ndmps::round_up(p.left_elems, 64);
-    ws_tail1[b] = ws_tail0[b] + ndmps::round_up(p.tail_elems, 64);
-  }
-  // ---- tail, right to left
-  std::vector<const float*> R(count);
-  for (int b = 0; b < count; ++b) R[b] = h_cores[(int64_t)b * L + L - 1];
-  int64_t n_tail = h_dims[L - 1];
-  int t = 0;
-  for (int i = L - 2; i >= j0; --i) {
-    for (int b = 0; b < count; ++b) {
-      A[b] = h_cores[(int64_t)b * L + i];
-      B[b] = R[b];
-      Cc[b] = t == 0 ? ws_tail0[b] : ws_tail1[b];
-    }
-    NDMPS_TRY(ndmps_sgemm_batched(count, 0, 0, h_bonds[i] * h_dims[i], n_tail, h_bonds[i + 1], A.data(), h_bonds[i + 1],
-                                  B.data(), n_tail, Cc.data(), n_tail, s));
-    for (int b = 0; b < count; ++b) R[b] = Cc[b];
-    t ^= 1;
-    n_tail *= h_dims[i];
-  }
-  // ---- left part, cumulative; the product before the final one must land in the workspace
-  const int last_left = j0 - 1;
-  std::vector<const float*> left(count);
-  for (int b = 0; b < count; ++b) left[b] = h_cores[(int64_t)b * L];
-  int64_t rows = h_dims[0];
-  for (int i = 1; i <= last_left; ++i) {
-    const int64_t chi = h_bonds[i], cols = h_dims[i] * h_bonds[i + 1];
-    const int remaining = (last_left - i) + 1;
-    for (int b = 0; b < count; ++b) {
-      A[b] = left[b];
-      B[b] = h_cores[(int64_t)b * L + i];
-      Cc[b] = remaining % 2 == 0 ? h_out[b] : ws_left[b];
-    }
-    NDMPS_TRY(ndmps_sgemm_batched(count, 0, 0, rows, cols, chi, A.data(), chi, B.data(), cols, Cc.data(), cols, s));
-    for (int b = 0; b < count; ++b) left[b] = Cc[b];
-    rows *= h_dims[i];
-  }
-  // ---- final product: columns of R in memory order, every element straight to its voxel
-  PtrPairs pp;
-  for (int b = 0; b < count; ++b) {
-    float* spare = (R[b] == ws_tail0[b]) ? ws_tail1[b] : ws_tail0[b];
-    pp.in[b] = R[b];
-    pp.out[b] = spare;
-    A[b] = left[b];
-    B[b] = spare;
-    Cc[b] = h_out[b];
-  }
-  const int64_t k = h_bonds[j0];
-  hipLaunchKernelGGL(gather_cols_batched_kernel, dim3(grid1d(k * n_tail), count), dim3(256), 0, s, pp, k, n_tail,
-                     sc.col_perm);
-  NDMPS_LAUNCH_CHECK();
-  return ndmps_sgemm_indexed_batched(count, rows, n_tail, k, A.data(), k, nullptr, nullptr, 0, B.data(), n_tail, Cc.data(), 0,
-                                     sc.row_off, sc.col_off, s);
-}
-}  // namespace
-
-// The same for a list of MPS over the same sites (conv_to_tensors, evaluation/benchmark.py:80-100): volume b has
-// bonds h_bonds[b (L + 1) ..], cores h_cores[b L ..] and goes to h_out[b].  MPS that share their bonds (a lockstep
-// group whose caps bind) go through the chain TOGETHER, one batched launch per stage, each in its own slice of
-// d_ws (ndmps_chain_batched_workspace_bytes); otherwise the volumes are contracted in turn.  Bit-identical to
-// ndmps_chain_contract_scatter_f32 on each volume either way.
-extern "C" int64_t ndmps_chain_batched_workspace_bytes(int batch, int L, const int64_t* h_dims, const int64_t* h_bonds) {
-  if (batch < 1 || L < 1 || !h_dims || !h_bonds) return 0;
-  int64_t each = 0;
-  bool same = true;
-  for (int b = 0; b < batch; ++b) {
-    each = std::max(each, ndmps_chain_workspace_bytes(L, h_dims, h_bonds + (int64_t)b * (L + 1)));
-    for (int i = 0; i <= L; ++i) same = same && h_bonds[(int64_t)b * (L + 1) + i] == h_bonds[i];
-  }
-  each = ndmps::round_up(each, 256);
-  return same ? each * std::min(batch, 64) : each;
-}
-
-extern "C" int ndmps_chain_contract_scatter_batched_f32(int batch, int L, const int64_t* h_dims, const int64_t* h_bonds,
-                                                        const float* const* h_cores, float* const* h_out,
-                                                        const int64_t* d_row_off, const int64_t* d_col_off,
-                                                        const int32_t* d_col_perm, int64_t n_cols, void* d_ws,
-                                                        int64_t ws_bytes, ndmps_stream_t stream) {
-  NDMPS_REQUIRE(batch >= 1 && L >= 1 && h_bonds && h_cores && h_out, "bad batched chain argument");
-  NDMPS_REQUIRE(d_row_off && d_col_off && d_col_perm && n_cols >= 1, "NULL scatter table");
-  ChainScatter sc{d_row_off, d_col_off, d_col_perm, n_cols};
-  bool same = batch > 1 && L >= 2;
-  for (int b = 1; b < batch && same; ++b)
-    for (int i = 0; i <= L; ++i) same = same && h_bonds[(int64_t)b * (L + 1) + i] == h_bonds[i];
-  const int64_t each = ndmps::round_up(ndmps_chain_workspace_bytes(L, h_dims, h_bonds), 256);
-  if (same && chain_plan(L, h_dims, h_bonds).j0 < L && d_ws && ws_bytes >= each * std::min(batch, 64)) {
-    // validate once through the single-volume entry's checks (bonds, operands) on volume 0 without launching
-    for (int b = 0; b < batch; ++b) {
-      NDMPS_REQUIRE(h_out[b], "NULL output %d", b);
-      for (int i = 0; i < L; ++i) NDMPS_REQUIRE(h_cores[(int64_t)b * L + i], "core %d of volume %d is NULL", i, b);
-    }
-    {
-      int64_t numel = 1, left = 1;
-      NDMPS_REQUIRE(h_bonds[0] == 1 && h_bonds[L] == 1, "open boundary bonds must be 1");
-      for (int i = 0; i < L; ++i) {
-        NDMPS_REQUIRE(h_dims[i] >= 1, "dims[%d] must be positive", i);
-        numel *= h_dims[i];
-      }
-      for (int i = 0; i < L; ++i) {
-        left *= h_dims[i];
-        NDMPS_REQUIRE(h_bonds[i + 1] >= 1 && h_bonds[i + 1] <= left && h_bonds[i + 1] <= numel / left,
-                      "bond %d = %lld exceeds min(%lld, %lld), the rank any unfolding can have", i + 1,
-                      (long long)h_bonds[i + 1], (long long)left, (long long)(numel / left));
-      }
-    }
-    for (int base = 0; base < batch; base += 64) {
-      const int count = std::min(64, batch - base);
-      NDMPS_TRY(chain_batched_same_bonds(count, L, h_dims, h_bonds, h_cores + (int64_t)base * L, h_out + base, sc,
-                                         (char*)d_ws, each, (hipStream_t)stream));
-    }
-    return NDMPS_OK;
-  }
-  for (int b = 0; b < batch; ++b)
-    NDMPS_TRY(chain_impl<float>(L, h_dims, h_bonds + (int64_t)b * (L + 1), h_cores + (int64_t)b * L, h_out[b], d_ws,
-                                ws_bytes, stream, &sc));
-  return NDMPS_OK;
-}
-
-extern "C" int ndmps_chain_contract_bf16(int L, const int64_t* h_dims, const int64_t* h_bonds,
-                                         const void* const* h_cores, void* d_dense, void* d_ws,
-                                         int64_t ws_bytes, ndmps_stream_t stream) {
-  return chain_impl<__bf16>(L, h_dims, h_bonds, (const __bf16* const*)h_cores, (__bf16*)d_dense, d_ws, ws_bytes, stream);
-}
-
-// fp64 cores: every product on the fp64 MFMA (workspace: ndmps_chain_workspace_bytes_f64)
-extern "C" int ndmps_chain_contract_f64(int L, const int64_t* h_dims, const int64_t* h_bonds,
-                                        const double* const* h_cores, double* d_dense, void* d_ws,
-                                        int64_t ws_bytes, ndmps_stream_t stream) {
-  return chain_impl<double>(L, h_dims, h_bonds, h_cores, d_dense, d_ws, ws_bytes, stream);
-}
-
-// =================================================================== overlap
-namespace {
-struct OverlapBuffers {
-  double* E[2];    // transfer matrix, ping and pong
-  double *A, *B;   // one core of either state in fp64
-  double* X;       // E^T A
-};
-void carve_overlap(Arena& ar, int L, const int64_t* dims, const int64_t* bonds_a, const int64_t* bonds_b, OverlapBuffers& o) {
-  int64_t emax = 1, amax = 1, bmax = 1, xmax = 1;
-  for (int i = 0; i < L; ++i) {
-    emax = std::max(emax, bonds_a[i + 1] * bonds_b[i + 1]);
-    amax = std::max(amax, bonds_a[i] * dims[i] * bonds_a[i + 1]);
-    bmax = std::max(bmax, bonds_b[i] * dims[i] * bonds_b[i + 1]);
-    xmax = std::max(xmax, bonds_b[i] * dims[i] * bonds_a[i + 1]);
-  }
-  o.E[0] = ar.take<double>(emax);
-  o.E[1] = ar.take<double>(emax);
-  o.A = ar.take<double>(amax);
-  o.B = ar.take<double>(bmax);
-  o.X = ar.take<double>(xmax);
-}
-}  // namespace
-extern "C" int64_t ndmps_overlap_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds_a,
-                                                 const int64_t* h_bonds_b) {
-  if (L < 1 || !h_dims || !h_bonds_a || !h_bonds_b) return 0;
-  Arena sizing(nullptr, 0);
-  OverlapBuffers unused;
-  carve_overlap(sizing, L, h_dims, h_bonds_a, h_bonds_b, unused);
-  return ndmps::round_up(sizing.used, 256) + 256;
-}
-
-namespace {
-template <typename T>
-int overlap_impl(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const T* const* h_cores_a,
-                 const int64_t* h_bonds_b, const T* const* h_cores_b, double* h_out, void* d_ws, int64_t ws_bytes,
-                 ndmps_stream_t stream) {
-  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds_a && h_bonds_b && h_cores_a && h_cores_b && h_out,
-                "bad overlap argument");
-  const int64_t need = ndmps_overlap_workspace_bytes(L, h_dims, h_bonds_a, h_bonds_b);
-  if (!d_ws || ws_bytes < need) {
-    ndmps::set_error("overlap workspace too small: %lld < %lld", (long long)ws_bytes, (long long)need);
-    return NDMPS_EWORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  Arena ar(d_ws, ws_bytes);
-  OverlapBuffers o;
-  carve_overlap(ar, L, h_dims, h_bonds_a, h_bonds_b, o);
-  NDMPS_REQUIRE(ar.fits(), "workspace carve failed");
-  double *const *E = o.E, *A = o.A, *B = o.B, *X = o.X;
-
-  hipLaunchKernelGGL(set_scalar_f64_kernel, dim3(1), dim3(1), 0, s, E[0], 1.0);  // no copy from pageable host memory
-  int cur = 0;
-  for (int i = 0; i < L; ++i) {
-    const int64_t ca = h_bonds_a[i], ca2 = h_bonds_a[i + 1];
-    const int64_t cb = h_bonds_b[i], cb2 = h_bonds_b[i + 1];
-    const int64_t d = h_dims[i];
-    hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(ca * d * ca2)), dim3(256), 0, s, h_cores_a[i], ca * d * ca2, A);
-    hipLaunchKernelGGL(f32_to_f64_kernel<T>, dim3(grid1d(cb * d * cb2)), dim3(256), 0, s, h_cores_b[i], cb * d * cb2, B);
-    NDMPS_LAUNCH_CHECK();
-    // X (cb, d ca2) = E^T (cb, ca) A (ca, d ca2)
-    NDMPS_TRY(ndmps_dgemm(1, 0, cb, d * ca2, ca, E[cur], cb, A, d * ca2, X, d * ca2, s));
-    // E' (ca2, cb2) = X'^T B' with X' = (cb d, ca2), B' = (cb d, cb2)
-    NDMPS_TRY(ndmps_dgemm(1, 0, ca2, cb2, cb * d, X, ca2, B, cb2, E[cur ^ 1], cb2, s));
-    cur ^= 1;
-  }
-  NDMPS_CHECK_HIP(hipMemcpyAsync(h_out, E[cur], sizeof(double), hipMemcpyDeviceToHost, s));
-  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-  return NDMPS_OK;
-}
-}  // namespace
-
-extern "C" int ndmps_overlap_f32(int L, const int64_t* h_dims, const int64_t* h_bonds_a,
-                                 const float* const* h_cores_a, const int64_t* h_bonds_b,
-                                 const float* const* h_cores_b, double* h_out, void* d_ws,
-                                 int64_t ws_bytes, ndmps_stream_t stream) {
-  return overlap_impl<float>(L, h_dims, h_bonds_a, h_cores_a, h_bonds_b, h_cores_b, h_out, d_ws, ws_bytes, stream);
-}
-// fp64 cores (same workspace query)
-extern "C" int ndmps_overlap_f64(int L, const int64_t* h_dims, const int64_t* h_bonds_a,
-                                 const double* const* h_cores_a, const int64_t* h_bonds_b,
-                                 const double* const* h_cores_b, double* h_out, void* d_ws,
-                                 int64_t ws_bytes, ndmps_stream_t stream) {
-  return overlap_impl<double>(L, h_dims, h_bonds_a, h_cores_a, h_bonds_b, h_cores_b, h_out, d_ws, ws_bytes, stream);
 }

@@ -512,6 +512,16 @@ int ndmps_chain_contract_scatter_batched_f32(int batch, int L, const int64_t* h_
                                              const int64_t* d_row_off, const int64_t* d_col_off,
                                              const int32_t* d_col_perm, int64_t n_cols, void* d_ws,
                                              int64_t ws_bytes, ndmps_stream_t stream);
+/* The plan a chain call would run by, for tests and tools: host arithmetic only, no GPU call, no effect on any launch.
+ * elem: 0 fp32, 1 bf16, 2 fp64.  h_out receives NDMPS_CHAIN_PLAN_SLOTS(L) values:
+ *    0 j0 (first site of the pre-contracted tail, L: none)   1 tail columns (0: none)   2 number of products (L - 1)
+ *    3 left_elems   4 tail_elems (capacities of ws_left / of either tail buffer)   5 workspace bytes
+ * then, per product in the order of the launches, C (m x n) = A (m x k) B (k x n):
+ *    kind (0 tail, 1 left, 2 final)   m   n   k   A   B   C   spare
+ * with buffers named as: i >= 0 core i, -1 ws_left, -2 ws_tail0, -3 ws_tail1, -4 the output, -5 none.  spare: the
+ * tail buffer the final product's right operand is gathered into by the scatter entries. */
+#define NDMPS_CHAIN_PLAN_SLOTS(L) (6 + 8 * ((L) - 1))
+int ndmps_chain_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t* h_out);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */

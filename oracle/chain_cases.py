@@ -1,7 +1,7 @@
 """Oracle (test infrastructure): the chains the decoders are tested on, and how their cores are drawn.
 
-The (dims, bonds) below are chosen from the branches of the chain contraction (csrc/tt.hip: ``chain_plan`` /
-``chain_impl``), not from what a sweep produces.  The tail of a chain is the longest run of trailing sites, never
+The (dims, bonds) below are chosen from the branches of the chain contraction (``chain_plan`` in csrc/chain_plan.h,
+run by csrc/chain.hip), not from what a sweep produces.  The tail of a chain is the longest run of trailing sites, never
 site 0, whose dims multiply to at most TAIL_MAX = 4096; it is contracted right to left first, the sites before it
 are contracted cumulatively left to right, and one last product joins the two.  Every bond obeys
 ``chi_i <= min(prod(dims[:i]), prod(dims[i:]))``, which the library requires (its intermediates live in N elements).
@@ -57,7 +57,7 @@ INTEGER_CHAINS = {
     "int_wide": ([8, 16, 9, 10], [1, 8, 16, 10, 1]),                        # 1280: exact in fp32 / fp64 only
 }
 
-# the graded family is drawn on these chains (one per route through chain_impl)
+# the graded family is drawn on these chains (one per route through the chain's plan)
 GRADED = ["L2_maxbond", "L5_ragged", "L5_tail_last", "L5_mid_tail_65", "L3_no_tail"]
 
 STORAGES = ("f32", "bf16", "f64")

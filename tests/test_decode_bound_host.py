@@ -1,7 +1,7 @@
 """The decoders' error bar (oracle/chain_bound.py) checked on the CPU, before any kernel is held to it.
 
 * sound: a NumPy float32 restatement of the chain contraction in the library's stage order (tail right to left,
-  then left to right, then the product that joins them; csrc/tt.hip ``chain_impl``) stays within ``chain_bound`` of
+  then left to right, then the product that joins them; csrc/chain_plan.h) stays within ``chain_bound`` of
   the fp64 contraction on every case of oracle/chain_cases.py, and so does the same chain with its intermediates
   rounded to bf16 against the bf16 bound;
 * teeth: three deliberate mistakes in that chain -- the last term of the inner sum of the final product dropped,
@@ -31,7 +31,7 @@ def _bf16(x):
 
 
 def staged_chain(cores, dims, bonds, store=None, mutate=None):
-    """The chain in float32, staged as chain_impl stages it.  ``store``: rounding applied to every product
+    """The chain in float32, staged as chain_plan stages it.  ``store``: rounding applied to every product
     (bf16 intermediates).  ``mutate`` in {None, "drop", "swap"}: a mistake made in the final product."""
     store = store or (lambda x: x)
     c32 = [np.asarray(c, dtype=np.float32) for c in cores]

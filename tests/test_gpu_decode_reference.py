@@ -241,7 +241,7 @@ def _check_batch(tag, dims, bonds_list, ws_single=False):
         assert torch.equal(out[b], single), f"volume {b}: batched decode differs from the single-volume call"
 
 
-@pytest.mark.parametrize("batch", [2, 64, 65, 130])
+@pytest.mark.parametrize("batch", [1, 2, 64, 65, 130])
 @pytest.mark.parametrize("name", ["L5_ragged", "L4_tail_last"])
 def test_batched_decode_same_bonds(name, batch):
     dims, bonds = cc.CHAINS[name]
