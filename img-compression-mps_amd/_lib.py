@@ -86,6 +86,11 @@ SIGNATURES = {
                                             i64, vp]),
     "ndmps_region_contract_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), p_i64, p_i64, vp, i64, i64, vp, vp,
                                             i64, vp]),
+    "ndmps_region_series_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64, i64]),
+    "ndmps_region_series_contract_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64, p_i64, vp, i64, vp, i64, vp,
+                                                   vp, i64, vp]),
+    "ndmps_region_series_contract_f64": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64, p_i64, vp, i64, vp, i64, vp,
+                                                   vp, i64, vp]),
     "ndmps_pool_workspace_bytes": (i64, [C.c_int, p_i64]),
     "ndmps_pool_cores": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, p_i64, p_f64, vp, i64,
                                    C.POINTER(vp), vp, i64, vp]),

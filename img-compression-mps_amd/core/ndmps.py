@@ -1557,18 +1557,154 @@ class NDMPS:
                 res = self._region_values(_region.plan_points(shape, pts))
             else:
                 n = shape[-1]
-                if len(shape) > 1:
-                    row_key = np.ravel_multi_index(tuple(pts[:-1]), shape[:-1])
-                    uniq, inv = np.unique(row_key, return_inverse=True)
-                    lead = np.stack(np.unravel_index(uniq, shape[:-1])).astype(np.int64)
-                else:
-                    uniq, inv, lead = np.zeros(1, np.int64), np.zeros(N, np.int64), np.zeros((0, 1), np.int64)
-                full = np.concatenate([np.repeat(lead, n, axis=1), np.tile(np.arange(n, dtype=np.int64), uniq.size)[None]])
+                full, sel = _region.full_rows_of_points(shape, pts)
                 rows = self._region_values(_region.plan_points(shape, full))
                 rec = _idct_last(rows, n).view(-1, n)
-                sel = torch.from_numpy(inv.ravel() * n + pts[-1]).to(device)
-                res = rec.reshape(-1).index_select(0, sel)
+                res = rec.reshape(-1).index_select(0, torch.from_numpy(sel).to(device))
         return self._result(res, as_torch, dtype)
+
+    # ------------------------------------------------- region decode of a series (one plan, one upload)
+    @staticmethod
+    def _region_series_objs(objs):
+        """The checked list of a series call: TypeError for a non-NDMPS, ValueError for an empty list, objects that
+        differ (``lincomb.check_compatible``) or an unknown shape."""
+        from . import lincomb as _lc
+
+        objs = list(objs)
+        for o in objs:
+            if not isinstance(o, NDMPS):
+                raise TypeError(f"a series takes NDMPS objects, not {type(o).__name__}")
+        if not objs:
+            raise ValueError("a series needs at least one object")
+        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
+                                   dims=o.mps.dims) for o in objs])
+        objs[0]._require_shape()
+        return objs
+
+    @staticmethod
+    def _series_is_f64(objs):
+        torch = _torch()
+        return any(o.mps.dtype == torch.float64 for o in objs)
+
+    @staticmethod
+    def _region_series_values(objs, plan):
+        """``plan``'s output elements of every frame (ndmps_region_series_contract_*): a (T, n_out) device tensor, fp64
+        if any frame has fp64 cores (the others are widened exactly), fp32 otherwise (bf16 cores upcast as in
+        ``_region_values``).  The tables are uploaded once; each chunk of frames (``region.plan_series``) uploads its
+        records -- core pointers, then bonds -- in one copy and issues L launches."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import region as _region
+
+        f64 = NDMPS._series_is_f64(objs)
+        work = torch.float64 if f64 else torch.float32
+        elem = 8 if f64 else 4
+        first = objs[0].mps
+        T, L, device = len(objs), len(first.cores), first.device
+        keep = [[c if c.dtype == work else c.to(work) for c in o.mps.cores] for o in objs]
+        ptrs = np.array([[c.data_ptr() for c in frame] for frame in keep], dtype=np.int64).reshape(T, L)
+        bonds = np.array([[1] + [c.shape[2] for c in frame] for frame in keep], dtype=np.int64).reshape(T, L + 1)
+        layout = _region.plan_series(bonds, plan, elem)
+        dims = _lib.i64_array(first.dims)
+        nodes, tiles = _lib.i64_array(plan.nodes), _lib.i64_array(plan.n_tiles)
+        tables = torch.from_numpy(plan.tables()).to(device)  # every table in one upload, once for the series
+        ws = torch.empty(max(layout.ws_bytes, 1), dtype=torch.uint8, device=device)
+        out = torch.empty((T, plan.n_out), dtype=work, device=device)
+        fn = lib.ndmps_region_series_contract_f64 if f64 else lib.ndmps_region_series_contract_f32
+        with _span("region_series"):
+            for a, b in layout.chunks:
+                records = torch.from_numpy(np.concatenate([ptrs[a:b].ravel(), bonds[a:b].ravel()])).to(device)
+                h_bonds = np.ascontiguousarray(bonds[a:b])
+                _lib.check(fn(b - a, L, dims, h_bonds.ctypes.data_as(_lib.p_i64), nodes, tiles, tables.data_ptr(),
+                              tables.numel(), records.data_ptr(), plan.n_out, out[a].data_ptr(), ws.data_ptr(),
+                              layout.ws_bytes, _lib.stream_ptr()))
+        del keep
+        return out
+
+    @staticmethod
+    def _series_result(objs, res, as_torch, dtype):
+        """``_result`` for a (T, ...) tensor of a series: float64 if the call contracted in fp64, float32 otherwise;
+        as_torch gives bf16 only when every frame is bf16 and the mode is Std."""
+        torch = _torch()
+        if as_torch:
+            if dtype is None and objs[0].mode == "Std" and all(o.mps.dtype == torch.bfloat16 for o in objs):
+                dtype = torch.bfloat16
+            return res if dtype is None else res.to(dtype)
+        return (res if res.dtype == torch.float64 else res.to(torch.float32)).cpu().numpy()
+
+    @staticmethod
+    def decode_regions(objs, key, as_torch: bool = False, dtype=None):
+        """
+        ``decode_region(key)`` of every frame of a series in one call: a result of shape ``(T,) + shape of
+        objs[0].decode_region(key)`` whose entry ``[t]`` is ``objs[t].decode_region(key, as_torch, dtype)`` -- a voxel
+        or ROI time course, a slice through time, the principal volumes of ``pca`` at a region.  The plan is built
+        and uploaded once and every launch covers all frames (csrc/region.hip); a frame's values are
+        those of its own ``decode_region``, bit for bit.
+
+        ``key`` means what it means for one object, with the same IndexError / TypeError / ValueError; the list
+        checks are those of ``gram`` (TypeError for a non-NDMPS, ValueError for an empty list or objects that differ
+        in qubit_size, shape, mode, device or site dims).  All are raised before anything runs on the device.  Bonds
+        may differ between frames.  Storage types may mix: with an fp64 frame the call contracts in fp64 (the other
+        frames' cores are widened exactly) and returns float64, otherwise it contracts in fp32 and returns float32;
+        ``as_torch=True`` gives bf16 only when every frame is bf16 in Std mode.  An empty region gives an empty result
+        without a launch; modes other than Std / DCT return None.  No counterpart in the reference.
+        """
+        torch = _torch()
+        from . import region as _region
+
+        objs = NDMPS._region_series_objs(objs)
+        first = objs[0]
+        shape = tuple(first._shape)
+        idx, keep = _region.normalize_key(key, shape)
+        if first.mode not in ("Std", "DCT"):
+            return None
+        T = len(objs)
+        out_shape = [T] + [i.size for i, k in zip(idx, keep) if k]
+        device = first.mps.device
+        with torch.cuda.device(device):
+            if any(i.size == 0 for i in idx):
+                res = torch.empty(out_shape, dtype=torch.float64 if NDMPS._series_is_f64(objs) else torch.float32,
+                                  device=device)
+            elif first.mode == "Std":
+                res = NDMPS._region_series_values(objs, _region.plan_outer(shape, idx)).view(out_shape)
+            else:
+                n = shape[-1]
+                rows = NDMPS._region_series_values(
+                    objs, _region.plan_outer(shape, idx[:-1] + [np.arange(n, dtype=np.int64)]))
+                rec = _idct_last(rows, n).view(T, -1, n)  # the rows of all frames lie back to back: one launch
+                res = rec.index_select(2, torch.from_numpy(idx[-1]).to(device)).reshape(out_shape)
+        return NDMPS._series_result(objs, res, as_torch, dtype)
+
+    @staticmethod
+    def values_at_many(objs, coords, as_torch: bool = False, dtype=None):
+        """
+        ``values_at(coords)`` of every frame of a series in one call: a (T, N) result whose row ``t`` is
+        ``objs[t].values_at(coords, as_torch, dtype)``, bit for bit.  Arguments, errors, mixed storage and result types
+        as ``decode_regions``; ``N == 0`` gives a (T, 0) result without a launch.
+        """
+        torch = _torch()
+        from . import region as _region
+
+        objs = NDMPS._region_series_objs(objs)
+        first = objs[0]
+        shape = tuple(first._shape)
+        pts = _region.normalize_points(coords, shape)
+        if first.mode not in ("Std", "DCT"):
+            return None
+        T, N = len(objs), pts.shape[1]
+        device = first.mps.device
+        with torch.cuda.device(device):
+            if N == 0:
+                res = torch.empty((T, 0), dtype=torch.float64 if NDMPS._series_is_f64(objs) else torch.float32,
+                                  device=device)
+            elif first.mode == "Std":
+                res = NDMPS._region_series_values(objs, _region.plan_points(shape, pts))
+            else:
+                full, sel = _region.full_rows_of_points(shape, pts)
+                rows = NDMPS._region_series_values(objs, _region.plan_points(shape, full))
+                rec = _idct_last(rows, shape[-1]).view(T, -1)
+                res = rec.index_select(1, torch.from_numpy(sel).to(device))
+        return NDMPS._series_result(objs, res, as_torch, dtype)
 
     # ------------------------------------------------------------ block-averaged decode
     def _pool_levels(self, levels):

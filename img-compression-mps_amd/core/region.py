@@ -16,6 +16,9 @@ core, written to its place in the C-order result (repeats of an index are separa
 ``RegionPlan.tables`` is what ``ndmps_region_contract_*`` (csrc/region.hip) reads: per level ``parent`` (nodes sorted
 by ``phys``) and tiles ``(phys, row0, count <= TILE_ROWS)`` of rows that share ``phys``; then ``leaf_parent`` and
 ``leaf_phys``.  Everything is range-checked here before it is uploaded.
+
+A series (``NDMPS.decode_regions`` / ``values_at_many``) uses one plan for all its frames; ``plan_series`` lays the
+frames' slabs out in the workspace of ``ndmps_region_series_contract_*`` and cuts the series into chunks.
 """
 from __future__ import annotations
 
@@ -27,6 +30,12 @@ import numpy as np
 from ..utils import core as _core
 
 TILE_ROWS = 32  # rows of one gathered product tile (csrc/region.hip kTileRows)
+MAX_SERIES_FRAMES = 65535  # frames of one ndmps_region_series_contract_* call (a grid dimension)
+# Largest workspace one chunk of a series may take (``plan_series``).  A memory policy, not a measurement: 1 GiB is
+# well under a percent of the card's HBM and holds both buffers of 64 frames of a 256 x 256 slice at chi = 64 (2 MiB
+# a frame) five hundred times over, so real series run in one chunk, while a huge ROI on thousands of frames cannot
+# take the memory the cores and the result need.  A single frame that needs more than this is a chunk of its own.
+SERIES_WS_BYTES = 1 << 30
 _I32_MAX = np.iinfo(np.int32).max
 
 
@@ -112,6 +121,20 @@ def normalize_points(coords, shape):
     return np.ascontiguousarray(arr % n)
 
 
+def full_rows_of_points(shape, pts):
+    """DCT mode decodes the last axis in full: the points (ndim, U * n) of every distinct last-axis row that ``pts``
+    (``normalize_points``) touches, row after row, and for each point of ``pts`` its position among them."""
+    n, N = shape[-1], pts.shape[1]
+    if len(shape) > 1:
+        row_key = np.ravel_multi_index(tuple(pts[:-1]), shape[:-1])
+        uniq, inv = np.unique(row_key, return_inverse=True)
+        lead = np.stack(np.unravel_index(uniq, shape[:-1])).astype(np.int64)
+    else:
+        uniq, inv, lead = np.zeros(1, np.int64), np.zeros(N, np.int64), np.zeros((0, 1), np.int64)
+    full = np.concatenate([np.repeat(lead, n, axis=1), np.tile(np.arange(n, dtype=np.int64), uniq.size)[None]])
+    return full, inv.ravel() * n + pts[-1]
+
+
 # ------------------------------------------------------------------------------------------------- plan
 class RegionPlan:
     """Level tables of one region.  ``levels[s] = (parent, phys)`` for ``s < L - 1`` (nodes sorted by phys);
@@ -173,6 +196,39 @@ class RegionPlan:
             parts += [parent, tiles.ravel()]
         parts += [self.leaf_parent, self.leaf_phys]
         return np.concatenate(parts).astype(np.int32)
+
+
+class SeriesLayout:
+    """Workspace layout of one region on T frames (``plan_series``): ``caps[s] = max_t bonds[t][s]``, the slab of a
+    frame ``frame_stride`` in elements, ``chunks`` = [(start, stop), ...] frame ranges contracted in turn, and
+    ``ws_bytes``, the workspace of the largest chunk (what ``ndmps_region_series_workspace_bytes`` returns for as many
+    frames of these caps)."""
+
+    def __init__(self, caps, frame_stride, ws_bytes, chunks):
+        self.caps, self.frame_stride, self.ws_bytes, self.chunks = caps, frame_stride, ws_bytes, chunks
+
+
+def plan_series(bonds, plan, elem_bytes, ws_limit=None):
+    """Layout of ``plan`` on a series whose frames have the bond lists ``bonds`` (T, L + 1), elements of
+    ``elem_bytes`` bytes.  Frame t of a chunk owns a slab of ``frame_stride = max_s nodes_s * cap_{s+1}`` elements in
+    each of the two ping-pong buffers, whatever its own bonds; a chunk holds at most MAX_SERIES_FRAMES frames and as
+    many as keep ``2 * round_up(frames * frame_stride * elem_bytes, 256)`` within ``ws_limit`` (SERIES_WS_BYTES), but
+    at least one."""
+    b = np.asarray(bonds, dtype=np.int64)
+    L = len(plan.site_dims)
+    if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] != L + 1:
+        raise ValueError(f"bond lists of shape {b.shape}, expected (T >= 1, {L + 1})")
+    if (b < 1).any() or (b[:, 0] != 1).any() or (b[:, L] != 1).any():
+        raise ValueError("open chains with bonds >= 1 expected")
+    T = b.shape[0]
+    limit = SERIES_WS_BYTES if ws_limit is None else int(ws_limit)
+    caps = [int(v) for v in b.max(axis=0)]
+    stride = max([1] + [n * caps[s + 1] for s, n in enumerate(plan.nodes)])
+    per = min(T, MAX_SERIES_FRAMES)
+    if L > 1:
+        per = max(1, min(per, (limit // 2) // 256 * 256 // (stride * elem_bytes)))
+    ws = 0 if L == 1 else 2 * (-(-per * stride * elem_bytes // 256) * 256)
+    return SeriesLayout(caps, stride, ws, [(a, min(a + per, T)) for a in range(0, T, per)])
 
 
 def _tiles(phys):

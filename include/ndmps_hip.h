@@ -555,6 +555,37 @@ int ndmps_region_contract_f64(int L, const int64_t* h_dims, const int64_t* h_bon
                               ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Region decode of a series (NDMPS.decode_regions / values_at_many): the same region of T frames over the same
+ * sites in one call -- one plan, one table upload, L launches with a frame dimension.  h_dims, h_nodes, h_tiles,
+ * d_tables and table_len are those of ndmps_region_contract_* (the plan depends on the shape and the key only).
+ * h_bonds (T x (L + 1), row t the bonds of frame t, outer bonds 1; inner bonds may differ between frames) is checked
+ * on the host and gives the per-level caps cap_s = max_t bonds[t][s].
+ * d_records, the frame records, is ONE device buffer the caller fills with one copy:
+ *     T * L        core pointers (8 bytes each), frame-major: entry t * L + s is core s of frame t, a
+ *                  (bonds[t][s], h_dims[s], bonds[t][s+1]) array of the call's element type;
+ *     T * (L + 1)  int64 bonds, the same values as h_bonds.
+ * d_out is (T, n_out): frame t's region at d_out + t * n_out, element for element what ndmps_region_contract_* gives
+ * for that frame alone (one tile body serves both kernel families).
+ * Workspace: two ping-pong buffers of T slabs; frame t uses the slab at t * frame_stride elements, frame_stride =
+ * max_s h_nodes[s] * cap_{s+1}, with its rows packed at its own bond.  ndmps_region_series_workspace_bytes gives
+ * 2 * round_up(T * frame_stride * elem_bytes, 256) (0 for L == 1, -1 for bad arguments); a smaller d_ws returns
+ * NDMPS_EWORKSPACE before anything is launched.  1 <= T <= 65535 (a grid dimension) and L <= 64: larger series are
+ * contracted in chunks of frames by the caller (core/region.py plan_series).
+ * The kernels trust the records no more than the tables: a frame whose device record holds a bond below 1 or above
+ * its cap, or a null core pointer, reads nothing, writes nothing to the workspace and gets zeros in d_out.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_region_series_workspace_bytes(int T, int L, const int64_t* h_bonds, const int64_t* h_nodes,
+                                            int64_t elem_bytes);
+int ndmps_region_series_contract_f32(int T, int L, const int64_t* h_dims, const int64_t* h_bonds,
+                                     const int64_t* h_nodes, const int64_t* h_tiles, const int32_t* d_tables,
+                                     int64_t table_len, const void* d_records, int64_t n_out, float* d_out,
+                                     void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_region_series_contract_f64(int T, int L, const int64_t* h_dims, const int64_t* h_bonds,
+                                     const int64_t* h_nodes, const int64_t* h_tiles, const int32_t* d_tables,
+                                     int64_t table_len, const void* d_records, int64_t n_out, double* d_out,
+                                     void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Block-averaged decode (NDMPS.downsample / sum / mean): no reference counterpart (there: to_tensor(), core/ndmps.py:
  * 131-153, then a reshape and a mean).  Reduces every site of the chain (tables from core/pool.py):
  *     out_l[x, q, y] = h_weight[l] * sum_r A_l[x, qoff_l[q] + roff_l[r], y]
