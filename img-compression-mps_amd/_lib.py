@@ -62,6 +62,8 @@ SIGNATURES = {
     "ndmps_gram_f32": (C.c_int, [vp, i64, i64, i64, vp, vp, i64, vp]),
     "ndmps_gemm_bf16_workspace_bytes": (i64, [C.c_int, i64, i64]),
     "ndmps_gemm_bf16": (C.c_int, [C.c_int, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+    "ndmps_gemm_plan_query": (C.c_int, [C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int,
+                                        p_i64]),
     "ndmps_gram_batched_workspace_bytes": (i64, [C.c_int, i64, i64]),
     "ndmps_gram_plan_query": (C.c_int, [C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, p_i64]),
     "ndmps_gram_batched_f32": (C.c_int, [C.c_int, C.POINTER(vp), i64, i64, i64, vp, i64, vp, i64, vp]),

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -443,20 +444,12 @@ gemm_batched_kernel(int64_t M, int64_t N, int64_t K, GemmBatchPtrs p, int64_t ld
 }
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N>
-int launch_gemm(int transA, int transB, int64_t m, int64_t n, int64_t k, const T* A, int64_t lda,
-                const T* B, int64_t ldb, T* C, int64_t ldc, hipStream_t stream, const GemmBatchPtrs* bp = nullptr,
-                int batch = 1) {
-  dim3 grid((unsigned)ndmps::ceil_div(m, BM), (unsigned)ndmps::ceil_div(n, BN), (unsigned)batch);
+int launch_gemm(const ndmps::GemmPlan& plan, int transA, int transB, int64_t m, int64_t n, int64_t k, const T* A,
+                int64_t lda, const T* B, int64_t ldb, T* C, int64_t ldc, hipStream_t stream, const GemmBatchPtrs* bp,
+                int batch) {
+  dim3 grid((unsigned)plan.grid_x, (unsigned)plan.grid_y, (unsigned)batch);
   dim3 block(256);
-  GemmIndex gi{nullptr, nullptr, nullptr, nullptr, gemm_guarded_env()};
-  // vector path: whole quads are either inside or outside every bound, and 4-element aligned
-  const uintptr_t al = sizeof(T) * 4;
-  bool vec = lda % 4 == 0 && ldb % 4 == 0 && k % 4 == 0 && (!transA || m % 4 == 0) && (transB || n % 4 == 0);
-  if (bp) {
-    for (int z = 0; z < batch; ++z) vec = vec && (uintptr_t)bp->a[z] % al == 0 && (uintptr_t)bp->b[z] % al == 0;
-  } else {
-    vec = vec && (uintptr_t)A % al == 0 && (uintptr_t)B % al == 0;
-  }
+  GemmIndex gi{nullptr, nullptr, nullptr, nullptr, plan.guarded};
 #define NDMPS_GEMM_LAUNCH(TA_, TB_, V_)                                                                            \
   do {                                                                                                              \
     if (bp)                                                                                                         \
@@ -473,7 +466,7 @@ int launch_gemm(int transA, int transB, int64_t m, int64_t n, int64_t k, const T
     else if (transB) NDMPS_GEMM_LAUNCH(false, true, V_);         \
     else NDMPS_GEMM_LAUNCH(false, false, V_);                    \
   } while (0)
-  if (vec) NDMPS_GEMM_TRANS(true);
+  if (plan.vec) NDMPS_GEMM_TRANS(true);
   else NDMPS_GEMM_TRANS(false);
 #undef NDMPS_GEMM_TRANS
 #undef NDMPS_GEMM_LAUNCH
@@ -482,15 +475,85 @@ int launch_gemm(int transA, int transB, int64_t m, int64_t n, int64_t k, const T
 }
 
 template <typename T>
+constexpr ndmps::GemmElem gemm_elem() {
+  return sizeof(T) == 8 ? ndmps::GemmElem::F64 : ndmps::GemmElem::F32;
+}
+
+inline int64_t gemm_misalignment(const void* p) { return (int64_t)((uintptr_t)p % 64); }
+
+template <typename T>
 int gemm_check(int64_t m, int64_t n, int64_t k, const T* A, int64_t lda, int transA, const T* B,
                int64_t ldb, int transB, T* C, int64_t ldc) {
-  NDMPS_REQUIRE(m >= 0 && n >= 0 && k >= 0, "negative GEMM extent");
   NDMPS_REQUIRE(A && B && C, "NULL GEMM operand");
-  NDMPS_REQUIRE(lda >= (transA ? m : k) && ldb >= (transB ? k : n) && ldc >= n,
-                "leading dimension too small (lda=%lld ldb=%lld ldc=%lld)", (long long)lda,
-                (long long)ldb, (long long)ldc);
-  NDMPS_REQUIRE(ndmps::ceil_div(n, 16) < 65536, "GEMM n=%lld exceeds grid.y", (long long)n);
-  NDMPS_REQUIRE(ndmps::ceil_div(m, 32) < 2147483647LL, "GEMM m=%lld exceeds grid.x", (long long)m);
+  const char* why = ndmps::gemm_refusal(gemm_elem<T>(), transA, transB, m, n, k, lda, ldb, ldc);
+  NDMPS_REQUIRE(!why, "%s (m=%lld n=%lld k=%lld lda=%lld ldb=%lld ldc=%lld)", why, (long long)m, (long long)n,
+                (long long)k, (long long)lda, (long long)ldb, (long long)ldc);
+  return NDMPS_OK;
+}
+
+// One product, or the same product for every triple of a batch (bp): checked, planned (gemm_plan.h) and launched on
+// the plan's tile.  The four dense entries are this function.
+template <typename T>
+int gemm_run(int transA, int transB, int64_t m, int64_t n, int64_t k, const T* A, int64_t lda, const T* B, int64_t ldb,
+             T* C, int64_t ldc, ndmps_stream_t stream, const GemmBatchPtrs* bp, int batch) {
+  if (bp) {
+    A = static_cast<const T*>(bp->a[0]);
+    B = static_cast<const T*>(bp->b[0]);
+    C = static_cast<T*>(bp->c[0]);
+  }
+  NDMPS_TRY(gemm_check(m, n, k, A, lda, transA, B, ldb, transB, C, ldc));
+  int64_t mis_a = gemm_misalignment(A), mis_b = gemm_misalignment(B), mis_c = gemm_misalignment(C);
+  for (int z = 1; bp && z < batch; ++z) {  // one unaligned member takes the whole batch off the vector path
+    mis_a |= gemm_misalignment(bp->a[z]);
+    mis_b |= gemm_misalignment(bp->b[z]);
+    mis_c |= gemm_misalignment(bp->c[z]);
+  }
+  const ndmps::GemmPlan plan = ndmps::gemm_plan(gemm_elem<T>(), transA, transB, m, n, k, lda, ldb, ldc, mis_a, mis_b,
+                                                mis_c, gemm_guarded_env() != 0);
+  if (plan.launches == 0) return NDMPS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (bp) A = B = nullptr, C = nullptr;  // the batched kernels take their operands from bp
+#define NDMPS_GEMM_TILE(BM_, BN_, WM_, WN_)  \
+  if (plan.bm == BM_ && plan.bn == BN_)      \
+  return launch_gemm<T, BM_, BN_, WM_, WN_>(plan, transA, transB, m, n, k, A, lda, B, ldb, C, ldc, s, bp, batch)
+  if constexpr (sizeof(T) == 4) {
+    NDMPS_GEMM_TILE(128, 32, 4, 1);
+    NDMPS_GEMM_TILE(64, 64, 2, 2);
+    NDMPS_GEMM_TILE(128, 128, 2, 2);
+  } else {
+    NDMPS_GEMM_TILE(64, 16, 4, 1);
+    NDMPS_GEMM_TILE(32, 32, 2, 2);
+    NDMPS_GEMM_TILE(64, 64, 2, 2);
+  }
+#undef NDMPS_GEMM_TILE
+  ndmps::set_error("no kernel for the planned tile %d x %d", plan.bm, plan.bn);
+  return NDMPS_EINVAL;
+}
+
+// table-addressed product on the plan's tile (64 x 64 or 128 x 128), one operand triple or a batch
+int launch_gemm_indexed(const ndmps::GemmPlan& plan, int64_t m, int64_t n, int64_t k, const float* A, int64_t lda,
+                        const float* B, int64_t ldb, float* C, int64_t ldc, const GemmIndex& ix, hipStream_t s,
+                        const GemmBatchPtrs* bp, int batch) {
+  const dim3 block(256);
+  const dim3 grid((unsigned)plan.grid_x, (unsigned)plan.grid_y, (unsigned)batch);
+#define NDMPS_GEMM_IDX(BM_, V_)                                                                                        \
+  do {                                                                                                                  \
+    if (bp)                                                                                                             \
+      hipLaunchKernelGGL((gemm_batched_kernel<float, BM_, BM_, 2, 2, false, false, V_, true>), grid, block, 0, s, m, n,  \
+                         k, *bp, lda, ldb, ldc, ix);                                                                    \
+    else                                                                                                                \
+      hipLaunchKernelGGL((gemm_kernel<float, BM_, BM_, 2, 2, false, false, V_, true>), grid, block, 0, s, m, n, k, A,    \
+                         lda, B, ldb, C, ldc, ix);                                                                      \
+  } while (0)
+  if (plan.bm == 64) {
+    if (plan.vec) NDMPS_GEMM_IDX(64, true);
+    else NDMPS_GEMM_IDX(64, false);
+  } else {
+    if (plan.vec) NDMPS_GEMM_IDX(128, true);
+    else NDMPS_GEMM_IDX(128, false);
+  }
+#undef NDMPS_GEMM_IDX
+  NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
 
@@ -499,13 +562,7 @@ int gemm_check(int64_t m, int64_t n, int64_t k, const T* A, int64_t lda, int tra
 extern "C" int ndmps_sgemm(int transA, int transB, int64_t m, int64_t n, int64_t k, const float* d_A,
                            int64_t lda, const float* d_B, int64_t ldb, float* d_C, int64_t ldc,
                            ndmps_stream_t stream) {
-  NDMPS_TRY(gemm_check(m, n, k, d_A, lda, transA, d_B, ldb, transB, d_C, ldc));
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (n <= 32) return launch_gemm<float, 128, 32, 4, 1>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
-  if (n <= 64 || m <= 64)
-    return launch_gemm<float, 64, 64, 2, 2>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
-  return launch_gemm<float, 128, 128, 2, 2>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
+  return gemm_run<float>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, stream, nullptr, 1);
 }
 
 // C = A B (no transposes) with table-driven addressing of A and / or C (see GemmIndex): the reshape stage fused
@@ -520,44 +577,18 @@ extern "C" int ndmps_sgemm_indexed(int64_t m, int64_t n, int64_t k, const float*
   NDMPS_REQUIRE((d_a_row == nullptr) == (d_a_col == nullptr) && (d_c_row == nullptr) == (d_c_col == nullptr),
                 "offset tables come in (row, column) pairs");
   NDMPS_REQUIRE(ldb >= n && (d_a_row || lda >= k) && (d_c_row || ldc >= n), "leading dimension too small");
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  GemmIndex ix{d_a_row, d_a_col, d_c_row, d_c_col, gemm_guarded_env()};
-  const uintptr_t al = 16;
-  const bool vec = ldb % 4 == 0 && k % 4 == 0 && n % 4 == 0 && (uintptr_t)d_A % al == 0 && (uintptr_t)d_B % al == 0 &&
-                   (d_a_row ? a_vec4 != 0 : lda % 4 == 0);
-  const dim3 block(256);
-  if (n <= 64 || m <= 64) {
-    const dim3 grid((unsigned)ndmps::ceil_div(m, 64), (unsigned)ndmps::ceil_div(n, 64));
-    if (vec)
-      hipLaunchKernelGGL((gemm_kernel<float, 64, 64, 2, 2, false, false, true, true>), grid, block, 0, s, m, n, k, d_A,
-                         lda, d_B, ldb, d_C, ldc, ix);
-    else
-      hipLaunchKernelGGL((gemm_kernel<float, 64, 64, 2, 2, false, false, false, true>), grid, block, 0, s, m, n, k, d_A,
-                         lda, d_B, ldb, d_C, ldc, ix);
-  } else {
-    const dim3 grid((unsigned)ndmps::ceil_div(m, 128), (unsigned)ndmps::ceil_div(n, 128));
-    if (vec)
-      hipLaunchKernelGGL((gemm_kernel<float, 128, 128, 2, 2, false, false, true, true>), grid, block, 0, s, m, n, k,
-                         d_A, lda, d_B, ldb, d_C, ldc, ix);
-    else
-      hipLaunchKernelGGL((gemm_kernel<float, 128, 128, 2, 2, false, false, false, true>), grid, block, 0, s, m, n, k,
-                         d_A, lda, d_B, ldb, d_C, ldc, ix);
-  }
-  NDMPS_LAUNCH_CHECK();
-  return NDMPS_OK;
+  const ndmps::GemmPlan plan = ndmps::gemm_plan_indexed(m, n, k, lda, ldb, d_a_row != nullptr, a_vec4 != 0,
+                                                        gemm_misalignment(d_A), gemm_misalignment(d_B),
+                                                        gemm_guarded_env() != 0);
+  if (plan.launches == 0) return NDMPS_OK;
+  GemmIndex ix{d_a_row, d_a_col, d_c_row, d_c_col, plan.guarded};
+  return launch_gemm_indexed(plan, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, ix, (hipStream_t)stream, nullptr, 1);
 }
 
 extern "C" int ndmps_dgemm(int transA, int transB, int64_t m, int64_t n, int64_t k, const double* d_A,
                            int64_t lda, const double* d_B, int64_t ldb, double* d_C, int64_t ldc,
                            ndmps_stream_t stream) {
-  NDMPS_TRY(gemm_check(m, n, k, d_A, lda, transA, d_B, ldb, transB, d_C, ldc));
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (n <= 16) return launch_gemm<double, 64, 16, 4, 1>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
-  if (n <= 32 || m <= 32)
-    return launch_gemm<double, 32, 32, 2, 2>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
-  return launch_gemm<double, 64, 64, 2, 2>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, s);
+  return gemm_run<double>(transA, transB, m, n, k, d_A, lda, d_B, ldb, d_C, ldc, stream, nullptr, 1);
 }
 
 namespace {
@@ -584,15 +615,7 @@ extern "C" int ndmps_sgemm_batched(int batch, int transA, int transB, int64_t m,
                                    float* const* h_C, int64_t ldc, ndmps_stream_t stream) {
   GemmBatchPtrs bp;
   NDMPS_TRY(gemm_batched_check(batch, h_A, h_B, h_C, bp));
-  NDMPS_TRY(gemm_check(m, n, k, h_A[0], lda, transA, h_B[0], ldb, transB, h_C[0], ldc));
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const float* A = nullptr;
-  float* Cn = nullptr;
-  if (n <= 32) return launch_gemm<float, 128, 32, 4, 1>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
-  if (n <= 64 || m <= 64)
-    return launch_gemm<float, 64, 64, 2, 2>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
-  return launch_gemm<float, 128, 128, 2, 2>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
+  return gemm_run<float>(transA, transB, m, n, k, nullptr, lda, nullptr, ldb, nullptr, ldc, stream, &bp, batch);
 }
 
 extern "C" int ndmps_dgemm_batched(int batch, int transA, int transB, int64_t m, int64_t n, int64_t k,
@@ -600,15 +623,24 @@ extern "C" int ndmps_dgemm_batched(int batch, int transA, int transB, int64_t m,
                                    double* const* h_C, int64_t ldc, ndmps_stream_t stream) {
   GemmBatchPtrs bp;
   NDMPS_TRY(gemm_batched_check(batch, h_A, h_B, h_C, bp));
-  NDMPS_TRY(gemm_check(m, n, k, h_A[0], lda, transA, h_B[0], ldb, transB, h_C[0], ldc));
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const double* A = nullptr;
-  double* Cn = nullptr;
-  if (n <= 16) return launch_gemm<double, 64, 16, 4, 1>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
-  if (n <= 32 || m <= 32)
-    return launch_gemm<double, 32, 32, 2, 2>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
-  return launch_gemm<double, 64, 64, 2, 2>(transA, transB, m, n, k, A, lda, A, ldb, Cn, ldc, s, &bp, batch);
+  return gemm_run<double>(transA, transB, m, n, k, nullptr, lda, nullptr, ldb, nullptr, ldc, stream, &bp, batch);
+}
+
+// The plan a dense product would launch by, for tests and tools (slot order: include/ndmps_hip.h).  Host arithmetic
+// only: no GPU call.  The entries above go through the same gemm_plan.
+extern "C" int ndmps_gemm_plan_query(int elem, int transA, int transB, int64_t m, int64_t n, int64_t k, int64_t lda,
+                                     int64_t ldb, int64_t ldc, int64_t mis_a, int64_t mis_b, int64_t mis_c, int guarded,
+                                     int64_t* h_out) {
+  NDMPS_REQUIRE(h_out && elem >= 0 && elem <= 2, "bad GEMM plan query (elem=%d)", elem);
+  NDMPS_REQUIRE(mis_a >= 0 && mis_b >= 0 && mis_c >= 0, "a misalignment is a byte count");
+  const ndmps::GemmElem e = (ndmps::GemmElem)elem;
+  const char* why = ndmps::gemm_refusal(e, transA, transB, m, n, k, lda, ldb, ldc);
+  NDMPS_REQUIRE(!why, "%s", why);
+  const ndmps::GemmPlan p = ndmps::gemm_plan(e, transA, transB, m, n, k, lda, ldb, ldc, mis_a, mis_b, mis_c, guarded != 0);
+  const int64_t out[NDMPS_GEMM_PLAN_SLOTS] = {p.bm,      p.bn,      p.vec,    p.va,      p.vb,         p.grid_x,  p.grid_y,
+                                              p.inner_a, p.inner_b, p.vec_in, p.vec_out, p.transposes, p.launches};
+  std::copy(out, out + NDMPS_GEMM_PLAN_SLOTS, h_out);
+  return NDMPS_OK;
 }
 
 // ----------------------------------------------------------------------------------
@@ -714,32 +746,16 @@ extern "C" int ndmps_sgemm_indexed_batched(int batch, int64_t m, int64_t n, int6
   NDMPS_REQUIRE((d_a_row == nullptr) == (d_a_col == nullptr) && (d_c_row == nullptr) == (d_c_col == nullptr),
                 "offset tables come in (row, column) pairs");
   NDMPS_REQUIRE(ldb >= n && (d_a_row || lda >= k) && (d_c_row || ldc >= n), "leading dimension too small");
-  if (m == 0 || n == 0) return NDMPS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  GemmIndex ix{d_a_row, d_a_col, d_c_row, d_c_col, gemm_guarded_env()};
-  const uintptr_t al = 16;
-  bool vec = ldb % 4 == 0 && k % 4 == 0 && n % 4 == 0 && (d_a_row ? a_vec4 != 0 : lda % 4 == 0);
-  for (int z = 0; z < batch; ++z) vec = vec && (uintptr_t)bp.a[z] % al == 0 && (uintptr_t)bp.b[z] % al == 0;
-  const dim3 block(256);
-  if (n <= 64 || m <= 64) {
-    const dim3 grid((unsigned)ndmps::ceil_div(m, 64), (unsigned)ndmps::ceil_div(n, 64), (unsigned)batch);
-    if (vec)
-      hipLaunchKernelGGL((gemm_batched_kernel<float, 64, 64, 2, 2, false, false, true, true>), grid, block, 0, s, m, n, k,
-                         bp, lda, ldb, ldc, ix);
-    else
-      hipLaunchKernelGGL((gemm_batched_kernel<float, 64, 64, 2, 2, false, false, false, true>), grid, block, 0, s, m, n,
-                         k, bp, lda, ldb, ldc, ix);
-  } else {
-    const dim3 grid((unsigned)ndmps::ceil_div(m, 128), (unsigned)ndmps::ceil_div(n, 128), (unsigned)batch);
-    if (vec)
-      hipLaunchKernelGGL((gemm_batched_kernel<float, 128, 128, 2, 2, false, false, true, true>), grid, block, 0, s, m, n,
-                         k, bp, lda, ldb, ldc, ix);
-    else
-      hipLaunchKernelGGL((gemm_batched_kernel<float, 128, 128, 2, 2, false, false, false, true>), grid, block, 0, s, m,
-                         n, k, bp, lda, ldb, ldc, ix);
+  int64_t mis_a = 0, mis_b = 0;
+  for (int z = 0; z < batch; ++z) {
+    mis_a |= gemm_misalignment(bp.a[z]);
+    mis_b |= gemm_misalignment(bp.b[z]);
   }
-  NDMPS_LAUNCH_CHECK();
-  return NDMPS_OK;
+  const ndmps::GemmPlan plan =
+      ndmps::gemm_plan_indexed(m, n, k, lda, ldb, d_a_row != nullptr, a_vec4 != 0, mis_a, mis_b, gemm_guarded_env() != 0);
+  if (plan.launches == 0) return NDMPS_OK;
+  GemmIndex ix{d_a_row, d_a_col, d_c_row, d_c_col, plan.guarded};
+  return launch_gemm_indexed(plan, m, n, k, nullptr, lda, nullptr, ldb, nullptr, ldc, ix, (hipStream_t)stream, &bp, batch);
 }
 
 // The first projection of the fused sweep for 64 gathered columns, as a stream (proj64_stream_kernel): C[b] (m x n,

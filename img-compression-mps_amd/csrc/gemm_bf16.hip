@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -26,6 +27,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int CHUNKS = BK / 8;  // 16-byte chunks per LDS row
+static_assert(BM == ndmps::kGemmBf16Tile && BN == ndmps::kGemmBf16Tile, "the plan's tile is the kernel's");
 
 __device__ __forceinline__ bf16x8 zero8() {
   bf16x8 z;
@@ -170,10 +172,9 @@ extern "C" int ndmps_gemm_bf16(int transB, int64_t m, int64_t n, int64_t k, cons
                                const void* d_B, int64_t ldb, void* d_C, int64_t ldc, void* d_ws, int64_t ws_bytes,
                                ndmps_stream_t stream) {
   NDMPS_REQUIRE(d_A && d_B && d_C, "NULL GEMM operand");
-  NDMPS_REQUIRE(m > 0 && n > 0 && k > 0, "bad GEMM extents m=%lld n=%lld k=%lld", (long long)m, (long long)n,
-                (long long)k);
-  NDMPS_REQUIRE(lda >= k && ldc >= n && ldb >= (transB ? k : n), "leading dimension smaller than a row");
-  NDMPS_REQUIRE(ndmps::ceil_div(m, BM) < 65536 * 32768LL, "too many row tiles");
+  const char* why = ndmps::gemm_refusal(ndmps::GemmElem::BF16, 0, transB, m, n, k, lda, ldb, ldc);
+  NDMPS_REQUIRE(!why, "%s (m=%lld n=%lld k=%lld lda=%lld ldb=%lld ldc=%lld)", why, (long long)m, (long long)n,
+                (long long)k, (long long)lda, (long long)ldb, (long long)ldc);
   hipStream_t s = (hipStream_t)stream;
   const bf16* Bt = (const bf16*)d_B;
   int64_t ldbt = ldb;
@@ -188,16 +189,19 @@ extern "C" int ndmps_gemm_bf16(int transB, int64_t m, int64_t n, int64_t k, cons
     Bt = (const bf16*)d_ws;
     ldbt = k;
   }
-  const int vec_in = (lda % 8 == 0 && ldbt % 8 == 0 && ((uintptr_t)d_A % 16) == 0 && ((uintptr_t)Bt % 16) == 0) ? 1 : 0;
-  const int vec_out = (ldc % 8 == 0 && ((uintptr_t)d_C % 16) == 0) ? 1 : 0;
+  // the kernel reads the transposed copy where there is one: its alignment decides, not d_B's
+  const ndmps::GemmPlan plan =
+      ndmps::gemm_plan(ndmps::GemmElem::BF16, 0, transB, m, n, k, lda, ldb, ldc, (int64_t)((uintptr_t)d_A % 64),
+                       (int64_t)((uintptr_t)Bt % 64), (int64_t)((uintptr_t)d_C % 64), false);
   // grid.y is limited to 65535: fold very tall problems into several launches
   const int64_t row_tiles = ndmps::ceil_div(m, BM);
-  for (int64_t t0 = 0; t0 < row_tiles; t0 += 65535) {
-    const int64_t tiles = std::min<int64_t>(65535, row_tiles - t0);
+  for (int64_t l = 0; l < plan.launches; ++l) {
+    const int64_t t0 = l * ndmps::kGemmBf16MaxRowTiles;
+    const int64_t tiles = std::min<int64_t>(ndmps::kGemmBf16MaxRowTiles, row_tiles - t0);
     const int64_t r0 = t0 * BM;
-    hipLaunchKernelGGL(gemm_bf16_kernel, dim3((unsigned)ndmps::ceil_div(n, BN), (unsigned)tiles), dim3(256), 0, s,
+    hipLaunchKernelGGL(gemm_bf16_kernel, dim3((unsigned)plan.grid_x, (unsigned)tiles), dim3(256), 0, s,
                        (const bf16*)d_A + r0 * lda, lda, Bt, ldbt, (bf16*)d_C + r0 * ldc, ldc, std::min(m - r0, tiles * BM),
-                       n, k, vec_in, vec_out);
+                       n, k, plan.vec_in, plan.vec_out);
   }
   NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;

@@ -199,6 +199,22 @@ int64_t ndmps_gemm_bf16_workspace_bytes(int transB, int64_t n, int64_t k);
 int ndmps_gemm_bf16(int transB, int64_t m, int64_t n, int64_t k, const void* d_A, int64_t lda,
                     const void* d_B, int64_t ldb, void* d_C, int64_t ldc, void* d_ws, int64_t ws_bytes,
                     ndmps_stream_t stream);
+/* The plan a dense product would launch by, for tests and tools: host arithmetic only, no GPU call; ndmps_sgemm,
+ * ndmps_dgemm, their _batched twins and ndmps_gemm_bf16 launch by the same plan.  elem: 0 fp32, 1 bf16, 2 fp64 (bf16
+ * takes transA == 0 only).  mis_a, mis_b, mis_c: the operands' addresses modulo 64, in bytes (a batch: the bitwise OR
+ * over its members; bf16 with transB == 0: mis_b is the workspace's, where the transposed copy is read from).
+ * guarded: whether NDMPS_GEMM_GUARDED is set (the query does not read the environment).  Shapes the entry would
+ * refuse are refused (NDMPS_EINVAL).  h_out receives NDMPS_GEMM_PLAN_SLOTS values:
+ *    0 bm   1 bn        (block tile; 0 0 for an empty fp32 / fp64 product)
+ *    2 vec              (fp32 / fp64: the launcher's test for whole aligned quads in both operands)
+ *    3 va   4 vb        (what the kernel stages in quads: vec and bm * 16 / 256 resp. bn * 16 / 256 a multiple of 4)
+ *    5 grid_x   6 grid_y  (fp32 / fp64: row blocks, column blocks; bf16: column blocks, row blocks of the first launch)
+ *    7 inner_a  8 inner_b (row / column blocks whose full k-tiles come by the straight-line fetch: 0 under guarded)
+ *    9 vec_in  10 vec_out  11 transposes   (bf16: 16-byte loads, 16-byte stores, a (k, n) right operand copied first)
+ *   12 launches           (0: m == 0 or n == 0, nothing runs; bf16: one per 65535 row tiles) */
+#define NDMPS_GEMM_PLAN_SLOTS 13
+int ndmps_gemm_plan_query(int elem, int transA, int transB, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb,
+                          int64_t ldc, int64_t mis_a, int64_t mis_b, int64_t mis_c, int guarded, int64_t* h_out);
 /* The same for `batch` matrices of one shape in ONE launch (m >= 256 and n >= 128, or 64 <= n < 128 with at least
  * two matrices: _workspace_bytes returns 0 for shapes without a group-wide launch; what a lockstep group of
  * volumes needs at a site of the sweep, core/ndmps.py:74 per volume in the reference): h_A is a HOST array of
