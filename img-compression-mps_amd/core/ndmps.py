@@ -1244,6 +1244,88 @@ class NDMPS:
         out.sweep_spectra = None if spec is None else [None if s is None else np.array(s, copy=True) for s in spec]
         return out
 
+    # ------------------------------------------------------- elementwise product on the cores (core/hadamard.py)
+    def _hadamard_sketch(self, other, ell, R) -> DeviceMPS:
+        """The unrounded sketched chain of ``self * other`` (csrc/hadamard.hip): fp64, left-orthonormal up to its last
+        site, bonds ``r_k <= ell[k]``; ``ell`` the sketch bonds and ``R`` the random cores of core/hadamard.py (host
+        fp64 arrays).  The zero product comes back as bond-1 zero cores.  ValueError when the workspace would exceed
+        ``hadamard.WS_LIMIT_BYTES``."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import hadamard as _hd
+        from . import lincomb as _lc
+
+        a, b = self.mps, other.mps
+        L, dims, device = a.L, a.dims, a.device
+        c_dims, c_ba, c_bb = _lib.i64_array(dims), _lib.i64_array(a.bonds), _lib.i64_array(b.bonds)
+        c_ell = _lib.i64_array(ell)
+        out_off = (C.c_int64 * (L + 1))()
+        ws_bytes = C.c_int64(0)
+        total = _lib.check(lib.ndmps_hadamard_layout(L, c_dims, c_ba, c_bb, c_ell, out_off, C.byref(ws_bytes)))
+        _hd.check_workspace(ws_bytes.value)
+        table = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
+        ranks = (C.c_int64 * (L + 1))()
+        with torch.cuda.device(device):
+            arena = torch.empty(max(int(total), 1), dtype=torch.float64, device=device)
+            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
+            with _span("hadamard"):
+                rc = _lib.check(lib.ndmps_hadamard_sketch(
+                    L, c_dims, c_ba, _lc.dtype_code(a.dtype), a._core_ptrs(), c_bb, _lc.dtype_code(b.dtype),
+                    b._core_ptrs(), c_ell, table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(), arena.numel(),
+                    ranks, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            del ws
+            if rc > 0:  # the zero product
+                return DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims], _trusted=True)
+        r = [int(v) for v in ranks]
+        return DeviceMPS([arena[out_off[k]: out_off[k] + r[k] * dims[k] * r[k + 1]].view(r[k], dims[k], r[k + 1])
+                          for k in range(L)], _trusted=True)
+
+    def multiply(self, other, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0, dtype=None) -> "NDMPS":
+        """
+        The elementwise (Hadamard) product ``to_tensor() * other.to_tensor()`` as a new object, computed on the cores
+        (csrc/hadamard.hip, core/hadamard.py): mask x volume, squares, windows.  No volume is formed, and neither is the
+        product chain of bond ``chi_a chi_b``: a random chain of bond ``max_bond + oversample`` sketches it down
+        ("randomise then orthogonalise" TT rounding), and the sketched chain is rounded like ``recompress`` (same
+        ``cutoff`` / ``max_bond`` / ``dtype``, gauge and ``sweep_spectra``; the storage floor is relative to the norm of
+        the sketched product).  ``oversample=None`` is ``max(8, max_bond)``; the random cores are drawn on the host
+        from ``numpy.random.default_rng(seed)``, so the same seed gives the same bits.  ``max_bond=None`` takes the
+        sketch bonds ``chi_a chi_b``: the exact product, nothing random.  A zero product is the zero MPS, as
+        ``linear_combination`` returns it.  ``a * b`` with two objects still raises TypeError (``*`` is scaling by a
+        number): the product needs ``max_bond`` for anything but small bonds, so it is a method.  No counterpart in the
+        reference.
+
+        Raises TypeError for a non-NDMPS operand; ValueError for objects that differ in qubit_size, shape, mode,
+        device or site dims, for DCT mode (a product of coefficient volumes is not the product of the volumes), for a
+        sketch bond above 512 (``max_bond + oversample`` must be <= 512; without ``max_bond``: pass ``max_bond``), for a
+        workspace above 2 GiB (recompress the inputs first), for ``oversample < 0``, a non-integer seed and the
+        ``dtype`` / ``cutoff`` / ``max_bond`` errors of ``linear_combination``.
+        """
+        torch = _torch()
+        from . import hadamard as _hd
+        from . import lincomb as _lc
+
+        if not isinstance(other, NDMPS):
+            raise TypeError(f"multiply takes an NDMPS, not {type(other).__name__}")
+        max_bond, oversample, seed = _hd.check_args(max_bond, cutoff, oversample, seed)
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
+            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
+        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
+                                   dims=o.mps.dims) for o in (self, other)])
+        if self.mode == "DCT":
+            raise ValueError("DCT mode stores DCT coefficients: their product is not the product of the volumes")
+        dims = self.mps.dims
+        ell = _hd.sketch_bonds(dims, self.mps.bonds, other.mps.bonds, max_bond, oversample)
+        sketched = self._hadamard_sketch(other, ell, _hd.sketch_cores(dims, ell, seed))
+        scale = float(torch.linalg.vector_norm(sketched.cores[-1]))
+        if dtype is None:
+            codes = [_lc.dtype_code(self.mps.dtype), _lc.dtype_code(other.mps.dtype)]
+            dtype = torch.float64 if _lc.work_is_f64(codes) else torch.float32
+        return self._round_chains([sketched], [1.0], cutoff, max_bond, dtype, scale)
+
+    def square(self, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0, dtype=None) -> "NDMPS":
+        """``multiply(self, ...)``: the voxelwise square."""
+        return self.multiply(self, max_bond=max_bond, cutoff=cutoff, oversample=oversample, seed=seed, dtype=dtype)
+
     # ------------------------------------------------------- Gram matrix and PCA of a series (core/series.py)
     @staticmethod
     def _series_args(objs, others):

@@ -681,6 +681,42 @@ int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dim
                       ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Elementwise product of two chains by a randomised sketch (no reference counterpart; core/hadamard.py,
+ * csrc/hadamard.hip).  Both chains have the L site dims h_dims; h_bonds_a / h_bonds_b: their L + 1 bonds (outer ones 1,
+ * at most 4096); h_ell: the L + 1 sketch bonds l_k, l_0 = l_L = 1 and 1 <= l_k <= min(512, chi_{a,k} chi_{b,k}).
+ * ndmps_hadamard_layout: returns the element count of the fp64 output arena; h_out_off (L + 1): site k starts at
+ * element h_out_off[k] and has the capacity l_k d_k l_{k+1}; the sketch cores R_k (l_k, d_k, l_{k+1}) are laid out the
+ * same way in h_R.  *h_ws_bytes, with m_k = chi_{a,k} chi_{b,k} and every piece rounded up to 256 bytes: 8 times
+ *     sum_k l_k d_k l_{k+1}  (R)  +  sum_{inner k, l_k < m_k} l_k m_k  (environments)  +  max_k l_k d_k m_{k+1}  (Y of the
+ *     environment pass and X of the forward pass share it: they are never live together)  +  max_k l_k m_k  (M)
+ *     + 2 max_k l_k d_k l_{k+1}  (S, Q)  +  2 lmax^2 + lmax  (G, V, w)
+ * plus ndmps_syevj_workspace_bytes(lmax) and, when some bond exceeds 64, both chains' cores in fp64 and
+ * max_k l_k chi_{a,k} d_k chi_{b,k+1} doubles.
+ * ndmps_hadamard_sketch: the left-orthonormal fp64 chain of bonds h_ranks[k] <= l_k that sketches the product chain
+ * (site k written contiguously as (r_k, d_k, r_{k+1}) at h_out_off[k]).  code_*: storage of a chain's cores (0 fp32,
+ * 1 bf16, 2 fp64); h_cores_*: L device pointers; h_R: r_len = the layout's element count HOST doubles.  Returns 0, or
+ * 1 when the product is zero (every h_ranks[k] = 1, d_out undefined).  Synchronises the stream.
+ * ndmps_hadamard_sandwich: the kernel family alone on one site, A (ca, d, ca2) and B (cb, d, cb2), n <= 512:
+ *   form 0 (forward):      d_out[rho d + i] (ca2 x cb2) = A[:, i, :]^T d_E[rho] B[:, i, :],          d_E: n matrices ca x cb
+ *   form 1 (environment):  d_out[rho] (ca x cb) = sum_i A[:, i, :] d_E[rho d + i] B[:, i, :]^T,      d_E: n d matrices ca2 x cb2
+ * row-major fp64, summed in fixed order.  With all four bonds <= 64 it is one launch and needs no workspace;
+ * otherwise d_ws holds 8 (ca d ca2 + cb d cb2 + n ca d cb2) bytes plus 768.  Only the ro x co elements of each
+ * result are written.
+ * Every argument error (NULL pointers, bad codes, outer bonds != 1, l_k > 512, a short arena or workspace) is
+ * NDMPS_EINVAL before anything is launched.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_hadamard_layout(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                              const int64_t* h_ell, int64_t* h_out_off, int64_t* h_ws_bytes);
+int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t* h_bonds_a, int code_a,
+                          const void* const* h_cores_a, const int64_t* h_bonds_b, int code_b,
+                          const void* const* h_cores_b, const int64_t* h_ell, const double* h_R, int64_t r_len,
+                          double* d_out, int64_t out_elems, int64_t* h_ranks, void* d_ws, int64_t ws_bytes,
+                          ndmps_stream_t stream);
+int ndmps_hadamard_sandwich(int form, int64_t ca, int64_t d, int64_t ca2, int64_t cb, int64_t cb2, int code_a,
+                            const void* d_core_a, int code_b, const void* d_core_b, int64_t n, const double* d_E,
+                            double* d_out, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
