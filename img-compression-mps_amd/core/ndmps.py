@@ -222,6 +222,28 @@ def _pooled_dct_basis(n, block, op, device, f64=False):
         return _POOL_DCT_CACHE[key]
 
 
+# ------------------------------------------------------------------------------------------------ on the cores
+def _check_result_dtype(dtype):
+    """The ``dtype`` argument of the operations on the cores: None or one of the three storage types."""
+    torch = _torch()
+    if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
+        raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
+
+
+def _check_compatible(objs):
+    """``lincomb.check_compatible`` over NDMPS objects: same qubit_size, shape, mode, device and site dims."""
+    from . import lincomb as _lc
+
+    _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
+                               dims=o.mps.dims) for o in objs])
+
+
+def _carve_cores(arena, out_off, bonds, dims):
+    """The cores ``(bonds[k], dims[k], bonds[k + 1])`` of an output arena as views: core k starts at ``out_off[k]``."""
+    return [arena[out_off[k]: out_off[k] + bonds[k] * d * bonds[k + 1]].view(bonds[k], d, bonds[k + 1])
+            for k, d in enumerate(dims)]
+
+
 # ------------------------------------------------------------------------------------------------ decode tail
 def _fused_tail_columns(dtype, dims):
     """Columns of the chain's last product that scatter straight into the C-order volume (the fused decode of fp32
@@ -1026,7 +1048,6 @@ class NDMPS:
         Raises ValueError for empty or mismatched inputs, a non-finite weight, ``cutoff < 0``, ``max_bond < 1``,
         objects that differ in qubit_size, shape, mode or device, or a summed bond above 4096.
         """
-        torch = _torch()
         from . import lincomb as _lc
 
         objs = list(objs)
@@ -1034,10 +1055,8 @@ class NDMPS:
             if not isinstance(o, NDMPS):
                 raise TypeError(f"linear_combination combines NDMPS objects, not {type(o).__name__}")
         w = _lc.check_args(len(objs), weights, cutoff, max_bond)
-        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
-            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
-        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
-                                   dims=o.mps.dims) for o in objs])
+        _check_result_dtype(dtype)
+        _check_compatible(objs)
         _lc.check_summed_bonds([o.mps.bonds for o in objs])
         scale = _lc.scale_of(w, [o.norm_value for o in objs])
         return objs[0]._round_chains([o.mps for o in objs], w, cutoff, max_bond, dtype, scale)
@@ -1078,8 +1097,7 @@ class NDMPS:
                     spectra.ctypes.data_as(_lib.p_f64), int(stride.value), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
             del ws
         r = [int(v) for v in out_bonds]
-        cores = [arena[out_off[j]: out_off[j] + r[j] * dims[j] * r[j + 1]].view(r[j], dims[j], r[j + 1])
-                 for j in range(L)]
+        cores = _carve_cores(arena, out_off, r, dims)
         if dtype == torch.bfloat16:
             cores = [c.to(torch.bfloat16) for c in cores]
         out = self._like(cores, norm=False)
@@ -1145,18 +1163,15 @@ class NDMPS:
                                                   arena.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
             del ws
         wide = [d * b for d, b in zip(mpo.bonds, mps.bonds)]
-        return DeviceMPS([arena[out_off[j]: out_off[j + 1]].view(wide[j], dims[j], wide[j + 1]) for j in range(L)],
-                         _trusted=True)
+        return DeviceMPS(_carve_cores(arena, out_off, wide, dims), _trusted=True)
 
     def _axis_rounded(self, mpo, axis, cutoff, max_bond, dtype) -> "NDMPS":
         """The operator applied along ``axis`` and rounded like ``recompress``; the storage floor is relative to
         ``mpo.opnorm * norm_value``, a bound on the result's norm."""
-        torch = _torch()
         from . import lincomb as _lc
 
         _lc.check_args(1, [1.0], cutoff, max_bond)
-        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
-            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
+        _check_result_dtype(dtype)
         wide = self._axis_apply(mpo, axis)
         return self._round_chains([wide], [1.0], cutoff, max_bond, dtype, mpo.opnorm * float(self.norm_value))
 
@@ -1277,8 +1292,7 @@ class NDMPS:
             if rc > 0:  # the zero product
                 return DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims], _trusted=True)
         r = [int(v) for v in ranks]
-        return DeviceMPS([arena[out_off[k]: out_off[k] + r[k] * dims[k] * r[k + 1]].view(r[k], dims[k], r[k + 1])
-                          for k in range(L)], _trusted=True)
+        return DeviceMPS(_carve_cores(arena, out_off, r, dims), _trusted=True)
 
     def multiply(self, other, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0, dtype=None) -> "NDMPS":
         """
@@ -1307,10 +1321,8 @@ class NDMPS:
         if not isinstance(other, NDMPS):
             raise TypeError(f"multiply takes an NDMPS, not {type(other).__name__}")
         max_bond, oversample, seed = _hd.check_args(max_bond, cutoff, oversample, seed)
-        if dtype is not None and dtype not in (torch.float32, torch.bfloat16, torch.float64):
-            raise ValueError("dtype must be None, torch.float32, torch.bfloat16 or torch.float64")
-        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
-                                   dims=o.mps.dims) for o in (self, other)])
+        _check_result_dtype(dtype)
+        _check_compatible((self, other))
         if self.mode == "DCT":
             raise ValueError("DCT mode stores DCT coefficients: their product is not the product of the volumes")
         dims = self.mps.dims
@@ -1339,8 +1351,7 @@ class NDMPS:
             if not isinstance(o, NDMPS):
                 raise TypeError(f"gram takes NDMPS objects, not {type(o).__name__}")
         _se.check_lists(len(objs), None if others is None else len(rows) - len(objs))
-        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
-                                   dims=o.mps.dims) for o in rows])
+        _check_compatible(rows)
         cols = objs if others is None else rows[len(objs):]
 
         def side(lst):
@@ -1650,16 +1661,13 @@ class NDMPS:
     def _region_series_objs(objs):
         """The checked list of a series call: TypeError for a non-NDMPS, ValueError for an empty list, objects that
         differ (``lincomb.check_compatible``) or an unknown shape."""
-        from . import lincomb as _lc
-
         objs = list(objs)
         for o in objs:
             if not isinstance(o, NDMPS):
                 raise TypeError(f"a series takes NDMPS objects, not {type(o).__name__}")
         if not objs:
             raise ValueError("a series needs at least one object")
-        _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
-                                   dims=o.mps.dims) for o in objs])
+        _check_compatible(objs)
         objs[0]._require_shape()
         return objs
 

@@ -18,6 +18,7 @@
 namespace {
 
 using ndmps::ceil_div;
+using ndmps::load_any;
 
 constexpr int kThreads = 256, kPerThread = 4, kTileElems = kThreads * kPerThread;
 constexpr int64_t kLdsDoubles = 4096;  // 32 KiB of LDS for one site's M
@@ -29,12 +30,6 @@ struct SiteTask {
   int64_t m_off;  // the site's M in the table, D f f D2 doubles
   int64_t total;  // elements of Z: D chi pre f post D2 chi2
 };
-
-__device__ __forceinline__ double load_any(const void* p, int code, int64_t i) {
-  if (code == 2) return ((const double*)p)[i];
-  if (code == 1) return (double)(float)((const __bf16*)p)[i];
-  return (double)((const float*)p)[i];
-}
 
 // TZ: the work type.  A task or tile outside its range does nothing.
 template <typename TZ>
@@ -120,7 +115,7 @@ int64_t ws_bytes_of(const Plan& p) {
   ndmps::Arena ar(nullptr, 0);
   ar.take<SiteTask>(p.L);
   ar.take<double>(p.m_total);
-  return ndmps::round_up(ar.used, 256) + 256;
+  return ar.query_bytes();
 }
 
 }  // namespace

@@ -56,6 +56,7 @@ struct Arena {
     return (T*)(base + off);
   }
   bool fits() const { return base != nullptr && used <= size; }  // every take() so far returned memory
+  int64_t query_bytes() const { return round_up(used, 256) + 256; }  // what a size query answers: room to align the base
 };
 
 constexpr int kNumCU = 256;  // MI355X
@@ -73,6 +74,14 @@ template <typename T>
 __device__ __forceinline__ T from_f64(double x) { return (T)(float)x; }
 template <>
 __device__ __forceinline__ double from_f64<double>(double x) { return x; }
+// element i of an array in the storage type of `code` (0 fp32, 1 bf16, 2 fp64)
+__device__ __forceinline__ double load_any(const void* p, int code, int64_t i) {
+  if (code == 2) return ((const double*)p)[i];
+  if (code == 1) return to_f64(((const __bf16*)p)[i]);
+  return to_f64(((const float*)p)[i]);
+}
+// dst[0 .. n) <- src widened to fp64; src is fp32 (code 0) or bf16 (code 1), both on the device (util.hip)
+int widen(const void* src, int code, int64_t n, double* dst, hipStream_t s);
 
 // accumulator of v_mfma_f64_16x16x4_f64
 typedef double f64x4 __attribute__((ext_vector_type(4)));

@@ -16,15 +16,11 @@
 //      s_0 = 0 at some bond: the product is zero.  The last site is X_{L-1}.
 //
 // The sandwich  out[t] (+)= op(A[:,i,:]) E[t] op(B[:,i,:])  is the hot path.  Resident route (all four bonds of the
-// site <= 64): the two-phase product of series_gram_resident_kernel (csrc/series.hip) on v_mfma_f64_16x16x4_f64, one
-// workgroup of four waves per rho and i (forward) or per lam with i ascending inside (environment: no atomics):
-//   LDS   Et  64 x 64 fp64  E transposed                         32 KiB
-//         Z   64 x 64 fp64  Z = E op(B_i), row-major             32 KiB      64 KiB: two workgroups per CU
-//   both with 512-byte rows whose 16-column blocks are XORed by the row's parity (series.hip: no bank conflict on the
-//   operand reads).  Phase 1: wave w forms column tile w of Z with E from LDS and the core of b from global memory;
-//   phase 2: wave w forms row tile w of the output with the core of a from global memory and Z from LDS.  Cores are
-//   read in their storage type (fp32, bf16, fp64; widening is exact) one phase ahead.  Bonds that are not multiples of
-//   16 are zero-padded in registers and LDS; tiles past the bonds are skipped and never stored.
+// site <= 64): the two-phase pair product of pair_product.h (the LDS images, the operand loader with its transposed
+// read for the environment form) and pair_product_step.inc (phase 1, Z, phase 2 of one i) on v_mfma_f64_16x16x4_f64,
+// one workgroup of four waves per rho and i (forward) or per lam with i ascending inside (environment: no atomics).
+// What is the sandwich's own: E comes from global memory and is transposed into LDS for every task and i, and the
+// result leaves by a guarded store (tiles past the bonds are skipped and never stored).
 // General route (some bond of the site > 64): the cores widened to fp64 once per call, then per site one ndmps_dgemm
 //   and ndmps_dgemm_batched over the tasks in chunks of ndmps_gemm_batched_max().
 // Nothing waits across workgroups; the order of every sum is fixed, so the same inputs give the same bits.
@@ -35,45 +31,18 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_product.h"
 
 namespace {
 
 using ndmps::Arena;
 using ndmps::f64x4;
 using ndmps::grid1d;
+using ndmps::widen;
 
-constexpr int kResident = 64;      // largest bond of the resident sandwich
-constexpr int kLd = 64;            // row length of the LDS images (doubles)
+constexpr int kResident = ndmps::kPairResident;  // largest bond of the resident sandwich
 constexpr int kMaxSketch = 512;    // largest sketch bond (order of the eigenproblems)
 constexpr double kFloor = 1e-7;    // SKETCH_FLOOR of core/hadamard.py
-
-// element (row, col) of a 64 x 64 LDS image: odd rows hold their 16-column blocks pairwise swapped
-__device__ __forceinline__ int img(int row, int col) { return row * kLd + (col ^ ((row & 1) << 4)); }
-
-// This lane's operands of one phase, q[ks] = op(core_i)[4 ks + lr][c], zero outside.
-//   kTrans == false:  op(core_i)[k][c] = core[k, i, c]   (k < chi, c < chi2)
-//   kTrans == true:   op(core_i)[k][c] = core[c, i, k]   (k < chi2, c < chi)
-// Branch-free per element (a lane outside reads element 0 and discards it).
-template <typename T, bool kTrans>
-__device__ __forceinline__ void load_operands_as(double (&q)[16], const T* __restrict__ core, int chi, int d, int chi2, int i,
-                                                 int lr, int c, bool active) {
-  const int klim = kTrans ? chi2 : chi;
-  const bool c_ok = active && c < (kTrans ? chi : chi2);
-  const int64_t base = kTrans ? ((int64_t)c * d + i) * chi2 + lr : ((int64_t)lr * d + i) * chi2 + c;
-  const int64_t step = kTrans ? (int64_t)4 : (int64_t)4 * d * chi2;
-  T raw[16];
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) raw[ks] = core[(c_ok && 4 * ks + lr < klim) ? base + ks * step : 0];
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) q[ks] = (c_ok && 4 * ks + lr < klim) ? ndmps::to_f64(raw[ks]) : 0.0;
-}
-template <bool kTrans>
-__device__ __forceinline__ void load_operands(double (&q)[16], const void* core, int code, int chi, int d, int chi2, int i,
-                                              int lr, int c, bool active) {
-  if (code == 2) load_operands_as<double, kTrans>(q, (const double*)core, chi, d, chi2, i, lr, c, active);
-  else if (code == 1) load_operands_as<__bf16, kTrans>(q, (const __bf16*)core, chi, d, chi2, i, lr, c, active);
-  else load_operands_as<float, kTrans>(q, (const float*)core, chi, d, chi2, i, lr, c, active);
-}
 
 struct SandwichArgs {
   const void* A;    // (ca, d, ca2) in storage type code_a
@@ -83,16 +52,23 @@ struct SandwichArgs {
   int ca, ca2, cb, cb2, d, n, code_a, code_b;
 };
 
-// kEnv == false: blockIdx.x = rho d + i,  out[rho d + i] = A_i^T E[rho] B_i
-// kEnv == true:  blockIdx.x = rho,        out[rho] = sum_i A_i E[rho d + i] B_i^T   (i ascending)
+// One workgroup's sandwich: E comes from global memory for every i, the step of one i is pair_product_step.inc, and
+// the result goes to out[task] by a guarded store.
+//   kEnv == false: blockIdx.x = rho d + i,  out[rho d + i] = A_i^T E[rho] B_i
+//   kEnv == true:  blockIdx.x = rho,        out[rho] = sum_i A_i E[rho d + i] B_i^T   (i ascending)
 template <bool kEnv>
 __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs g) {
+  using ndmps::pair_img;
+  constexpr int kLd = ndmps::kPairLd;
+  constexpr bool kTrans = kEnv;
   __shared__ double Et[kLd * kLd];
   __shared__ double Z[kLd * kLd];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
   const int d = g.d;
   const int64_t task = blockIdx.x;
   if (task >= (kEnv ? (int64_t)g.n : (int64_t)g.n * d)) return;
+  const void* B = g.B;
+  const int cb = g.cb, cb2 = g.cb2, code_b = g.code_b;
   // E is re x ce; the output ro x co
   const int re = kEnv ? g.ca2 : g.ca, ce = kEnv ? g.cb2 : g.cb;
   const int ro = kEnv ? g.ca : g.ca2, co = kEnv ? g.cb : g.cb2;
@@ -107,7 +83,7 @@ __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs 
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) acc[nt] = (f64x4){0.0, 0.0, 0.0, 0.0};
   double bq[16], aq[16];
-  load_operands<kEnv>(bq, g.B, g.code_b, g.cb, d, g.cb2, i0, lr, col, own1);
+  ndmps::pair_load_operands<kTrans>(bq, B, code_b, cb, d, cb2, i0, lr, col, own1);
 
   for (int i = i0; i < i1; ++i) {
     // ---- E of this task, transposed into Et: Et[k][m] = E[m][k], zero outside re x ce.  A wave's pass reads 16
@@ -122,47 +98,12 @@ __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs 
           const int k = 16 * kb + kk, m = 16 * mb + mm;
           const bool ok = k < ce && m < re;
           const double v = E[ok ? (int64_t)m * ce + k : 0];
-          Et[img(k, m)] = ok ? v : 0.0;
+          Et[pair_img(k, m)] = ok ? v : 0.0;
         }
     }
-    load_operands<kEnv>(aq, g.A, g.code_a, g.ca, d, g.ca2, i, lr, col, own2);
+    ndmps::pair_load_operands<kTrans>(aq, g.A, g.code_a, g.ca, d, g.ca2, i, lr, col, own2);
     __syncthreads();
-    // ---- phase 1: Z[:, 16 wave ..] = E op(B_i)[:, 16 wave ..]
-    f64x4 z[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) z[mt] = (f64x4){0.0, 0.0, 0.0, 0.0};
-    if (own1) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        if (ks < steps1) {
-          const int k = 4 * ks + lr;
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-            if (mt < tiles_re) z[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Et[img(k, 16 * mt + lc)], bq[ks], z[mt], 0, 0, 0);
-        }
-        if (ks & 1) __builtin_amdgcn_sched_barrier(0);  // at most eight LDS operands in flight: no spill
-      }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Z[img(16 * mt + lr + 4 * r, col)] = z[mt][r];
-    __syncthreads();
-    if (i + 1 < i1) load_operands<kEnv>(bq, g.B, g.code_b, g.cb, d, g.cb2, i + 1, lr, col, own1);
-    // ---- phase 2: out[16 wave .., :] += op(A_i)[16 wave .., :] Z
-    if (own2) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        if (ks < steps2) {
-          const int k = 4 * ks + lr;
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            if (nt < tiles_co) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[ks], Z[img(k, 16 * nt + lc)], acc[nt], 0, 0, 0);
-        }
-        if (ks & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    __syncthreads();  // Et and Z are rewritten by the next i
+#include "pair_product_step.inc"
   }
   double* out = g.out + task * (int64_t)ro * co;
 #pragma unroll
@@ -174,10 +115,6 @@ __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs 
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) widen_kernel(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
-}
 // Q (rows x r, row-major) columns divided by sqrt(w), in place
 __global__ void __launch_bounds__(256) cols_over_sqrt_kernel(double* __restrict__ Q, int64_t rows, int64_t r,
                                                              const double* __restrict__ w) {
@@ -199,15 +136,6 @@ int check_site(const Site& t, int64_t n) {
   NDMPS_REQUIRE(n <= kMaxSketch && n * t.d <= INT32_MAX / 2, "a sandwich takes at most %d matrices, got %lld", kMaxSketch, (long long)n);
   NDMPS_REQUIRE(t.code_a >= 0 && t.code_a <= 2 && t.code_b >= 0 && t.code_b <= 2, "bad dtype code (%d, %d)", t.code_a, t.code_b);
   NDMPS_REQUIRE(t.A && t.B, "NULL core");
-  return NDMPS_OK;
-}
-
-int widen(const void* src, int code, int64_t n, double* dst, hipStream_t s) {
-  if (code == 1)
-    hipLaunchKernelGGL(widen_kernel<__bf16>, dim3(grid1d(n)), dim3(256), 0, s, (const __bf16*)src, n, dst);
-  else
-    hipLaunchKernelGGL(widen_kernel<float>, dim3(grid1d(n)), dim3(256), 0, s, (const float*)src, n, dst);
-  NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
 
@@ -402,7 +330,7 @@ extern "C" int64_t ndmps_hadamard_layout(int L, const int64_t* h_dims, const int
     Arena ar(nullptr, 0);
     Buffers b;
     carve(p, ar, b);
-    *h_ws_bytes = ndmps::round_up(ar.used, 256) + 256;
+    *h_ws_bytes = ar.query_bytes();
   }
   return p.out_off[L];
 }

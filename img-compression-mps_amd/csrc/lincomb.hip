@@ -33,6 +33,7 @@ namespace {
 
 using ndmps::Arena;
 using ndmps::ceil_div;
+using ndmps::load_any;
 
 constexpr int kTile = 64, kTk = 16;
 
@@ -46,12 +47,6 @@ struct Task {
   int64_t brow, crow;  // projection launches: B = Pbase + brow r, C = Cbase + crow r, N = ldb = ldc = r
   int32_t a_code, b_code, transA, pad;
 };
-
-__device__ __forceinline__ double load_any(const void* p, int code, int64_t i) {
-  if (code == 2) return ((const double*)p)[i];
-  if (code == 1) return (double)(float)((const __bf16*)p)[i];
-  return (double)((const float*)p)[i];
-}
 
 // blockIdx.y = task, blockIdx.x = 64 x 64 output tile; 256 threads, 4 x 4 outputs each (rows ty + 16 i,
 // columns tx + 16 j).  A task or tile outside its range does nothing.
@@ -299,7 +294,7 @@ int lincomb_impl(const Plan& p, const int* h_codes, const void* const* h_cores, 
   Arena ar(d_ws, ws_bytes);
   Buffers b;
   carve(p, ar, b);
-  if (!d_ws || ar.used > ws_bytes) {
+  if (!ar.fits()) {
     ndmps::set_error("lincomb workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
     return NDMPS_EWORKSPACE;
   }
@@ -450,7 +445,7 @@ extern "C" int64_t ndmps_lincomb_layout(int K, int L, const int64_t* h_dims, con
     Arena ar(nullptr, 0);
     Buffers b;
     carve(p, ar, b);
-    *h_ws_bytes = ndmps::round_up(ar.used, 256) + 256;
+    *h_ws_bytes = ar.query_bytes();
   }
   if (h_spec_stride) *h_spec_stride = p.smax;
   return p.out_off[L];

@@ -26,7 +26,7 @@ using ndmps::ceil_div;
 using ndmps::round_up;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+using ndmps::f64x4;
 
 constexpr int kTileRows = 32;
 

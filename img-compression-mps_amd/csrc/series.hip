@@ -5,22 +5,12 @@
 //     E_{j+1} = sum_i  A_j[:, i, :]^T ( E_j B_j[:, i, :] ),        G[a, b] = E_L[0, 0]
 // (`E B` first: the other association of oracle.mps.mps_overlap and of ndmps_overlap_*).  Pairs are independent.
 //
-// Resident route (every inner bond of both lists <= 64): ONE launch, one workgroup of four waves per pair, all L sites.
-//   LDS   Et  64 x 64 fp64  E_j transposed, Et[k][m] = E_j[m][k]            32 KiB
-//         Z   64 x 64 fp64  Z_i = E_j B_j[:, i, :], row-major               32 KiB      64 KiB: two workgroups per CU
-//   Both images have 512-byte rows with the 16-column block index XORed by the row's parity.  An operand read of
-//   v_mfma_f64_16x16x4_f64 takes 16 consecutive doubles of four consecutive rows; ds_read_b64 resolves banks per half
-//   wave (two rows), and the XOR puts the odd row on the other 128-byte half of the bank row: no conflict.
-//   Per physical index i:  phase 1, wave w forms column tile w of Z_i (four row tiles, 16 registers) with E from LDS
-//   as the A operand and the core of b from GLOBAL memory as the B operand; phase 2, wave w accumulates row tile w of
-//   E_{j+1} (four column tiles, kept in accumulators over all i) with the core of a from global memory as the A
-//   operand and Z_i from LDS as the B operand.  Departure from the planned design: the cores are not staged through
-//   LDS.  With this split of the tiles every core element is the operand of exactly one wave, so a copy in LDS would
-//   be written once and read once; instead each lane loads its <= 16 operands of a phase into registers one phase
-//   ahead (the core of a during phase 1, the core of b of i + 1 during phase 2), in the storage type (fp32, bf16,
-//   fp64: widening is exact).  LDS operand reads are fenced in groups of eight so that they do not pile up in registers.  Bonds that are not multiples of 16 are zero-padded in registers and LDS; tiles past a
-//   pair's own bonds are skipped.  Order of summation is fixed (k ascending inside a product, i ascending), nothing
-//   is shared between workgroups, and nothing waits.
+// Resident route (every inner bond of both lists <= 64): ONE launch, one workgroup of four waves per pair, all L sites,
+//   on the two-phase pair product of pair_product.h (the LDS images Et and Z, the operand loader) and
+//   pair_product_step.inc (phase 1, Z, phase 2 of one physical index i), in the forward form: E_j stays in LDS as Et
+//   from site to site, a site's accumulators are transposed back into Et, and E_L[0, 0] is G[a, b].  Order of
+//   summation is fixed (k ascending inside a product, i ascending), nothing is shared between workgroups, and nothing
+//   waits.
 // General route (some inner bond > 64): every core widened to fp64 once, then per site and pair two products on
 //   ndmps_dgemm; when all chains of both lists have the same bonds the pairs go through ndmps_dgemm_batched in chunks
 //   of ndmps_gemm_batched_max().  The last product writes its 1 x 1 result into G.
@@ -29,16 +19,14 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_product.h"
 
 namespace {
 
 using ndmps::Arena;
 using ndmps::ceil_div;
 
-constexpr int kResident = 64;  // largest inner bond of the resident kernel
-constexpr int kLd = 64;        // row length of the LDS images (doubles)
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+constexpr int kResident = ndmps::kPairResident;  // largest inner bond of the resident kernel
 
 struct SeriesArgs {
   const void* const* cores_a;  // Ka x L
@@ -52,30 +40,13 @@ struct SeriesArgs {
   int Ka, Kb, L, symmetric;
 };
 
-// element (row, col) of a 64 x 64 LDS image: odd rows hold their 16-column blocks pairwise swapped
-__device__ __forceinline__ int img(int row, int col) { return row * kLd + (col ^ ((row & 1) << 4)); }
-
-// this lane's operands of one phase: core[4 ks + lr, i, col] for ks < 16, zero outside chi x chi2.  Branch-free per
-// element (a lane outside reads element 0 and discards it); the storage type is switched once per call.
-template <typename T>
-__device__ __forceinline__ void load_operands_as(double (&q)[16], const T* __restrict__ core, int chi, int d, int chi2, int i,
-                                                 int lr, int col, bool active) {
-  const bool col_ok = active && col < chi2;
-  const int64_t base = ((int64_t)lr * d + i) * chi2 + col, step = (int64_t)4 * d * chi2;
-  T raw[16];
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) raw[ks] = core[(col_ok && 4 * ks + lr < chi) ? base + ks * step : 0];
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) q[ks] = (col_ok && 4 * ks + lr < chi) ? ndmps::to_f64(raw[ks]) : 0.0;
-}
-__device__ __forceinline__ void load_operands(double (&q)[16], const void* core, int code, int chi, int d, int chi2, int i,
-                                              int lr, int col, bool active) {
-  if (code == 2) load_operands_as(q, (const double*)core, chi, d, chi2, i, lr, col, active);
-  else if (code == 1) load_operands_as(q, (const __bf16*)core, chi, d, chi2, i, lr, col, active);
-  else load_operands_as(q, (const float*)core, chi, d, chi2, i, lr, col, active);
-}
-
+// One workgroup per pair (a, b): E stays in LDS over all L sites, every site runs all its i through the step of
+// pair_product_step.inc, and E_L[0, 0] goes to G[a, b] and its mirror.
 __global__ void __launch_bounds__(256, 2) series_gram_resident_kernel(SeriesArgs g) {
+  using ndmps::f64x4;
+  using ndmps::pair_img;
+  constexpr int kLd = ndmps::kPairLd;
+  constexpr bool kTrans = false;
   const int a = (int)(blockIdx.x / (unsigned)g.Kb), b = (int)(blockIdx.x % (unsigned)g.Kb);
   if (a >= g.Ka || (g.symmetric && a > b)) return;
   __shared__ double Et[kLd * kLd];
@@ -90,64 +61,30 @@ __global__ void __launch_bounds__(256, 2) series_gram_resident_kernel(SeriesArgs
   __syncthreads();
 
   for (int j = 0; j < L; ++j) {
-    const int ca = ba[j], ca2 = ba[j + 1], cb = bb[j], cb2 = bb[j + 1], d = g.dims[j];
+    const int ca = ba[j], ca2 = ba[j + 1], cb = bb[j], cb2 = bb[j + 1], d = g.dims[j], i1 = d;
     const void* A = g.cores_a[(int64_t)a * L + j];
     const void* B = g.cores_b[(int64_t)b * L + j];
-    const int tiles_a = (ca + 15) >> 4, tiles_a2 = (ca2 + 15) >> 4, tiles_b2 = (cb2 + 15) >> 4;
-    const int steps_b = (cb + 3) >> 2, steps_a = (ca + 3) >> 2;
-    const bool own1 = wave < tiles_b2, own2 = wave < tiles_a2;  // this wave's tile of Z / of E' exists
+    // E_j is ca x cb, E_{j+1} ca2 x cb2
+    const int tiles_re = (ca + 15) >> 4, tiles_ro = (ca2 + 15) >> 4, tiles_co = (cb2 + 15) >> 4;
+    const int steps1 = (cb + 3) >> 2, steps2 = (ca + 3) >> 2;
+    const bool own1 = wave < tiles_co, own2 = wave < tiles_ro;  // this wave's tile of Z / of E' exists
     const int col = wave * 16 + lc;
 
     f64x4 acc[4];  // E_{j+1}: rows 16 wave + lr + 4 r, columns 16 nt + lc
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc[nt] = (f64x4){0.0, 0.0, 0.0, 0.0};
     double bq[16], aq[16];
-    load_operands(bq, B, code_b, cb, d, cb2, 0, lr, col, own1);
+    ndmps::pair_load_operands<kTrans>(bq, B, code_b, cb, d, cb2, 0, lr, col, own1);
 
-    for (int i = 0; i < d; ++i) {
-      load_operands(aq, A, code_a, ca, d, ca2, i, lr, col, own2);
-      // ---- phase 1: Z_i[:, 16 wave ..] = E_j B_j[:, i, 16 wave ..]
-      f64x4 z[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) z[mt] = (f64x4){0.0, 0.0, 0.0, 0.0};
-      if (own1) {
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-          if (ks < steps_b) {
-            const int k = 4 * ks + lr;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-              if (mt < tiles_a) z[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Et[img(k, 16 * mt + lc)], bq[ks], z[mt], 0, 0, 0);
-          }
-          if (ks & 1) __builtin_amdgcn_sched_barrier(0);  // at most eight LDS operands in flight: no spill
-        }
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Z[img(16 * mt + lr + 4 * r, col)] = z[mt][r];
-      __syncthreads();
-      if (i + 1 < d) load_operands(bq, B, code_b, cb, d, cb2, i + 1, lr, col, own1);
-      // ---- phase 2: E_{j+1}[16 wave .., :] += A_j[:, i, 16 wave ..]^T Z_i
-      if (own2) {
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-          if (ks < steps_a) {
-            const int k = 4 * ks + lr;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-              if (nt < tiles_b2) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq[ks], Z[img(k, 16 * nt + lc)], acc[nt], 0, 0, 0);
-          }
-          if (ks & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      __syncthreads();
+    for (int i = 0; i < i1; ++i) {
+      ndmps::pair_load_operands<kTrans>(aq, A, code_a, ca, d, ca2, i, lr, col, own2);
+#include "pair_product_step.inc"
     }
     // E_{j+1} transposed into Et (every entry: the padding is zero in the accumulators)
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Et[img(16 * nt + lc, 16 * wave + lr + 4 * r)] = acc[nt][r];
+      for (int r = 0; r < 4; ++r) Et[pair_img(16 * nt + lc, 16 * wave + lr + 4 * r)] = acc[nt][r];
     __syncthreads();
   }
   if (tid == 0) {
@@ -157,10 +94,6 @@ __global__ void __launch_bounds__(256, 2) series_gram_resident_kernel(SeriesArgs
   }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) widen_kernel(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
-}
 // G[b, a] <- G[a, b] for a < b (K x K)
 __global__ void __launch_bounds__(256) mirror_kernel(double* __restrict__ G, int64_t K) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < K * K; e += (int64_t)gridDim.x * 256) {
@@ -169,6 +102,7 @@ __global__ void __launch_bounds__(256) mirror_kernel(double* __restrict__ G, int
   }
 }
 using ndmps::grid1d;
+using ndmps::widen;
 
 enum { kRouteResident = 0, kRouteBatched = 1, kRoutePerPair = 2 };
 
@@ -253,15 +187,6 @@ void carve(const Plan& p, const int* codes_a, const int* codes_b, bool symmetric
   b.E[0] = ar.take<double>(p.emax * p.chunk);
   b.E[1] = ar.take<double>(p.emax * p.chunk);
   b.Z = ar.take<double>(p.zmax * p.chunk);
-}
-
-int widen(const void* src, int code, int64_t n, double* dst, hipStream_t s) {
-  if (code == 1)
-    hipLaunchKernelGGL(widen_kernel<__bf16>, dim3(grid1d(n)), dim3(256), 0, s, (const __bf16*)src, n, dst);
-  else
-    hipLaunchKernelGGL(widen_kernel<float>, dim3(grid1d(n)), dim3(256), 0, s, (const float*)src, n, dst);
-  NDMPS_LAUNCH_CHECK();
-  return NDMPS_OK;
 }
 
 int run_resident(const Plan& p, int symmetric, const int* codes_a, const void* const* cores_a, const int* codes_b,
@@ -384,7 +309,7 @@ extern "C" int64_t ndmps_series_gram_workspace_bytes(int Ka, int Kb, int L, cons
   Arena ar(nullptr, 0);
   Buffers b;
   carve(p, nullptr, nullptr, false, ar, b);
-  return ndmps::round_up(ar.used, 256) + 256;
+  return ar.query_bytes();
 }
 
 extern "C" int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
@@ -412,7 +337,7 @@ extern "C" int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int
   Arena ar(d_ws, ws_bytes);
   Buffers b;
   carve(p, h_codes_a, h_codes_b, symmetric, ar, b);
-  if (!d_ws || ar.used > ws_bytes) {
+  if (!ar.fits()) {
     ndmps::set_error("series workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
     return NDMPS_EWORKSPACE;
   }

@@ -277,3 +277,20 @@ int Turn::end() {
   return NDMPS_OK;
 }
 }  // namespace ndmps
+
+// ---- widening copy of a core to fp64 (the general routes of series.hip and hadamard.hip)
+namespace {
+template <typename T>
+__global__ void __launch_bounds__(256) widen_kernel(const T* __restrict__ x, int64_t n, double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = ndmps::to_f64(x[i]);
+}
+}  // namespace
+
+int ndmps::widen(const void* src, int code, int64_t n, double* dst, hipStream_t s) {
+  if (code == 1)
+    hipLaunchKernelGGL(widen_kernel<__bf16>, dim3(grid1d(n)), dim3(256), 0, s, (const __bf16*)src, n, dst);
+  else
+    hipLaunchKernelGGL(widen_kernel<float>, dim3(grid1d(n)), dim3(256), 0, s, (const float*)src, n, dst);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
