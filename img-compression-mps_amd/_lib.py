@@ -109,6 +109,11 @@ SIGNATURES = {
                                         p_f64, i64, vp, i64, p_i64, vp, i64, vp]),
     "ndmps_hadamard_sandwich": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, C.c_int, vp, C.c_int, vp, i64, vp, vp, vp, i64,
                                           vp]),
+    "ndmps_sumsketch_layout": (i64, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64, p_i64, p_i64]),
+    "ndmps_sumsketch_sketch": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_f64, p_i64, p_f64,
+                                         i64, vp, i64, p_i64, p_int, vp, i64, vp]),
+    "ndmps_sumsketch_step": (C.c_int, [C.c_int, C.c_int, i64, p_i64, p_i64, p_int, C.POINTER(vp), i64, i64, vp, vp, vp, vp,
+                                       vp, i64, vp]),
     "ndmps_series_gram_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_series_gram_route": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_series_gram": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_i64, p_int,

@@ -1338,6 +1338,142 @@ class NDMPS:
         """``multiply(self, ...)``: the voxelwise square."""
         return self.multiply(self, max_bond=max_bond, cutoff=cutoff, oversample=oversample, seed=seed, dtype=dtype)
 
+    # ------------------------------------------------------- sums of many objects by a sketch (core/sumsketch.py)
+    @staticmethod
+    def _sum_sketch(objs, w, ell, R) -> list:
+        """The unrounded sketched chains of ``sum_a w[j, a] * objs[a]`` for every row j (csrc/sumsketch.hip): fp64,
+        left-orthonormal up to their last sites, bonds ``r_k <= ell[k]``.  ``objs``: the frames some row uses; a zero
+        output comes back as bond-1 zero cores.  ValueError when the workspace would exceed
+        ``hadamard.WS_LIMIT_BYTES``."""
+        torch = _torch()
+        lib = _lib.load()
+        from . import hadamard as _hd
+        from . import lincomb as _lc
+
+        first = objs[0].mps
+        T, K, L, dims, device = len(objs), int(w.shape[0]), first.L, first.dims, first.device
+        c_dims = _lib.i64_array(dims)
+        c_bonds = _lib.i64_array([b for o in objs for b in o.mps.bonds])
+        c_ell = _lib.i64_array(ell)
+        out_off = (C.c_int64 * (L + 1))()
+        ws_bytes = C.c_int64(0)
+        total = _lib.check(lib.ndmps_sumsketch_layout(T, K, L, c_dims, c_bonds, c_ell, out_off, C.byref(ws_bytes)))
+        _hd.check_workspace(ws_bytes.value)
+        table = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
+        codes = (C.c_int * T)(*[_lc.dtype_code(o.mps.dtype) for o in objs])
+        ptrs = (C.c_void_p * (T * L))(*[c.data_ptr() for o in objs for c in o.mps.cores])
+        weights = np.ascontiguousarray(w, dtype=np.float64)
+        ranks = (C.c_int64 * (K * (L + 1)))()
+        zero = (C.c_int * K)()
+        chain = int(out_off[L])
+        with torch.cuda.device(device):
+            arena = torch.empty(max(int(total), 1), dtype=torch.float64, device=device)
+            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
+            with _span("sumsketch"):
+                _lib.check(lib.ndmps_sumsketch_sketch(
+                    T, K, L, c_dims, c_bonds, codes, ptrs, weights.ctypes.data_as(_lib.p_f64), c_ell,
+                    table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(), arena.numel(), ranks, zero,
+                    ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            del ws
+            chains = []
+            for j in range(K):
+                if zero[j]:
+                    chains.append(DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims],
+                                            _trusted=True))
+                    continue
+                r = [int(v) for v in ranks[j * (L + 1):(j + 1) * (L + 1)]]
+                chains.append(DeviceMPS(_carve_cores(arena[j * chain:(j + 1) * chain], out_off, r, dims), _trusted=True))
+        return chains
+
+    @staticmethod
+    def linear_combinations(objs, weights, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0,
+                            dtype=None) -> list:
+        """
+        The TT roundings of ``sum_a weights[j, a] * objs[a]`` for every row j of ``weights`` (``(K, T)``; a 1-D array
+        of length T is one row) as a list of K new objects, computed on the cores by a randomised sketch
+        (csrc/sumsketch.hip, core/sumsketch.py).  Unlike ``linear_combination`` there is no limit on the summed bond
+        ``sum_a chi_a``: a random chain of bond ``max_bond + oversample`` sketches the formal sum chain down frame by
+        frame ("randomise then orthogonalise" TT rounding), the cost is linear in T, no eigenproblem exceeds
+        ``max_bond + oversample``, and the right environments are shared by all K rows.  The sketched chains are
+        rounded like ``multiply``'s (same ``cutoff`` / ``max_bond`` / ``dtype``, gauge, ``norm=False``,
+        ``boundary_list``, ``norm_value`` and ``sweep_spectra``; the storage floor is relative to the norm of the
+        sketched sum).  ``oversample=None`` is ``max(8, max_bond)``; the random cores are drawn on the host from
+        ``numpy.random.default_rng(seed)`` and every sum over frames runs in ascending order without atomics, so the
+        same arguments give the same bits.  ``max_bond=None`` takes the sketch bonds equal to the summed bonds: the
+        exact sum, allowed while they are <= 512.  In DCT mode the combination is taken on the coefficients.  A frame
+        whose weights are zero in every row is never read, and a zero entry is skipped in that row; a row of zeros,
+        or a sum that vanishes, gives the zero MPS of ``linear_combination``.  ``dtype=None`` is fp64 if any input is
+        fp64 and fp32 otherwise.  No counterpart in the reference.
+
+        Raises TypeError for a non-NDMPS; ValueError for an empty list, weights whose last dimension is not T or with
+        more than two dimensions, a non-finite weight, ``cutoff < 0``, ``max_bond < 1``, ``oversample < 0``, a bad
+        seed, objects that differ in qubit_size, shape, mode, device or site dims, a sketch bond above 512 or a
+        workspace above 2 GiB (recompress the inputs first).  Objects whose bonds are all <= 64 run in the resident
+        kernels; an object with a larger bond takes a general route through fp64 dense products.
+        """
+        torch = _torch()
+        from . import hadamard as _hd
+        from . import lincomb as _lc
+        from . import sumsketch as _ss
+
+        objs = list(objs)
+        for o in objs:
+            if not isinstance(o, NDMPS):
+                raise TypeError(f"linear_combinations combines NDMPS objects, not {type(o).__name__}")
+        w = _ss.check_weights(len(objs), weights)
+        max_bond, oversample, seed = _hd.check_args(max_bond, cutoff, oversample, seed)
+        _check_result_dtype(dtype)
+        _check_compatible(objs)
+        first = objs[0]
+        dims = first.mps.dims
+        if dtype is None:
+            dtype = torch.float64 if _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]) else torch.float32
+        used = _ss.used_frames(w)
+        if used:
+            frames = [objs[a] for a in used]
+            bond_lists = [o.mps.bonds for o in frames]
+            ell = _ss.sketch_bonds(dims, bond_lists, max_bond, oversample)
+            chains = NDMPS._sum_sketch(frames, w[:, used], ell, _hd.sketch_cores(dims, ell, seed))
+        else:
+            device = first.mps.device
+            chains = [DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims], _trusted=True)
+                      for _ in range(w.shape[0])]
+        out = []
+        for sketched in chains:
+            scale = float(torch.linalg.vector_norm(sketched.cores[-1]))
+            out.append(first._round_chains([sketched], [1.0], cutoff, max_bond, dtype, scale))
+        return out
+
+    @staticmethod
+    def pca_sketched(objs, n_components=None, max_bond=None, center: bool = True, cutoff: float = 0.0, oversample=None,
+                     seed: int = 0, dtype=None):
+        """
+        ``pca`` with its last step replaced: ``G = gram(objs)``, the weights (``core.series.pca_weights``), the kept
+        set, the signs and ``explained_variance`` are those of ``pca``; the components and, when ``center``, the mean
+        come from ONE ``linear_combinations`` call with the weight matrix ``[W[:, 0], ..., W[:, r-1], (1/T, ..., 1/T)]``,
+        so a series of any length is accepted and all outputs share the right environments.  ``max_bond``, ``cutoff``,
+        ``oversample``, ``seed`` and ``dtype`` as in ``linear_combinations``.  Returns a ``SeriesPCA``.
+        """
+        torch = _torch()
+        from . import hadamard as _hd
+        from . import lincomb as _lc
+        from . import series as _se
+
+        objs = list(objs)
+        _se.check_components(n_components)
+        _hd.check_args(max_bond, cutoff, oversample, seed)
+        _check_result_dtype(dtype)
+        G = NDMPS.gram(objs)
+        T = len(objs)
+        f64 = dtype == torch.float64 or (dtype != torch.float32
+                                         and _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]))
+        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(f64))
+        rows = [W[:, k] for k in range(len(sigma))] + ([np.full(T, 1.0 / T)] if center else [])
+        outs = NDMPS.linear_combinations(objs, np.stack(rows), max_bond=max_bond, cutoff=cutoff, oversample=oversample,
+                                         seed=seed, dtype=dtype) if rows else []
+        components, mean = (outs[:-1], outs[-1]) if center else (outs, None)
+        return _se.SeriesPCA(sigma, _se.explained_variance(sigma, T, center), U * sigma[None, :], W, components, mean)
+
     # ------------------------------------------------------- Gram matrix and PCA of a series (core/series.py)
     @staticmethod
     def _series_args(objs, others):

@@ -11,7 +11,7 @@
 //   2. forward, k = 0 .. L-2, carrying X_k ((r_k d_k) x m_{k+1}), M_0 = [1]:
 //        X_k[(rho,i)] (chi_a' x chi_b') = A_k[:,i,:]^T M_k[rho] B_k[:,i,:]        the sandwich, forward form
 //        S = X_k Wt_{k+1}^T   ((r_k d_k) x l_{k+1};  S = X_k where l_{k+1} = m_{k+1})
-//        twice:  G = S^T S = V diag(s^2) V^T (ndmps_syevj_f64, order <= 512), keep s_j > 1e-7 s_0,  S <- S V_r diag(1/s)
+//        twice:  G = S^T S = V diag(s^2) V^T (ndmps_syevj_f64, order <= 512), keep s_j > 1e-7 s_0,  S <- S V_r diag(1/s)   (gram_pass.h)
 //        site k = S (left-orthonormal after the second pass),  M_{k+1} = S^T X_k  (r_{k+1} x m_{k+1})
 //      s_0 = 0 at some bond: the product is zero.  The last site is X_{L-1}.
 //
@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gram_pass.h"
 #include "pair_product.h"
 
 namespace {
@@ -42,7 +43,6 @@ using ndmps::widen;
 
 constexpr int kResident = ndmps::kPairResident;  // largest bond of the resident sandwich
 constexpr int kMaxSketch = 512;    // largest sketch bond (order of the eigenproblems)
-constexpr double kFloor = 1e-7;    // SKETCH_FLOOR of core/hadamard.py
 
 struct SandwichArgs {
   const void* A;    // (ca, d, ca2) in storage type code_a
@@ -113,13 +113,6 @@ __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs 
       const int row = 16 * wave + lr + 4 * r, c = 16 * nt + lc;
       if (row < ro && c < co) out[(int64_t)row * co + c] = acc[nt][r];
     }
-}
-
-// Q (rows x r, row-major) columns divided by sqrt(w), in place
-__global__ void __launch_bounds__(256) cols_over_sqrt_kernel(double* __restrict__ Q, int64_t rows, int64_t r,
-                                                             const double* __restrict__ w) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < rows * r; e += (int64_t)gridDim.x * 256)
-    Q[e] /= sqrt(w[e % r]);
 }
 
 // One site's sandwich: the checked extents and, on the general route, the fp64 cores and the scratch T.
@@ -297,25 +290,11 @@ void carve(const Plan& p, Arena& ar, Buffers& b) {
   }
 }
 
-// One Gram orthonormalisation pass of S (rows x l, row-major): G = S^T S = V diag(w) V^T, kept r = #{sqrt(w_j) >
-// kFloor sqrt(w_0)} (0 when w_0 <= 0), Q (rows x r) = S V_r diag(1 / sqrt(w)).  Synchronises the stream.
-int gram_pass(const Plan& p, const Buffers& b, const double* S, int64_t rows, int64_t l, double* Q, int64_t* r_out,
-              std::vector<double>& hw, hipStream_t s) {
-  NDMPS_TRY(ndmps_dgemm(1, 0, l, l, rows, S, l, S, l, b.G, l, s));
-  NDMPS_TRY(ndmps_syevj_f64(b.G, l, b.V, b.w, b.ev, p.eig, nullptr, s));
-  NDMPS_CHECK_HIP(hipMemcpyAsync(hw.data(), b.w, l * sizeof(double), hipMemcpyDeviceToHost, s));
-  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-  *r_out = 0;
-  if (!(hw[0] > 0.0)) return NDMPS_OK;
-  const double s0 = std::sqrt(hw[0]);
-  int64_t r = 0;
-  while (r < l && hw[r] > 0.0 && std::sqrt(hw[r]) > kFloor * s0) ++r;
-  r = std::min(r, rows);
-  NDMPS_TRY(ndmps_dgemm(0, 0, rows, r, l, S, l, b.V, l, Q, r, s));
-  hipLaunchKernelGGL(cols_over_sqrt_kernel, dim3(grid1d(rows * r)), dim3(256), 0, s, Q, rows, r, b.w);
-  NDMPS_LAUNCH_CHECK();
-  *r_out = r;
-  return NDMPS_OK;
+// the pieces of the workspace that a Gram orthonormalisation pass (gram_pass.h) uses
+ndmps::GramPassWs gram_ws(const Plan& p, const Buffers& b) {
+  ndmps::GramPassWs g;
+  g.G = b.G, g.V = b.V, g.w = b.w, g.ev = b.ev, g.eig = p.eig;
+  return g;
 }
 
 }  // namespace
@@ -423,6 +402,7 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
   // ---- 2. forward pass
   std::vector<int64_t> r(L + 1, 1);
   std::vector<double> hw(p.lmax);
+  const ndmps::GramPassWs gw = gram_ws(p, b);
   const double one = 1.0;
   NDMPS_CHECK_HIP(hipMemcpyAsync(b.M, &one, sizeof(double), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));  // `one` and h_R are read
@@ -444,10 +424,10 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
       S = b.S;
     }
     int64_t r1 = 0, r2 = 0;
-    NDMPS_TRY(gram_pass(p, b, S, rows, l, b.Q, &r1, hw, s));
+    NDMPS_TRY(ndmps::gram_pass(gw, S, rows, l, b.Q, &r1, hw, s));
     if (r1 == 0) return zero_product();
     double* site_out = d_out + p.out_off[k];
-    NDMPS_TRY(gram_pass(p, b, b.Q, rows, r1, site_out, &r2, hw, s));
+    NDMPS_TRY(ndmps::gram_pass(gw, b.Q, rows, r1, site_out, &r2, hw, s));
     if (r2 == 0) return zero_product();
     r[k + 1] = r2;
     // M_{k+1} (r2 x m_{k+1}) = site^T X_k

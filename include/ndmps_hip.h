@@ -717,6 +717,51 @@ int ndmps_hadamard_sandwich(int form, int64_t ca, int64_t d, int64_t ca2, int64_
                             double* d_out, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Rounding of K weighted sums of T chains by a randomised sketch (no reference counterpart; core/sumsketch.py,
+ * csrc/sumsketch.hip).  All chains have the L site dims h_dims; h_bonds: T x (L + 1) bonds, frame a at a (L + 1)
+ * (outer ones 1, at most 4096; a frame with a bond above 64 leaves the resident kernels for a general route through
+ * ndmps_dgemm on its cores widened to fp64); h_ell: the L + 1 sketch bonds l_k, l_0 = l_L = 1,
+ * 1 <= l_k <= 512.
+ * ndmps_sumsketch_layout (host only): returns the element count of the fp64 output arena for K chains, K times the
+ * count of one chain; h_out_off (L + 1): inside a chain site k starts at element h_out_off[k] and has the capacity
+ * l_k d_k l_{k+1}; chain j starts at j h_out_off[L]; the sketch cores R_k (l_k, d_k, l_{k+1}) are laid out like one chain
+ * in h_R.  *h_ws_bytes, with m_k = sum_a chi_{a,k}, every piece rounded up to 256 bytes, plus 256: 8 times
+ *     sum_k l_k d_k l_{k+1}  (R)  |  1  (W_{a,L})  |  max(1, sum_{k=1..L-1} l_k m_k)  (environments)  |  max_{k<L} l_k m_k
+ *     (M, twice)  |  max_k l_k d_k l_{k+1}  (S and Q, one piece each)  |  max_k nsplit_k l_k d_k l_{k+1}  (partials of the sketch
+ *     form, nsplit_k = min(max(1, 512 / (d_k ceil(l_k / 64) ceil(l_{k+1} / 64))), max(1, min(16, T / 4))), integer
+ *     divisions)  |  lmax^2  (G and V, one piece each)  |  lmax  (w)
+ * then max(1, ndmps_syevj_workspace_bytes(lmax)) bytes, 64 T L bytes (records) and 8 T bytes (frame lists), and, when
+ * some frame has a bond above 64, 8 times the sum of those frames' core sizes and 8 max l_k d_k chi_{a,k+1} over them.
+ * ndmps_sumsketch_sketch: for each output row j of h_weights (K x T, HOST) the left-orthonormal fp64 chain of bonds
+ * h_ranks[j (L + 1) + k] <= l_k that sketches sum_a h_weights[j, a] chain_a (site k written contiguously as
+ * (r_k, d_k, r_{k+1}) at its offset).  h_codes: T storage codes (0 fp32, 1 bf16, 2 fp64); h_cores: T x L device
+ * pointers, frame a site k at a L + k; h_R: r_len = h_out_off[L] HOST doubles.  h_zero[j] = 1 where output j is zero
+ * (a row of zero weights, or s_0 = 0 at some bond): its ranks are 1 and its part of d_out is undefined.  A frame
+ * whose weights are zero in every row is read in neither pass; a zero entry is skipped in that row's forward pass.
+ * Sums over frames run in ascending order without atomics.  Synchronises the stream.
+ * ndmps_sumsketch_step: the kernel family alone on one site for T frames with cores (chi_a, d, chi2_a); per-frame
+ * matrices are row-major fp64, concatenated in frame order:
+ *   form 0 (env):      d_out: W_a (chi_a x l0) = sum_i A_a[:, i, :] (Wn_a R[:, i, :]^T),   d_in: Wn_a (chi2_a x l1), d_mat: R (l0, d, l1)
+ *   form 1 (sketch):   d_out: S ((l0 d) x l1) = sum_a (M_a A_a[:, i, :]) Wn_a,             d_in: M_a (l0 x chi_a), d_in2: Wn_a (chi2_a x l1)
+ *   form 2 (project):  d_out: Mn_a (l1 x chi2_a) = sum_i Q[(., i), :]^T (M_a A_a[:, i, :]), d_in: M_a (l0 x chi_a), d_mat: Q ((l0 d) x l1)
+ * l0, l1 <= 512.  d_ws: 68 T bytes plus 8 nsplit l0 d l1 (form 1, nsplit as above with l_k = l0, l_{k+1} = l1) plus 1024;
+ * with frames of a bond above 64 (general route) also 8 (chi_a d chi2_a) + 256 for each of them, 8 l0 d max chi2_a and
+ * (form 1) 8 l0 d l1.
+ * Only the elements of each result are written.  Synchronises the stream.
+ * Every argument error (NULL pointers, bad codes, outer bonds != 1, a frame bond > 4096, l_k > 512, a non-finite
+ * weight, a short arena or workspace) is NDMPS_EINVAL before anything is launched.
+ * --------------------------------------------------------------------------------- */
+int64_t ndmps_sumsketch_layout(int T, int K, int L, const int64_t* h_dims, const int64_t* h_bonds, const int64_t* h_ell,
+                               int64_t* h_out_off, int64_t* h_ws_bytes);
+int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims, const int64_t* h_bonds, const int* h_codes,
+                           const void* const* h_cores, const double* h_weights, const int64_t* h_ell, const double* h_R,
+                           int64_t r_len, double* d_out, int64_t out_elems, int64_t* h_ranks, int* h_zero, void* d_ws,
+                           int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_sumsketch_step(int form, int T, int64_t d, const int64_t* h_chi, const int64_t* h_chi2, const int* h_codes,
+                         const void* const* h_cores, int64_t l0, int64_t l1, const double* d_in, const double* d_in2,
+                         const double* d_mat, double* d_out, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Overlap: replaces `mps @ mps` (core/ndmps.py:76,86; utils/metrics.py:160), real data,
  * no conjugation, fp64 transfer matrices.  Synchronises the stream.
  * --------------------------------------------------------------------------------- */
