@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(256)
 slice_range_kernel(const float* __restrict__ a, const float* __restrict__ b, Slicing s, double* __restrict__ range) {
   __shared__ float rmin[4], rmax[4];
   const int64_t base = slice_base(s, blockIdx.x);
-  float lo = FLT_MAX, hi = -FLT_MAX;
+  float lo = INFINITY, hi = -INFINITY;
   const int64_t n = s.H * s.W;
   for (int64_t e = threadIdx.x; e < n; e += 256) {
     const int64_t off = base + (e / s.W) * s.sH + (e % s.W) * s.sW;
@@ -163,7 +163,7 @@ psnr_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, in
   __shared__ double rs[4];
   __shared__ float rm[4];
   double acc = 0.0;
-  float mx = -FLT_MAX;
+  float mx = -INFINITY;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const double d = (double)a[i] - (double)b[i];
     acc += d * d;
@@ -344,7 +344,7 @@ extern "C" int ndmps_psnr_f32(const float* d_a, const float* d_b, int64_t n, dou
   std::vector<double> host(2 * (size_t)grid);
   NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), partial, host.size() * 8, hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
-  double sum = 0.0, mx = -DBL_MAX;
+  double sum = 0.0, mx = -INFINITY;
   for (int i = 0; i < grid; ++i) {
     sum += host[2 * i];
     mx = std::max(mx, host[2 * i + 1]);

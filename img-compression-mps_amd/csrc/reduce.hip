@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) sum_final_kernel(const double* __restrict
 __global__ void __launch_bounds__(256)
 minmax_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ partial) {
   __shared__ float rmin[4], rmax[4];
-  float lo = FLT_MAX, hi = -FLT_MAX;
+  float lo = INFINITY, hi = -INFINITY;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const float v = x[i];
@@ -89,7 +89,7 @@ minmax_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict_
 __global__ void __launch_bounds__(256) minmax_final_kernel(const float* __restrict__ partial, int count,
                                                            float* __restrict__ out) {
   __shared__ float rmin[256], rmax[256];
-  float lo = FLT_MAX, hi = -FLT_MAX;
+  float lo = INFINITY, hi = -INFINITY;
   for (int i = threadIdx.x; i < count; i += 256) {
     lo = fminf(lo, partial[2 * i]);
     hi = fmaxf(hi, partial[2 * i + 1]);
@@ -147,7 +147,7 @@ minmax_many_kernel(const float* const* __restrict__ ptrs, const int64_t* __restr
   __shared__ double rsum[4];
   const float* x = ptrs[blockIdx.y];
   const int64_t n = lens[blockIdx.y];
-  float lo = FLT_MAX, hi = -FLT_MAX;
+  float lo = INFINITY, hi = -INFINITY;
   double ss = 0.0;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -187,7 +187,7 @@ minmax_many_f64_kernel(const double* const* __restrict__ ptrs, const int64_t* __
   __shared__ double rmin[4], rmax[4], rsum[4];
   const double* x = ptrs[blockIdx.y];
   const int64_t n = lens[blockIdx.y];
-  double lo = DBL_MAX, hi = -DBL_MAX, ss = 0.0;
+  double lo = INFINITY, hi = -INFINITY, ss = 0.0;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const double v = x[i];
@@ -510,31 +510,30 @@ int dct_fft_launch(const float* src, float* dst, int64_t rows, int64_t n, hipStr
   dv.out[0] = dst;
   return dct_fft_launch_vols<INVERSE>(dv, 1, rows, n, s);
 }
-// the volumes of a lockstep group, thirty-two per launch; volumes the FFT does not take (row length, alignment) and
-// every volume when the row length is not a power of two go through the basis product one by one
+// the volumes of a lockstep group: every volume takes the route its single call would take (dct_fft_ok on its own
+// operands), so a member's result does not depend on its neighbours.  Volumes the FFT takes go thirty-two per launch,
+// the others (row length, alignment) through the basis product one by one.
 template <bool INVERSE>
 int dct_many(int count, const float* const* h_in, float* const* h_out, int64_t rows, int64_t n, const float* d_basis,
              hipStream_t s) {
-  bool fft = true;
   for (int v = 0; v < count; ++v) {
     NDMPS_REQUIRE(h_in[v] && h_out[v] && h_in[v] != h_out[v], "the DCT is out of place (volume %d)", v);
-    fft = fft && dct_fft_ok(rows, n, h_in[v], h_out[v]);
+    NDMPS_REQUIRE(d_basis != nullptr || dct_fft_ok(rows, n, h_in[v], h_out[v]), "volume %d needs the DCT basis", v);
   }
-  if (!fft) {
-    NDMPS_REQUIRE(d_basis != nullptr, "this row length needs the DCT basis");
-    for (int v = 0; v < count; ++v)
+  DctVols dv = {};
+  int nv = 0;
+  for (int v = 0; v < count; ++v) {
+    if (dct_fft_ok(rows, n, h_in[v], h_out[v])) {
+      dv.in[nv] = h_in[v];
+      dv.out[nv] = h_out[v];
+      if (++nv < kDctVols) continue;
+      NDMPS_TRY(dct_fft_launch_vols<INVERSE>(dv, nv, rows, n, s));
+      nv = 0;
+    } else {
       NDMPS_TRY(ndmps_sgemm(0, INVERSE ? 1 : 0, rows, n, n, h_in[v], n, d_basis, n, h_out[v], n, (ndmps_stream_t)s));
-    return NDMPS_OK;
-  }
-  for (int v0 = 0; v0 < count; v0 += kDctVols) {
-    const int nv = std::min(kDctVols, count - v0);
-    DctVols dv = {};
-    for (int v = 0; v < nv; ++v) {
-      dv.in[v] = h_in[v0 + v];
-      dv.out[v] = h_out[v0 + v];
     }
-    NDMPS_TRY(dct_fft_launch_vols<INVERSE>(dv, nv, rows, n, s));
   }
+  if (nv) NDMPS_TRY(dct_fft_launch_vols<INVERSE>(dv, nv, rows, n, s));
   return NDMPS_OK;
 }
 
@@ -639,7 +638,7 @@ extern "C" int ndmps_minmax_many_f32(int count, const float* const* h_ptrs, cons
   NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), partial, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < count; ++i) {
-    double lo = FLT_MAX, hi = -FLT_MAX, ss = 0.0;
+    double lo = INFINITY, hi = -INFINITY, ss = 0.0;
     for (int j = 0; j < kManySlices; ++j) {
       const double* o = &host[3 * ((size_t)i * kManySlices + j)];
       lo = std::min(lo, o[0]);
@@ -672,7 +671,7 @@ minmax_arena_kernel(const float* __restrict__ base, int64_t row_stride, int n_co
   const int t = blockIdx.y;  // tensor index = volume * n_cores + core
   const float* x = base + (int64_t)(t / n_cores) * row_stride + ac.offset[t % n_cores];
   const int64_t n = ac.len[t % n_cores];
-  float lo = FLT_MAX, hi = -FLT_MAX;
+  float lo = INFINITY, hi = -INFINITY;
   double ss = 0.0;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -729,7 +728,7 @@ extern "C" int ndmps_minmax_collect(int count, const double* d_partial, float* h
   NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), d_partial, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < count; ++i) {
-    double lo = FLT_MAX, hi = -FLT_MAX, ss = 0.0;
+    double lo = INFINITY, hi = -INFINITY, ss = 0.0;
     for (int j = 0; j < kManySlices; ++j) {
       const double* o = &host[3 * ((size_t)i * kManySlices + j)];
       lo = std::min(lo, o[0]);
@@ -778,7 +777,7 @@ extern "C" int ndmps_minmax_many_f64(int count, const double* const* h_ptrs, con
   NDMPS_CHECK_HIP(hipMemcpyAsync(host.data(), partial, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < count; ++i) {
-    double lo = DBL_MAX, hi = -DBL_MAX, ss = 0.0;
+    double lo = INFINITY, hi = -INFINITY, ss = 0.0;
     for (int j = 0; j < kManySlices; ++j) {
       const double* o = &host[3 * ((size_t)i * kManySlices + j)];
       lo = std::min(lo, o[0]);
@@ -833,7 +832,7 @@ extern "C" int ndmps_idct_last_f32(const float* d_y, float* d_x, int64_t rows, i
 // The same transforms for the volumes of a lockstep group in one launch (thirty-two per launch): h_x / h_y are HOST arrays
 // of `count` device pointers, every volume (rows, n) row-major.  The reference transforms volume by volume in a Python
 // loop (evaluation/benchmark.py:80-100 around core/ndmps.py:62-63 and :152-153); results equal the single-volume calls
-// bit for bit.
+// bit for bit, also in a group whose members differ in alignment (dct_many routes volume by volume).
 extern "C" int ndmps_dct_last_many_f32(int count, const float* const* h_x, float* const* h_y, int64_t rows, int64_t n,
                                        const float* d_basis, ndmps_stream_t stream) {
   NDMPS_REQUIRE(count >= 1 && h_x && h_y && rows >= 1 && n >= 1, "bad dct_last_many argument");

@@ -123,7 +123,9 @@ int ndmps_idct_last_f32(const float* d_y, float* d_x, int64_t rows, int64_t n,
 /* The same transforms for the volumes of a lockstep group in ONE launch (thirty-two per launch): h_x / h_y are HOST
  * arrays of `count` device pointers, every volume (rows, n) row-major and distinct from its result.  Replaces the
  * per-volume Python loop around core/ndmps.py:62-63 and :152-153 (evaluation/benchmark.py:80-100); results equal the
- * single-volume calls bit for bit.  d_basis may be NULL when n is a power of two in [64, 1024] (the FFT route). */
+ * single-volume calls bit for bit: every volume takes the route of its own single call (a volume whose operands are
+ * not 16-byte aligned goes through the basis product, its aligned neighbours through the FFT).  d_basis may be NULL
+ * when n is a power of two in [64, 1024] and every operand is 16-byte aligned (the FFT route). */
 int ndmps_dct_last_many_f32(int count, const float* const* h_x, float* const* h_y, int64_t rows, int64_t n,
                             const float* d_basis, ndmps_stream_t stream);
 int ndmps_idct_last_many_f32(int count, const float* const* h_y, float* const* h_x, int64_t rows, int64_t n,
