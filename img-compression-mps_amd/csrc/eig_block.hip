@@ -19,8 +19,10 @@
 //           the 16x16 cross pairs (16 inner steps): every index pair once per sweep.
 //
 // The two roles touch disjoint outputs, so the serial chain of a sweep is nb-1 launches whose
-// length is max(apply, diag) instead of 2 (nb-1) launches of apply + diag (n-1 = 511 launches for
-// the scalar-parallel method in eig.hip, kept as ndmps_syevj_simple_f64 for cross-checks).
+// length is max(apply, diag) instead of 2 (nb-1) launches of apply + diag (a scalar-parallel
+// Jacobi needs n-1 = 511 launches per sweep at order 512; the one this file replaced was removed,
+// DESIGN 5.2).  The regimes of the host driver and the matrices every one of them is tested on are
+// listed in DESIGN 5.35 (tests/jacobi_cases.py, tests/test_gpu_jacobi_exact.py).
 //
 // Batched: every kernel takes a batch of matrices (blockIdx.y); matrices of different size are
 // padded to the common np (padded indices never rotate) and converged ones are skipped, so B

@@ -250,7 +250,17 @@ int ndmps_convert_bf16_to_f32(const void* d_x, int64_t n, float* d_y, ndmps_stre
 int ndmps_convert_f32_to_bf16(const float* d_x, int64_t n, void* d_y, ndmps_stream_t stream);
 /* symmetric eigen-decomposition (block two-sided Jacobi, fp64): G = V diag(w) V^T,
  * w descending, eigenvectors in the COLUMNS of V, each with its largest-magnitude
- * component positive.  d_G is destroyed.  Synchronises the stream. */
+ * component positive (the first one on ties).  Only the symmetric part 0.5 (G + G^T) of the input is
+ * decomposed.  d_G is destroyed.  Synchronises the stream.
+ * Thresholds: a sweep that visits no |a_pq| above rel_tol * max|a_ii| ends the iteration, and an |a_pq| at or
+ * below 1e-19 * max|a_ii| is not rotated -- both are relative to the largest DIAGONAL entry of the input, not
+ * to its norm (finding the norm would cost every solve a pass over n^2 entries).  Every caller passes a
+ * positive semi-definite matrix, for which max|a_ii| is the norm within a factor n.  Indefinite matrices
+ * whose diagonal stays within a factor 8 of max|lambda| are inside the contract and tested
+ * (tests/jacobi_cases.py).  For a symmetric matrix whose diagonal is small against its off-diagonal
+ * entries the thresholds fall below the rounding of the matrix (they are 0 for a zero diagonal):
+ * convergence within the limit of 40 sweeps is not promised, and the call may end with NDMPS_ENOCONV.
+ * Nothing depends on the absolute scale: a power of two in front of G changes no bit of V. */
 int64_t ndmps_syevj_workspace_bytes(int64_t n);
 int ndmps_syevj_f64(double* d_G, int64_t n, double* d_V, double* d_w, void* d_ws,
                     int64_t ws_bytes, int* h_sweeps, ndmps_stream_t stream);
