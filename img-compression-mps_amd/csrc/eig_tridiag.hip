@@ -3356,10 +3356,11 @@ int trd_launch_vectors(int batch, const int64_t* h_n, const int64_t* h_k, int64_
 }  // namespace
 
 // Phase 2 with the rank decided ON THE DEVICE from the eigenvalues of phase 1: k_b = number of singular values
-// sqrt(w_i) above cutoff * sqrt(w_0), at least 1, at most k_cap.  Columns k_b .. k_cap-1 of V are zero-filled, so
-// callers size everything by k_cap and never wait for the rank.  d_ranks[b] (device) receives k_b, d_spectra (may
-// be NULL) the k_cap leading singular values at stride spectra_stride, d_status[b] (may be NULL) != 0 if the
-// orthonormalisation of matrix b broke down.  Fully asynchronous on `stream`.
+// sqrt(max(w_i, 0)) above cutoff * sqrt(max(w_0, 0)), at least 1, at most min(k_cap, n_b).  Columns k_b ..
+// min(k_cap, n_b)-1 of V are zero-filled, so callers size everything by k_cap and never wait for the rank.  d_ranks[b]
+// (device) receives k_b, d_spectra (may be NULL) the min(k_cap, n_b) leading singular values at stride spectra_stride
+// (nothing behind them is written), d_status[b] (may be NULL) != 0 if the orthonormalisation of matrix b broke down.
+// Fully asynchronous on `stream`.
 extern "C" int ndmps_syevd_topk_vectors_auto_f64(int batch, const int64_t* h_n, int64_t k_cap, double cutoff,
                                                  int* d_ranks, double* d_spectra, int64_t spectra_stride,
                                                  int* d_status, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {

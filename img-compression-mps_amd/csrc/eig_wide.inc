@@ -226,8 +226,9 @@ int wide_orthonormalise(TrdDesc* desc_b, double* Z, int n, int k, int kp, double
 
 // The same for at most 128 vectors of one or two BIG matrices whose rank is known on the device only (the sweep decides
 // it there and never waits for it): all kp columns are factored, with the rows and columns of S from the rank on
-// replaced by the identity -- what sits in those columns of Z (nothing inverse iteration wrote) neither enters the
-// kept columns nor is touched; the back-transformation zero-fills them.  Two passes, no look at the defect (that
+// replaced by the identity -- those columns of Z (zeros: trd_invit_kernel clears the columns of its block behind the
+// rank, so nothing the workspace held before meets the solve) neither enter the kept columns nor are touched; the
+// back-transformation zero-fills them.  Two passes, no look at the defect (that
 // would be a host read); a Cholesky breakdown is reported through the status word like everywhere.
 __global__ void __launch_bounds__(256) wide_mask_rank_kernel(double* __restrict__ S, int k, const TrdDesc* __restrict__ d) {
   const int r = d->k;
@@ -498,11 +499,12 @@ __global__ void __launch_bounds__(64 * kBwWaves) back_wide_kernel(const TrdDesc*
 constexpr int kBrR = 256;  // rows per workgroup
 constexpr int kBrC = 16;   // columns per workgroup
 
-// X <- Z for the kept columns, zeros up to k_fill
+// X <- Z for the kept columns, zeros up to k_fill.  k_fill is the batch's (min(k_cap, n_max)): a member of a smaller
+// order has n columns only, and a column index past them would land in the next row of its V (ld n)
 __global__ void __launch_bounds__(256) back_rows_init_kernel(const TrdDesc* __restrict__ desc, TrdWork w, int k_fill) {
   const TrdDesc& d = desc[blockIdx.y];
   const int n = d.n, k = d.k, kp = w.kp;
-  const int cols = max(k, k_fill);
+  const int cols = min(max(k, k_fill), n);
   const double* Z = w.Z + (int64_t)blockIdx.y * w.n_max * kp;
   double* X = d.V_out;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < (int64_t)n * cols; e += (int64_t)gridDim.x * 256) {

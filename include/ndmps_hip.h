@@ -377,10 +377,16 @@ int ndmps_debug_inject_team_abort(int launches);
  * place of ds_bpermute), on one wave: d_out[12][64] = the sums of d_in[64] over 2, 4, 8, 16, 32, 64 adjacent lanes, then
  * over the lanes with equal lane % 1, 2, 4, 8, 16, 32 -- every lane holds its group's sum. */
 int ndmps_debug_lane_sums_f64(const double* d_in, double* d_out, ndmps_stream_t stream);
-/* Phase 2 with the rank decided ON THE DEVICE from phase 1's eigenvalues: k_b = #{i < k_cap : sqrt(w_i) > cutoff
- * sqrt(w_0)}, at least 1.  Columns k_b .. k_cap-1 of V are zero-filled, so a caller sizes everything by k_cap and
- * never waits for the rank.  d_ranks[b] (device) receives k_b, d_spectra (may be NULL) the k_cap leading singular
- * values at stride spectra_stride, d_status (may be NULL) the breakdown flags.  Fully asynchronous. */
+/* Phase 2 with the rank decided ON THE DEVICE from phase 1's eigenvalues:
+ * k_b = #{i < min(k_cap, n_b) : sqrt(max(w_i, 0)) > cutoff * sqrt(max(w_0, 0))}, at least 1; k_cap <=
+ * ndmps_syevd_topk_max_k(), cutoff >= 0 (cutoff >= 1 keeps one; the zero matrix keeps one, a unit vector).  Columns
+ * k_b .. min(k_cap, n_b)-1 of V are zero-filled, so a caller sizes everything by k_cap and never waits for the rank.
+ * Write extents, per matrix b of order n_b (a batch may mix orders below k_cap with larger ones): of V exactly the
+ * columns 0 .. min(k_cap, n_b)-1 of its n_b x n_b block (ld n_b) -- no column behind them, nothing past n_b^2;
+ * d_ranks[b] (device) receives k_b; d_spectra (may be NULL) the min(k_cap, n_b) leading singular values
+ * sqrt(max(w_i, 0)) at b * spectra_stride -- a matrix of order n_b < k_cap has no more, and the entries from
+ * min(k_cap, n_b) up to spectra_stride are left as they were; d_status (may be NULL) the breakdown flags (2, a resident
+ * team that gave up, is sticky).  d_G of phase 1 is only read.  Fully asynchronous. */
 int ndmps_syevd_topk_vectors_auto_f64(int batch, const int64_t* h_n, int64_t k_cap, double cutoff,
                                       int* d_ranks, double* d_spectra, int64_t spectra_stride,
                                       int* d_status, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);

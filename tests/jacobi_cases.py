@@ -96,7 +96,7 @@ class Case:
     G: np.ndarray                 # what the solver is given (not symmetric for ``skew``)
     S: np.ndarray                 # its symmetric part: the matrix that is decomposed
     lam: np.ndarray               # the spectrum, descending
-    vec: np.ndarray = None        # laplace: exact eigenvectors, column j for lam[j]
+    vec: np.ndarray = None        # laplace, hadamard, skew: exact eigenvectors, column j for lam[j] (any basis of a cluster)
     indefinite: bool = False
     rank: int = None              # deficient: the exact rank
 
@@ -175,9 +175,13 @@ def hadamard(n, spectrum="a"):
             break
     else:
         raise AssertionError("no draw met the diagonal condition")
-    g, _ = _perm_sym(a, rng)
-    return Case(f"hadamard-{spectrum}-{n}", "hadamard", g, g, np.sort(full)[::-1].copy(),
-                indefinite=bool((full < 0).any()))
+    g, p = _perm_sym(a, rng)
+    basis = np.zeros((n, n))                  # the columns of H / sqrt(m), and unit vectors for the diagonal entries
+    basis[:m, :m] = h / np.sqrt(m)
+    basis[np.arange(m, n), np.arange(m, n)] = 1.0
+    order = np.argsort(-full, kind="stable")
+    return Case(f"hadamard-{spectrum}-{n}", "hadamard", g, g, full[order].copy(),
+                vec=np.ascontiguousarray(basis[p][:, order]), indefinite=bool((full < 0).any()))
 
 
 def hadamard_m(n):
@@ -261,7 +265,8 @@ def skew(n, spectrum="b"):
     k = (r - r.T) / 4
     if n > 1 and not k.any():
         k[0, 1], k[1, 0] = 0.25, -0.25
-    return Case(f"skew-{spectrum}-{n}", "skew", base.S + k, base.S, base.lam, indefinite=base.indefinite)
+    return Case(f"skew-{spectrum}-{n}", "skew", base.S + k, base.S, base.lam, vec=base.vec,
+                indefinite=base.indefinite)
 
 
 def outside_contract():
@@ -348,7 +353,7 @@ def ratios(case, w, v):
     out["resid"] = rel(np.abs(case.S @ v - v * w[None, :k]).max(), e * scale)
     top = v[np.argmax(np.abs(v), axis=0), np.arange(k)]
     out["sign"] = 0.0 if np.all(top > 0) else np.inf
-    if case.vec is not None:
+    if case.family == "laplace":
         err = np.minimum(np.abs(v - case.vec[:, :k]).max(axis=0), np.abs(v + case.vec[:, :k]).max(axis=0))
         gap = gaps(case.lam)[:k]
         gap = np.where(np.isinf(gap), 0.0, gap)       # order 1: no neighbour, no bar
