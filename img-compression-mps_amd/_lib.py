@@ -118,6 +118,10 @@ SIGNATURES = {
     "ndmps_series_gram_route": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64]),
     "ndmps_series_gram": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_i64, p_int,
                                     C.POINTER(vp), vp, vp, i64, vp]),
+    "ndmps_series_wgram_route": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64, p_i64]),
+    "ndmps_series_wgram_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_i64, p_i64, i64]),
+    "ndmps_series_wgram": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i64, p_i64, p_int, C.POINTER(vp), p_i64, p_int,
+                                     C.POINTER(vp), p_i64, C.c_int, C.POINTER(vp), vp, vp, i64, vp]),
     "ndmps_chain_contract_scatter_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, vp, i64, vp]),
     "ndmps_chain_batched_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64]),
     "ndmps_chain_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64]),

@@ -1501,17 +1501,38 @@ class NDMPS:
         return objs, cols, _lib.i64_array(objs[0].mps.dims), sa, sb
 
     @staticmethod
-    def gram_route(objs, others=None) -> str:
+    def _weight_args(rows, weight):
+        """The checks of a ``weight=`` argument against the objects of the call, and its C arguments (bonds, storage
+        code, core pointers)."""
+        from . import lincomb as _lc
+        from . import wgram as _wg
+
+        _wg.check_weight_type(weight, NDMPS)
+        _check_compatible(list(rows) + [weight])
+        _wg.check_mode(weight.mode)
+        L = weight.mps.L
+        return (_lib.i64_array(weight.mps.bonds), _lc.dtype_code(weight.mps.dtype),
+                (C.c_void_p * L)(*[c.data_ptr() for c in weight.mps.cores]))
+
+    @staticmethod
+    def gram_route(objs, others=None, *, weight=None) -> str:
         """Which path ``gram`` takes for these lists: "resident" (every inner bond <= 64: one launch, one workgroup
-        per pair), "batched" (larger bonds, equal in all objects) or "per-pair" (larger ragged bonds)."""
+        per pair), "batched" (larger bonds, equal in all objects) or "per-pair" (larger ragged bonds).  With a
+        ``weight`` (csrc/wgram.hip): "resident" (every inner bond of the objects <= 64, whatever the weight's bonds)
+        or "per-pair"."""
         from . import series as _se
 
         objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
-        return _se.ROUTES[_lib.check(_lib.load().ndmps_series_gram_route(len(objs), len(cols), objs[0].mps.L, c_dims,
-                                                                         sa[0], sb[0]))]
+        lib = _lib.load()
+        if weight is not None:
+            sw = NDMPS._weight_args(objs if others is None else objs + cols, weight)
+            return _se.ROUTES[_lib.check(lib.ndmps_series_wgram_route(len(objs), len(cols), objs[0].mps.L, c_dims, sa[0],
+                                                                      sb[0], sw[0]))]
+        return _se.ROUTES[_lib.check(lib.ndmps_series_gram_route(len(objs), len(cols), objs[0].mps.L, c_dims,
+                                                                 sa[0], sb[0]))]
 
     @staticmethod
-    def gram(objs, others=None, as_torch: bool = False):
+    def gram(objs, others=None, as_torch: bool = False, *, weight=None):
         """
         The fp64 Gram matrix ``G[a, b] = objs[a].mps @ others[b].mps`` of a series, computed on the cores in one call
         (csrc/series.hip); ``others=None`` gives the symmetric K x K matrix, where only a <= b is computed and
@@ -1520,31 +1541,58 @@ class NDMPS:
         series (``pca``) are functions of G.  Storage types may mix; the same inputs give the same bits.  NumPy
         array by default, device tensor with ``as_torch=True``.  No counterpart in the reference.
 
-        Raises TypeError for a non-NDMPS, ValueError for an empty list or objects that differ in qubit_size, shape,
-        mode, device or site dims (as ``linear_combination``).
+        ``weight`` (an NDMPS of the same shape, site dims and mode: a mask, an ROI indicator, a window) gives the
+        second moments under it, ``G_w[a, b] = sum_x w(x) X^a(x) X^b(x)``, by the exact three-chain contraction on
+        the cores (csrc/wgram.hip): nothing is decoded, rounded or sketched, the weight's bonds are unrestricted, and
+        the same inputs give the same bits.  ``norm`` / ``norm_value`` play no part, as without a weight.  The pairs
+        are processed in chunks that keep the workspace within ``wgram.WS_LIMIT_BYTES``.
+
+        Raises TypeError for a non-NDMPS (``weight`` included), ValueError for an empty list or objects that differ in
+        qubit_size, shape, mode, device or site dims (as ``linear_combination``; the weight counts as one of them), for
+        a weight in DCT mode (a product of coefficient volumes is not the product of the volumes) and when a single
+        pair does not fit the workspace limit.
         """
         torch = _torch()
         lib = _lib.load()
         objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
         Ka, Kb, L = len(objs), len(cols), objs[0].mps.L
         device = objs[0].mps.device
+        sym = 1 if others is None else 0
+        if weight is not None:
+            from . import wgram as _wg
+
+            sw = NDMPS._weight_args(objs if others is None else objs + cols, weight)
+            nbytes = lib.ndmps_series_wgram_workspace_bytes(Ka, Kb, sym, L, c_dims, sa[0], sb[0], sw[0], _wg.WS_LIMIT_BYTES)
+            if nbytes != _lib.EWORKSPACE:
+                _lib.check(nbytes)
+            nbytes = _wg.check_workspace(nbytes)
+            with torch.cuda.device(device):
+                G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
+                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+                with _span("wgram"):
+                    _lib.check(lib.ndmps_series_wgram(Ka, Kb, sym, L, c_dims, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2],
+                                                      sw[0], sw[1], sw[2], G.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _lib.stream_ptr()))
+                del ws
+            return G if as_torch else G.cpu().numpy()
         nbytes = _lib.check(lib.ndmps_series_gram_workspace_bytes(Ka, Kb, L, c_dims, sa[0], sb[0]))
         with torch.cuda.device(device):
             G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
             ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
             with _span("gram"):
-                _lib.check(lib.ndmps_series_gram(Ka, Kb, 1 if others is None else 0, L, c_dims, sa[0], sa[1], sa[2],
+                _lib.check(lib.ndmps_series_gram(Ka, Kb, sym, L, c_dims, sa[0], sa[1], sa[2],
                                                  sb[0], sb[1], sb[2], G.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  _lib.stream_ptr()))
             del ws
         return G if as_torch else G.cpu().numpy()
 
-    def inner(self, other) -> float:
-        """``<self, other>``: the entry of ``NDMPS.gram([self], [other])``."""
-        return float(NDMPS.gram([self], [other])[0, 0])
+    def inner(self, other, *, weight=None) -> float:
+        """``<self, other>``: the entry of ``NDMPS.gram([self], [other])``; with ``weight`` the entry of
+        ``NDMPS.gram([self], [other], weight=weight)``, ``sum_x w(x) self(x) other(x)``."""
+        return float(NDMPS.gram([self], [other], weight=weight)[0, 0])
 
     @staticmethod
-    def pca(objs, n_components=None, center: bool = True, cutoff: float = 0.0, max_bond=None, dtype=None):
+    def pca(objs, n_components=None, center: bool = True, cutoff: float = 0.0, max_bond=None, dtype=None, *, weight=None):
         """
         Temporal PCA of a series without a decoded volume (core/series.py): from ``G = gram(objs)`` the centred Gram
         matrix ``H G H = U diag(lam) U^T`` (host, fp64), ``sigma_k = sqrt(lam_k)``; component k is the unit volume
@@ -1555,6 +1603,12 @@ class NDMPS:
         (``lam / (K - 1)``, or ``lam / K`` uncentred), scores (K x r), weights (K x r), components (NDMPS) and mean
         (``linear_combination(objs, [1/K] * K, cutoff, max_bond, dtype)`` when ``center``, else None).  Errors as
         ``gram`` and ``linear_combination`` (the summed bonds of the series must not exceed 4096).
+
+        ``weight`` (see ``gram``) makes this the PCA under the weighted inner product ``<x, y>_w = sum_x w x y``:
+        ``G_w = gram(objs, weight=weight)`` takes the place of G, the components are still linear combinations of the
+        unmasked objects, and each is unit-norm in the weighted norm, ``inner(c_k, c_l, weight=weight) = delta_kl``.
+        The weight should be non-negative: a weight with negative values can make ``G_w`` indefinite, and its negative
+        eigenvalues are clipped to zero like rounding noise.
         """
         torch = _torch()
         from . import lincomb as _lc
@@ -1563,7 +1617,7 @@ class NDMPS:
         objs = list(objs)
         _se.check_components(n_components)
         _lc.check_args(max(len(objs), 1), [0.0] * max(len(objs), 1), cutoff, max_bond)
-        G = NDMPS.gram(objs)
+        G = NDMPS.gram(objs, weight=weight)
         K = len(objs)
         f64 = dtype == torch.float64 or (dtype != torch.float32
                                          and _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]))

@@ -699,6 +699,30 @@ int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dim
                       ndmps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Masked / weighted Gram matrix of a series (no reference counterpart; core/wgram.py, csrc/wgram.hip):
+ * d_G[a, b] = sum_x w(x) X^a(x) X^b(x) for every pair of two lists of chains and ONE weight chain w over the same L
+ * site dims, by the exact three-chain contraction on the cores (no rounding, no sketch).  The lists are given as in
+ * ndmps_series_gram; h_bonds_w: the weight's L + 1 bonds (outer ones 1, inner ones unrestricted), code_w its storage
+ * code, h_cores_w its L device pointers.
+ * Route (ndmps_series_wgram_route): 0 every inner bond of both lists <= 64, one sandwich launch and one fp64 product
+ * per site over a whole chunk of pairs; 2 larger bonds, pair by pair on ndmps_dgemm / ndmps_dgemm_batched.
+ * Workspace: the pairs are processed in chunks that fit d_ws.  ndmps_series_wgram_workspace_bytes returns what the call
+ * uses under a cap of cap_bytes (all pairs in one chunk if they fit), or NDMPS_EWORKSPACE if not even one pair fits;
+ * ndmps_series_wgram chunks by the ws_bytes it is given.  The workspace need not be zeroed.  The chunking changes no bit
+ * of d_G, and the same inputs give the same bits.  The route and workspace functions need no device.
+ * --------------------------------------------------------------------------------- */
+int ndmps_series_wgram_route(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                             const int64_t* h_bonds_b, const int64_t* h_bonds_w);
+int64_t ndmps_series_wgram_workspace_bytes(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims,
+                                           const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                                           const int64_t* h_bonds_w, int64_t cap_bytes);
+int ndmps_series_wgram(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const int64_t* h_bonds_a,
+                       const int* h_codes_a, const void* const* h_cores_a, const int64_t* h_bonds_b,
+                       const int* h_codes_b, const void* const* h_cores_b, const int64_t* h_bonds_w, int code_w,
+                       const void* const* h_cores_w, double* d_G, void* d_ws, int64_t ws_bytes,
+                       ndmps_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Elementwise product of two chains by a randomised sketch (no reference counterpart; core/hadamard.py,
  * csrc/hadamard.hip).  Both chains have the L site dims h_dims; h_bonds_a / h_bonds_b: their L + 1 bonds (outer ones 1,
  * at most 4096); h_ell: the L + 1 sketch bonds l_k, l_0 = l_L = 1 and 1 <= l_k <= min(512, chi_{a,k} chi_{b,k}).
