@@ -238,6 +238,25 @@ def _check_compatible(objs):
                                dims=o.mps.dims) for o in objs])
 
 
+def _chain_list_args(lst):
+    """The C arguments of a list of objects: (bonds, storage codes, core pointers), object by object."""
+    from . import lincomb as _lc
+
+    return (_lib.i64_array([b for o in lst for b in o.mps.bonds]),
+            (C.c_int * len(lst))(*[_lc.dtype_code(o.mps.dtype) for o in lst]),
+            (C.c_void_p * (len(lst) * lst[0].mps.L))(*[c.data_ptr() for o in lst for c in o.mps.cores]))
+
+
+def _sketch_table(R):
+    """The random cores of a sketch as one flat fp64 table, site by site."""
+    return np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
+
+
+def _zero_chain(dims, device):
+    """The zero MPS: bond-1 zero cores in fp64."""
+    return DeviceMPS([_torch().zeros((1, d, 1), dtype=_torch().float64, device=device) for d in dims], _trusted=True)
+
+
 def _carve_cores(arena, out_off, bonds, dims):
     """The cores ``(bonds[k], dims[k], bonds[k + 1])`` of an output arena as views: core k starts at ``out_off[k]``."""
     return [arena[out_off[k]: out_off[k] + bonds[k] * d * bonds[k + 1]].view(bonds[k], d, bonds[k + 1])
@@ -1278,7 +1297,7 @@ class NDMPS:
         ws_bytes = C.c_int64(0)
         total = _lib.check(lib.ndmps_hadamard_layout(L, c_dims, c_ba, c_bb, c_ell, out_off, C.byref(ws_bytes)))
         _hd.check_workspace(ws_bytes.value)
-        table = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
+        table = _sketch_table(R)
         ranks = (C.c_int64 * (L + 1))()
         with torch.cuda.device(device):
             arena = torch.empty(max(int(total), 1), dtype=torch.float64, device=device)
@@ -1290,7 +1309,7 @@ class NDMPS:
                     ranks, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
             del ws
             if rc > 0:  # the zero product
-                return DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims], _trusted=True)
+                return _zero_chain(dims, device)
         r = [int(v) for v in ranks]
         return DeviceMPS(_carve_cores(arena, out_off, r, dims), _trusted=True)
 
@@ -1348,20 +1367,17 @@ class NDMPS:
         torch = _torch()
         lib = _lib.load()
         from . import hadamard as _hd
-        from . import lincomb as _lc
 
         first = objs[0].mps
         T, K, L, dims, device = len(objs), int(w.shape[0]), first.L, first.dims, first.device
         c_dims = _lib.i64_array(dims)
-        c_bonds = _lib.i64_array([b for o in objs for b in o.mps.bonds])
+        c_bonds, codes, ptrs = _chain_list_args(objs)
         c_ell = _lib.i64_array(ell)
         out_off = (C.c_int64 * (L + 1))()
         ws_bytes = C.c_int64(0)
         total = _lib.check(lib.ndmps_sumsketch_layout(T, K, L, c_dims, c_bonds, c_ell, out_off, C.byref(ws_bytes)))
         _hd.check_workspace(ws_bytes.value)
-        table = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
-        codes = (C.c_int * T)(*[_lc.dtype_code(o.mps.dtype) for o in objs])
-        ptrs = (C.c_void_p * (T * L))(*[c.data_ptr() for o in objs for c in o.mps.cores])
+        table = _sketch_table(R)
         weights = np.ascontiguousarray(w, dtype=np.float64)
         ranks = (C.c_int64 * (K * (L + 1)))()
         zero = (C.c_int * K)()
@@ -1378,8 +1394,7 @@ class NDMPS:
             chains = []
             for j in range(K):
                 if zero[j]:
-                    chains.append(DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims],
-                                            _trusted=True))
+                    chains.append(_zero_chain(dims, device))
                     continue
                 r = [int(v) for v in ranks[j * (L + 1):(j + 1) * (L + 1)]]
                 chains.append(DeviceMPS(_carve_cores(arena[j * chain:(j + 1) * chain], out_off, r, dims), _trusted=True))
@@ -1435,9 +1450,7 @@ class NDMPS:
             ell = _ss.sketch_bonds(dims, bond_lists, max_bond, oversample)
             chains = NDMPS._sum_sketch(frames, w[:, used], ell, _hd.sketch_cores(dims, ell, seed))
         else:
-            device = first.mps.device
-            chains = [DeviceMPS([torch.zeros((1, d, 1), dtype=torch.float64, device=device) for d in dims], _trusted=True)
-                      for _ in range(w.shape[0])]
+            chains = [_zero_chain(dims, first.mps.device) for _ in range(w.shape[0])]
         out = []
         for sketched in chains:
             scale = float(torch.linalg.vector_norm(sketched.cores[-1]))
@@ -1478,7 +1491,6 @@ class NDMPS:
     @staticmethod
     def _series_args(objs, others):
         """Checked lists and the C arguments of the ndmps_series_gram* calls."""
-        from . import lincomb as _lc
         from . import series as _se
 
         objs = list(objs)
@@ -1489,15 +1501,8 @@ class NDMPS:
         _se.check_lists(len(objs), None if others is None else len(rows) - len(objs))
         _check_compatible(rows)
         cols = objs if others is None else rows[len(objs):]
-
-        def side(lst):
-            L = lst[0].mps.L
-            return (_lib.i64_array([b for o in lst for b in o.mps.bonds]),
-                    (C.c_int * len(lst))(*[_lc.dtype_code(o.mps.dtype) for o in lst]),
-                    (C.c_void_p * (len(lst) * L))(*[c.data_ptr() for o in lst for c in o.mps.cores]))
-
-        sa = side(objs)
-        sb = sa if others is None else side(cols)
+        sa = _chain_list_args(objs)
+        sb = sa if others is None else _chain_list_args(cols)
         return objs, cols, _lib.i64_array(objs[0].mps.dims), sa, sb
 
     @staticmethod
@@ -1558,6 +1563,7 @@ class NDMPS:
         Ka, Kb, L = len(objs), len(cols), objs[0].mps.L
         device = objs[0].mps.device
         sym = 1 if others is None else 0
+        lists = sa + sb
         if weight is not None:
             from . import wgram as _wg
 
@@ -1566,23 +1572,15 @@ class NDMPS:
             if nbytes != _lib.EWORKSPACE:
                 _lib.check(nbytes)
             nbytes = _wg.check_workspace(nbytes)
-            with torch.cuda.device(device):
-                G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-                with _span("wgram"):
-                    _lib.check(lib.ndmps_series_wgram(Ka, Kb, sym, L, c_dims, sa[0], sa[1], sa[2], sb[0], sb[1], sb[2],
-                                                      sw[0], sw[1], sw[2], G.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      _lib.stream_ptr()))
-                del ws
-            return G if as_torch else G.cpu().numpy()
-        nbytes = _lib.check(lib.ndmps_series_gram_workspace_bytes(Ka, Kb, L, c_dims, sa[0], sb[0]))
+            span, entry, lists = "wgram", lib.ndmps_series_wgram, lists + sw
+        else:
+            nbytes = int(_lib.check(lib.ndmps_series_gram_workspace_bytes(Ka, Kb, L, c_dims, sa[0], sb[0])))
+            span, entry = "gram", lib.ndmps_series_gram
         with torch.cuda.device(device):
             G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
-            ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-            with _span("gram"):
-                _lib.check(lib.ndmps_series_gram(Ka, Kb, sym, L, c_dims, sa[0], sa[1], sa[2],
-                                                 sb[0], sb[1], sb[2], G.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 _lib.stream_ptr()))
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+            with _span(span):
+                _lib.check(entry(Ka, Kb, sym, L, c_dims, *lists, G.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
             del ws
         return G if as_torch else G.cpu().numpy()
 

@@ -1,5 +1,6 @@
-// One Gram orthonormalisation pass of a sketched bond, shared by the sketch of the elementwise product (hadamard.hip)
-// and the sketch of a sum (sumsketch.hip): the only definition of the pass and of its floor.
+// What the sketch of the elementwise product (hadamard.hip) and the sketch of a sum (sumsketch.hip) share on the host:
+// the only definition of the layout of a sketched chain, of one Gram orthonormalisation pass of a sketched bond, of
+// its floor and of its pieces of the workspace.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -17,6 +18,42 @@ struct GramPassWs {
   char* ev = nullptr;
   int64_t eig = 0;
 };
+// its carve for passes of order <= lmax, in the order G, V, w, ev
+static inline GramPassWs carve_gram_pass(Arena& ar, int64_t lmax, int64_t eig) {
+  GramPassWs g;
+  g.G = ar.take<double>(lmax * lmax);
+  g.V = ar.take<double>(lmax * lmax);
+  g.w = ar.take<double>(lmax);
+  g.ev = ar.take<char>(std::max<int64_t>(eig, 1));
+  g.eig = eig;
+  return g;
+}
+
+// The layout of a sketched chain: site k of the output holds at most ell[k] dims[k] ell[k+1] doubles at out_off[k], and
+// the random cores R have the same layout.
+struct SketchLayout {
+  std::vector<int64_t> dims, ell, out_off;  // dims and ell: assigned and checked by the caller
+  int64_t lmax = 1, sq = 1, r_elems = 0, eig = 0;  // largest sketch bond, largest site, all sites, the eigen-solver's bytes
+};
+static inline int fill_sketch_layout(SketchLayout& s) {
+  const int L = (int)s.dims.size();
+  s.lmax = *std::max_element(s.ell.begin(), s.ell.end());
+  s.out_off.assign(L + 1, 0);
+  for (int k = 0; k < L; ++k) {
+    const int64_t cap = s.ell[k] * s.dims[k] * s.ell[k + 1];
+    s.out_off[k + 1] = s.out_off[k] + cap;
+    s.sq = std::max(s.sq, cap);
+  }
+  s.r_elems = s.out_off[L];
+  s.eig = ndmps_syevj_workspace_bytes(s.lmax);
+  NDMPS_REQUIRE(s.eig >= 0, "internal: eigen-solver workspace");
+  return NDMPS_OK;
+}
+// the caller's random cores: as many as the layout says (they are copied once the workspace is known to fit)
+static inline int check_sketch_cores(const SketchLayout& s, int64_t r_len) {
+  NDMPS_REQUIRE(r_len == s.r_elems, "the sketch cores have %lld elements, expected %lld", (long long)r_len, (long long)s.r_elems);
+  return NDMPS_OK;
+}
 
 // Q (rows x r, row-major) columns divided by sqrt(w), in place
 static __global__ void __launch_bounds__(256) cols_over_sqrt_kernel(double* __restrict__ Q, int64_t rows, int64_t r,

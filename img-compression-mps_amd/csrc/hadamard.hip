@@ -32,14 +32,15 @@
 
 #include "common.h"
 #include "gram_pass.h"
+#include "pair_host.h"
 #include "pair_product.h"
 
 namespace {
 
 using ndmps::Arena;
 using ndmps::f64x4;
+using ndmps::core64;
 using ndmps::grid1d;
-using ndmps::widen;
 
 constexpr int kResident = ndmps::kPairResident;  // largest bond of the resident sandwich
 constexpr int kMaxSketch = 512;    // largest sketch bond (order of the eigenproblems)
@@ -88,31 +89,12 @@ __global__ void __launch_bounds__(256, 2) hadamard_sandwich_kernel(SandwichArgs 
   for (int i = i0; i < i1; ++i) {
     // ---- E of this task, transposed into Et: Et[k][m] = E[m][k], zero outside re x ce.  A wave's pass reads 16
     // consecutive k of four rows m (128-byte runs) and writes four consecutive m of 16 image rows.
-    const double* E = g.E + (e0 + (kEnv ? i : 0)) * (int64_t)re * ce;
-    {
-      const int kk = tid & 15, mm = tid >> 4;
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-          const int k = 16 * kb + kk, m = 16 * mb + mm;
-          const bool ok = k < ce && m < re;
-          const double v = E[ok ? (int64_t)m * ce + k : 0];
-          Et[pair_img(k, m)] = ok ? v : 0.0;
-        }
-    }
+    ndmps::pair_load_et(Et, g.E + (e0 + (kEnv ? i : 0)) * (int64_t)re * ce, re, ce, ce, tid);
     ndmps::pair_load_operands<kTrans>(aq, g.A, g.code_a, g.ca, d, g.ca2, i, lr, col, own2);
     __syncthreads();
 #include "pair_product_step.inc"
   }
-  double* out = g.out + task * (int64_t)ro * co;
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * wave + lr + 4 * r, c = 16 * nt + lc;
-      if (row < ro && c < co) out[(int64_t)row * co + c] = acc[nt][r];
-    }
+  ndmps::pair_store_strip(g.out + task * (int64_t)ro * co, co, acc, ro, co, wave, lr, lc);
 }
 
 // One site's sandwich: the checked extents and, on the general route, the fp64 cores and the scratch T.
@@ -158,28 +140,15 @@ int sandwich_resident(const Site& t, bool env, int64_t n, const double* E, doubl
 int64_t general_scratch(const Site& t, int64_t n) { return n * t.ca * t.d * t.cb2; }
 
 // General route on fp64 cores A64 / B64.
-//   forward:      T (n ca x d cb2) = E (n ca x cb) B (cb x d cb2);   out[rho, i] = A_i^T T[rho][:, i, :]
+//   forward:      sandwich_forward_general of pair_host.h
 //   environment:  T[lam][:, i, :] (ca x cb2) = A_i E[lam, i];        out[lam] = T[lam] (ca x d cb2) B (cb x d cb2)^T
 int sandwich_general(const Site& t, bool env, int64_t n, const double* A64, const double* B64, const double* E, double* out,
                      double* T, hipStream_t s) {
   const int64_t ca = t.ca, ca2 = t.ca2, cb = t.cb, cb2 = t.cb2, d = t.d;
+  if (!env) return ndmps::sandwich_forward_general(ca, ca2, cb, cb2, d, n, A64, B64, E, out, T, s);
   const int chunk = ndmps_gemm_batched_max();
   std::vector<const double*> pa(chunk), pb(chunk);
   std::vector<double*> pc(chunk);
-  if (!env) {
-    NDMPS_TRY(ndmps_dgemm(0, 0, n * ca, d * cb2, cb, E, cb, B64, d * cb2, T, d * cb2, s));
-    for (int64_t t0 = 0; t0 < n * d; t0 += chunk) {
-      const int nb = (int)std::min<int64_t>(chunk, n * d - t0);
-      for (int q = 0; q < nb; ++q) {
-        const int64_t rho = (t0 + q) / d, i = (t0 + q) % d;
-        pa[q] = A64 + i * ca2;
-        pb[q] = T + rho * ca * d * cb2 + i * cb2;
-        pc[q] = out + (t0 + q) * ca2 * cb2;
-      }
-      NDMPS_TRY(ndmps_dgemm_batched(nb, 1, 0, ca2, cb2, ca, pa.data(), d * ca2, pb.data(), d * cb2, pc.data(), cb2, s));
-    }
-    return NDMPS_OK;
-  }
   for (int64_t t0 = 0; t0 < n * d; t0 += chunk) {
     const int nb = (int)std::min<int64_t>(chunk, n * d - t0);
     for (int q = 0; q < nb; ++q) {
@@ -203,11 +172,11 @@ int sandwich_general(const Site& t, bool env, int64_t n, const double* A64, cons
 }
 
 // Host plan of a sketch: the checked arguments, the output layout and the workspace carve.
-struct Plan {
+struct Plan : ndmps::SketchLayout {
   int L = 0;
   bool resident = true;
-  std::vector<int64_t> dims, ba, bb, ell, m, out_off;
-  int64_t lmax = 1, r_elems = 0, xy = 1, mm = 1, sq = 1, tmax = 1, eig = 0;
+  std::vector<int64_t> ba, bb, m;
+  int64_t xy = 1, mm = 1, tmax = 1;
   bool identity(int k) const { return ell[k] == m[k]; }
   int64_t core_a(int k) const { return ba[k] * dims[k] * ba[k + 1]; }
   int64_t core_b(int k) const { return bb[k] * dims[k] * bb[k + 1]; }
@@ -234,29 +203,20 @@ int make_plan(int L, const int64_t* h_dims, const int64_t* h_ba, const int64_t* 
                   (long long)p.m[k]);
     NDMPS_REQUIRE(p.ell[k] <= kMaxSketch, "bond %d: sketch bond %lld exceeds %d", k, (long long)p.ell[k], kMaxSketch);
     top = std::max({top, p.ba[k], p.bb[k]});
-    p.lmax = std::max(p.lmax, p.ell[k]);
   }
   p.resident = top <= kResident;
-  p.out_off.assign(L + 1, 0);
   for (int k = 0; k < L; ++k) {
-    const int64_t cap = p.ell[k] * p.dims[k] * p.ell[k + 1];
-    p.out_off[k + 1] = p.out_off[k] + cap;
-    p.r_elems += cap;
-    p.sq = std::max(p.sq, cap);
     p.xy = std::max(p.xy, p.ell[k] * p.dims[k] * p.m[k + 1]);
     p.mm = std::max(p.mm, p.ell[k] * p.m[k]);
     p.tmax = std::max(p.tmax, p.ell[k] * p.ba[k] * p.dims[k] * p.bb[k + 1]);
   }
-  p.eig = ndmps_syevj_workspace_bytes(p.lmax);
-  NDMPS_REQUIRE(p.eig >= 0, "internal: eigen-solver workspace");
-  return NDMPS_OK;
+  return ndmps::fill_sketch_layout(p);
 }
 
 struct Buffers {
-  double *R = nullptr, *XY = nullptr, *M = nullptr, *S = nullptr, *Q = nullptr, *G = nullptr, *V = nullptr, *w = nullptr,
-         *T = nullptr;
+  double *R = nullptr, *XY = nullptr, *M = nullptr, *S = nullptr, *Q = nullptr, *T = nullptr;
+  ndmps::GramPassWs gw;
   std::vector<double*> Wt, wa, wb;  // Wt[k]: null where the bond is an identity; wa / wb: the general route's cores
-  char* ev = nullptr;
 };
 
 // Workspace (doubles, every piece 256-byte aligned), in this order:
@@ -277,10 +237,7 @@ void carve(const Plan& p, Arena& ar, Buffers& b) {
   b.M = ar.take<double>(p.mm);
   b.S = ar.take<double>(p.sq);
   b.Q = ar.take<double>(p.sq);
-  b.G = ar.take<double>(p.lmax * p.lmax);
-  b.V = ar.take<double>(p.lmax * p.lmax);
-  b.w = ar.take<double>(p.lmax);
-  b.ev = ar.take<char>(std::max<int64_t>(p.eig, 1));
+  b.gw = ndmps::carve_gram_pass(ar, p.lmax, p.eig);
   if (!p.resident) {
     b.wa.assign(L, nullptr);
     b.wb.assign(L, nullptr);
@@ -288,13 +245,6 @@ void carve(const Plan& p, Arena& ar, Buffers& b) {
     for (int k = 0; k < L; ++k) b.wb[k] = ar.take<double>(p.core_b(k));
     b.T = ar.take<double>(p.tmax);
   }
-}
-
-// the pieces of the workspace that a Gram orthonormalisation pass (gram_pass.h) uses
-ndmps::GramPassWs gram_ws(const Plan& p, const Buffers& b) {
-  ndmps::GramPassWs g;
-  g.G = b.G, g.V = b.V, g.w = b.w, g.ev = b.ev, g.eig = p.eig;
-  return g;
 }
 
 }  // namespace
@@ -331,15 +281,9 @@ extern "C" int ndmps_hadamard_sandwich(int form, int64_t ca, int64_t d, int64_t 
   double* wb = ar.take<double>(cb * d * cb2);
   double* T = ar.take<double>(general_scratch(t, n));
   NDMPS_REQUIRE(ar.fits(), "sandwich workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
-  const double *A64 = (const double*)d_core_a, *B64 = (const double*)d_core_b;
-  if (code_a != 2) {
-    NDMPS_TRY(widen(d_core_a, code_a, ca * d * ca2, wa, s));
-    A64 = wa;
-  }
-  if (code_b != 2) {
-    NDMPS_TRY(widen(d_core_b, code_b, cb * d * cb2, wb, s));
-    B64 = wb;
-  }
+  const double *A64, *B64;
+  NDMPS_TRY(core64(d_core_a, code_a, ca * d * ca2, wa, s, &A64));
+  NDMPS_TRY(core64(d_core_b, code_b, cb * d * cb2, wb, s, &B64));
   return sandwich_general(t, form == 1, n, A64, B64, d_E, d_out, T, s);
 }
 
@@ -353,7 +297,7 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
   Plan p;
   NDMPS_TRY(make_plan(L, h_dims, h_bonds_a, h_bonds_b, h_ell, p));
   for (int k = 0; k < L; ++k) NDMPS_REQUIRE(h_cores_a[k] && h_cores_b[k], "site %d: NULL core", k);
-  NDMPS_REQUIRE(r_len == p.r_elems, "the sketch cores have %lld elements, expected %lld", (long long)r_len, (long long)p.r_elems);
+  NDMPS_TRY(ndmps::check_sketch_cores(p, r_len));
   NDMPS_REQUIRE(out_elems >= p.out_off[L], "output arena too small: %lld < %lld", (long long)out_elems, (long long)p.out_off[L]);
   Arena ar(d_ws, ws_bytes);
   Buffers b;
@@ -370,16 +314,8 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
     t.code_a = code_a, t.code_b = code_b;
     t.A = h_cores_a[k], t.B = h_cores_b[k];
     if (p.resident) continue;
-    A64[k] = (const double*)t.A;
-    B64[k] = (const double*)t.B;
-    if (code_a != 2) {
-      NDMPS_TRY(widen(t.A, code_a, p.core_a(k), b.wa[k], s));
-      A64[k] = b.wa[k];
-    }
-    if (code_b != 2) {
-      NDMPS_TRY(widen(t.B, code_b, p.core_b(k), b.wb[k], s));
-      B64[k] = b.wb[k];
-    }
+    NDMPS_TRY(core64(t.A, code_a, p.core_a(k), b.wa[k], s, &A64[k]));
+    NDMPS_TRY(core64(t.B, code_b, p.core_b(k), b.wb[k], s, &B64[k]));
   }
   auto sandwich = [&](int k, bool env, int64_t n, const double* E, double* out) -> int {
     if (p.resident) return sandwich_resident(site[k], env, n, E, out, s);
@@ -402,7 +338,6 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
   // ---- 2. forward pass
   std::vector<int64_t> r(L + 1, 1);
   std::vector<double> hw(p.lmax);
-  const ndmps::GramPassWs gw = gram_ws(p, b);
   const double one = 1.0;
   NDMPS_CHECK_HIP(hipMemcpyAsync(b.M, &one, sizeof(double), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));  // `one` and h_R are read
@@ -424,10 +359,10 @@ extern "C" int ndmps_hadamard_sketch(int L, const int64_t* h_dims, const int64_t
       S = b.S;
     }
     int64_t r1 = 0, r2 = 0;
-    NDMPS_TRY(ndmps::gram_pass(gw, S, rows, l, b.Q, &r1, hw, s));
+    NDMPS_TRY(ndmps::gram_pass(b.gw, S, rows, l, b.Q, &r1, hw, s));
     if (r1 == 0) return zero_product();
     double* site_out = d_out + p.out_off[k];
-    NDMPS_TRY(ndmps::gram_pass(gw, b.Q, rows, r1, site_out, &r2, hw, s));
+    NDMPS_TRY(ndmps::gram_pass(b.gw, b.Q, rows, r1, site_out, &r2, hw, s));
     if (r2 == 0) return zero_product();
     r[k + 1] = r2;
     // M_{k+1} (r2 x m_{k+1}) = site^T X_k

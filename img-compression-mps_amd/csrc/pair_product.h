@@ -1,6 +1,15 @@
-// The two-phase fp64 pair product on v_mfma_f64_16x16x4_f64, shared by the Gram matrix of a series (series.hip) and
-// the sandwich of the elementwise product (hadamard.hip).  This header holds the only definition of the LDS
-// image and of the operand loader; pair_product_step.inc holds the two phases with their fencing.
+// The two-phase fp64 pair product on v_mfma_f64_16x16x4_f64 and what its users share on the device.  The users are the
+// Gram matrix of a series (series.hip), its weighted form (wgram.hip), the sandwich of the elementwise product
+// (hadamard.hip) and the three forms of the sketch of a sum (sumsketch.hip).  What is shared lives in three places:
+//   pair_product_step.inc  the two phases of one physical index with their fencing (text, included at kernel level);
+//   this header            the only definition of the LDS image (pair_img), of the operand loader
+//                          (pair_load_operands), of the loaders of the Et image (pair_load_et, pair_set_unit) and of
+//                          the guarded store of a wave's strip of accumulators (pair_store_strip); the site kernel of
+//                          wgram.hip alone spells pair_load_et and pair_store_strip out itself, for its time;
+//   pair_host.h            the host front end: lists of chains and their checks, the fp64 copies of cores, the device
+//                          tables, the pair table and the general route's forward sandwich (gram_pass.h: the layout
+//                          of a sketch and its Gram pass).
+// DESIGN.md 5.38 maps which file uses which piece.
 //
 // One workgroup of four waves forms, for the physical indices i of a site,
 //     acc (+)= op(A_i) ( E op(B_i) ),      op(X_i) = X[:, i, :]   (kEnv == false: op(A_i) is used transposed)
@@ -62,6 +71,40 @@ __device__ __forceinline__ void pair_load_operands(double (&q)[16], const void* 
   if (code == 2) pair_load_operands_as<double, kTrans>(q, (const double*)core, chi, d, chi2, i, lr, c, active);
   else if (code == 1) pair_load_operands_as<__bf16, kTrans>(q, (const __bf16*)core, chi, d, chi2, i, lr, c, active);
   else pair_load_operands_as<float, kTrans>(q, (const float*)core, chi, d, chi2, i, lr, c, active);
+}
+
+// src (rows x cols, leading dimension ld) transposed into an LDS image, img[k][m] = src[m][k], zero outside.  A wave's
+// pass reads 16 consecutive k of four rows m and writes four consecutive m of 16 image rows.
+__device__ __forceinline__ void pair_load_et(double* img, const double* __restrict__ src, int rows, int cols, int64_t ld, int tid) {
+  asm volatile("" : "+v"(tid));  // the addresses are formed here, per call: hoisted out of a kernel's loop they spill
+  const int kk = tid & 15, mm = tid >> 4;
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+      const int k = 16 * kb + kk, m = 16 * mb + mm;
+      const bool ok = k < cols && m < rows;
+      const double v = src[ok ? (int64_t)m * ld + k : 0];
+      img[pair_img(k, m)] = ok ? v : 0.0;
+    }
+}
+
+// E_0 = [1] as an image: element (0, 0) one, zero elsewhere
+__device__ __forceinline__ void pair_set_unit(double* img, int tid) {
+  for (int e = tid; e < kPairLd * kPairLd; e += 256) img[e] = e == 0 ? 1.0 : 0.0;
+}
+
+// A wave's 16 x 64 strip of accumulators, rows 16 wave + lr + 4 r and columns 16 nt + lc, stored into out (row-major,
+// leading dimension ld) where it lies inside rows x cols.  The caller folds a row or column offset into `out`.
+__device__ __forceinline__ void pair_store_strip(double* out, int64_t ld, const f64x4 (&acc)[4], int rows, int cols, int wave,
+                                                 int lr, int lc) {
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * wave + lr + 4 * r, c = 16 * nt + lc;
+      if (row < rows && c < cols) out[(int64_t)row * ld + c] = acc[nt][r];
+    }
 }
 
 }  // namespace ndmps

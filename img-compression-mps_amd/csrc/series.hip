@@ -19,25 +19,22 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_host.h"
 #include "pair_product.h"
 
 namespace {
 
 using ndmps::Arena;
-using ndmps::ceil_div;
+using ndmps::ChainList;
+using ndmps::grid1d;
 
 constexpr int kResident = ndmps::kPairResident;  // largest inner bond of the resident kernel
 
 struct SeriesArgs {
-  const void* const* cores_a;  // Ka x L
-  const void* const* cores_b;  // Kb x L
-  const int* bonds_a;          // Ka x (L + 1)
-  const int* bonds_b;          // Kb x (L + 1)
-  const int* codes_a;          // storage codes: 0 fp32, 1 bf16, 2 fp64
-  const int* codes_b;
-  const int* dims;             // L
-  double* G;                   // Ka x Kb
-  int Ka, Kb, L, symmetric;
+  ndmps::PairListArgs t;  // the tables of both lists
+  const int* dims;        // L
+  double* G;              // Ka x Kb
+  int Ka, Kb, symmetric;
 };
 
 // One workgroup per pair (a, b): E stays in LDS over all L sites, every site runs all its i through the step of
@@ -52,18 +49,18 @@ __global__ void __launch_bounds__(256, 2) series_gram_resident_kernel(SeriesArgs
   __shared__ double Et[kLd * kLd];
   __shared__ double Z[kLd * kLd];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
-  const int L = g.L;
-  const int* ba = g.bonds_a + (int64_t)a * (L + 1);
-  const int* bb = g.bonds_b + (int64_t)b * (L + 1);
-  const int code_a = g.codes_a[a], code_b = g.codes_b[b];
+  const int L = g.t.L;
+  const int* ba = g.t.bonds_a + (int64_t)a * (L + 1);
+  const int* bb = g.t.bonds_b + (int64_t)b * (L + 1);
+  const int code_a = g.t.codes_a[a], code_b = g.t.codes_b[b];
 
-  for (int e = tid; e < kLd * kLd; e += 256) Et[e] = e == 0 ? 1.0 : 0.0;  // E_0 = [1]
+  ndmps::pair_set_unit(Et, tid);  // E_0 = [1]
   __syncthreads();
 
   for (int j = 0; j < L; ++j) {
     const int ca = ba[j], ca2 = ba[j + 1], cb = bb[j], cb2 = bb[j + 1], d = g.dims[j], i1 = d;
-    const void* A = g.cores_a[(int64_t)a * L + j];
-    const void* B = g.cores_b[(int64_t)b * L + j];
+    const void* A = g.t.cores_a[(int64_t)a * L + j];
+    const void* B = g.t.cores_b[(int64_t)b * L + j];
     // E_j is ca x cb, E_{j+1} ca2 x cb2
     const int tiles_re = (ca + 15) >> 4, tiles_ro = (ca2 + 15) >> 4, tiles_co = (cb2 + 15) >> 4;
     const int steps1 = (cb + 3) >> 2, steps2 = (ca + 3) >> 2;
@@ -101,8 +98,6 @@ __global__ void __launch_bounds__(256) mirror_kernel(double* __restrict__ G, int
     if (r > c) G[e] = G[c * K + r];
   }
 }
-using ndmps::grid1d;
-using ndmps::widen;
 
 enum { kRouteResident = 0, kRouteBatched = 1, kRoutePerPair = 2 };
 
@@ -110,12 +105,8 @@ enum { kRouteResident = 0, kRouteBatched = 1, kRoutePerPair = 2 };
 struct Plan {
   int Ka = 0, Kb = 0, L = 0, route = 0, chunk = 1;
   std::vector<int64_t> dims;
-  const int64_t *ba = nullptr, *bb = nullptr;
+  ChainList la, lb;            // codes and cores: set by the entry point
   int64_t emax = 1, zmax = 1;  // largest E_j and Z of any pair
-  int64_t chi_a(int a, int j) const { return ba[(int64_t)a * (L + 1) + j]; }
-  int64_t chi_b(int b, int j) const { return bb[(int64_t)b * (L + 1) + j]; }
-  int64_t core_a(int a, int j) const { return chi_a(a, j) * dims[j] * chi_a(a, j + 1); }
-  int64_t core_b(int b, int j) const { return chi_b(b, j) * dims[j] * chi_b(b, j + 1); }
 };
 
 int make_plan(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* ba, const int64_t* bb, Plan& p) {
@@ -124,30 +115,23 @@ int make_plan(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* ba, c
   p.Ka = Ka;
   p.Kb = Kb;
   p.L = L;
-  p.ba = ba;
-  p.bb = bb;
+  p.la.count = Ka, p.la.L = L, p.la.dims = h_dims, p.la.bonds = ba;
+  p.lb.count = Kb, p.lb.L = L, p.lb.dims = h_dims, p.lb.bonds = bb;
   p.dims.assign(h_dims, h_dims + L);
   for (int j = 0; j < L; ++j)
     NDMPS_REQUIRE(p.dims[j] >= 1 && p.dims[j] <= INT32_MAX, "site %d: bad physical dim %lld", j, (long long)p.dims[j]);
   int64_t top = 1, amax = 1, bmax = 1, a2max = 1, b2max = 1;
-  bool same = true;
-  for (int side = 0; side < 2; ++side) {
-    const int64_t* bl = side ? bb : ba;
-    for (int a = 0; a < (side ? Kb : Ka); ++a) {
-      const int64_t* row = bl + (int64_t)a * (L + 1);
-      NDMPS_REQUIRE(row[0] == 1 && row[L] == 1, "list %d, chain %d: the outer bonds must be 1", side, a);
-      for (int j = 0; j <= L; ++j) {
-        NDMPS_REQUIRE(row[j] >= 1 && row[j] <= (1 << 20), "list %d, chain %d, bond %d: bad bond %lld", side, a, j,
-                      (long long)row[j]);
-        top = std::max(top, row[j]);
-        same = same && row[j] == ba[j];
-      }
-    }
-  }
+  NDMPS_TRY(ndmps::check_chain_bonds(p.la, 0, "", &top));
+  NDMPS_TRY(ndmps::check_chain_bonds(p.lb, 1, "", &top));
+  bool same = true;  // every chain of both lists has the bonds of the first
+  for (int a = 0; a < Ka; ++a)
+    for (int j = 0; j <= L; ++j) same = same && p.la.chi(a, j) == ba[j];
+  for (int b = 0; b < Kb; ++b)
+    for (int j = 0; j <= L; ++j) same = same && p.lb.chi(b, j) == ba[j];
   for (int j = 0; j < L; ++j) {  // bounds over all pairs: per site, largest factors of either list
     amax = a2max = bmax = b2max = 1;
-    for (int a = 0; a < Ka; ++a) amax = std::max(amax, p.chi_a(a, j)), a2max = std::max(a2max, p.chi_a(a, j + 1));
-    for (int b = 0; b < Kb; ++b) bmax = std::max(bmax, p.chi_b(b, j)), b2max = std::max(b2max, p.chi_b(b, j + 1));
+    for (int a = 0; a < Ka; ++a) amax = std::max(amax, p.la.chi(a, j)), a2max = std::max(a2max, p.la.chi(a, j + 1));
+    for (int b = 0; b < Kb; ++b) bmax = std::max(bmax, p.lb.chi(b, j)), b2max = std::max(b2max, p.lb.chi(b, j + 1));
     p.emax = std::max(p.emax, a2max * b2max);
     p.zmax = std::max(p.zmax, amax * p.dims[j] * b2max);
   }
@@ -157,114 +141,62 @@ int make_plan(int Ka, int Kb, int L, const int64_t* h_dims, const int64_t* ba, c
 }
 
 struct Buffers {
-  // resident: the tables of SeriesArgs
-  const void** cores = nullptr;
-  int *bonds = nullptr, *codes = nullptr, *dims = nullptr;
-  // general: the widened cores (null where a core is fp64 already), and per pair of a chunk two E and one Z
-  std::vector<double*> wa, wb;
+  ndmps::ChainTables tables;  // resident: the tables of SeriesArgs, and its dims
+  int* dims = nullptr;
+  // general: the cores in fp64, and per pair of a chunk two E and one Z
+  ndmps::WidenedLists w;
   double *E[2] = {nullptr, nullptr}, *Z = nullptr;
 };
 
-void carve(const Plan& p, const int* codes_a, const int* codes_b, bool symmetric, Arena& ar, Buffers& b) {
-  const int64_t K = (int64_t)p.Ka + p.Kb;
+void carve(const Plan& p, bool symmetric, Arena& ar, Buffers& b) {
   if (p.route == kRouteResident) {
-    b.cores = ar.take<const void*>(K * p.L);
-    b.bonds = ar.take<int>(K * (p.L + 1));
-    b.codes = ar.take<int>(K);
+    b.tables.carve(p.la, p.lb, ar);
     b.dims = ar.take<int>(p.L);
     return;
   }
-  // workspace query (no codes): every core counted as if it had to be widened
-  b.wa.assign((size_t)p.Ka * p.L, nullptr);
-  b.wb.assign((size_t)p.Kb * p.L, nullptr);
-  for (int a = 0; a < p.Ka; ++a)
-    for (int j = 0; j < p.L; ++j)
-      if (!codes_a || codes_a[a] != 2) b.wa[(size_t)a * p.L + j] = ar.take<double>(p.core_a(a, j));
-  if (!symmetric || !codes_a)
-    for (int c = 0; c < p.Kb; ++c)
-      for (int j = 0; j < p.L; ++j)
-        if (!codes_b || codes_b[c] != 2) b.wb[(size_t)c * p.L + j] = ar.take<double>(p.core_b(c, j));
+  b.w.carve(p.la, p.lb, symmetric, ar);
   b.E[0] = ar.take<double>(p.emax * p.chunk);
   b.E[1] = ar.take<double>(p.emax * p.chunk);
   b.Z = ar.take<double>(p.zmax * p.chunk);
 }
 
-int run_resident(const Plan& p, int symmetric, const int* codes_a, const void* const* cores_a, const int* codes_b,
-                 const void* const* cores_b, double* d_G, const Buffers& b, hipStream_t s) {
-  const int L = p.L, Ka = p.Ka, Kb = p.Kb;
-  std::vector<const void*> hc(cores_a, cores_a + (size_t)Ka * L);
-  hc.insert(hc.end(), cores_b, cores_b + (size_t)Kb * L);
-  std::vector<int> hb((size_t)(Ka + Kb) * (L + 1)), hk(codes_a, codes_a + Ka), hd(p.dims.begin(), p.dims.end());
-  for (size_t e = 0; e < (size_t)Ka * (L + 1); ++e) hb[e] = (int)p.ba[e];
-  for (size_t e = 0; e < (size_t)Kb * (L + 1); ++e) hb[(size_t)Ka * (L + 1) + e] = (int)p.bb[e];
-  hk.insert(hk.end(), codes_b, codes_b + Kb);
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.cores, hc.data(), hc.size() * sizeof(void*), hipMemcpyHostToDevice, s));
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.bonds, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.codes, hk.data(), hk.size() * sizeof(int), hipMemcpyHostToDevice, s));
+int run_resident(const Plan& p, int symmetric, double* d_G, Buffers& b, hipStream_t s) {
+  SeriesArgs g;
+  NDMPS_TRY(b.tables.upload(p.la, p.lb, s, g.t));
+  const std::vector<int> hd(p.dims.begin(), p.dims.end());
   NDMPS_CHECK_HIP(hipMemcpyAsync(b.dims, hd.data(), hd.size() * sizeof(int), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));  // the host vectors go out of scope; nothing waits after the launch
-  SeriesArgs g;
-  g.cores_a = b.cores;
-  g.cores_b = b.cores + (size_t)Ka * L;
-  g.bonds_a = b.bonds;
-  g.bonds_b = b.bonds + (size_t)Ka * (L + 1);
-  g.codes_a = b.codes;
-  g.codes_b = b.codes + Ka;
   g.dims = b.dims;
   g.G = d_G;
-  g.Ka = Ka;
-  g.Kb = Kb;
-  g.L = L;
+  g.Ka = p.Ka;
+  g.Kb = p.Kb;
   g.symmetric = symmetric;
   // 1-D grid over the pairs (a, b) = (x / Kb, x % Kb): no 65535 limit; the symmetric case leaves a > b at once
-  hipLaunchKernelGGL(series_gram_resident_kernel, dim3((unsigned)((int64_t)Ka * Kb)), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(series_gram_resident_kernel, dim3((unsigned)((int64_t)p.Ka * p.Kb)), dim3(256), 0, s, g);
   NDMPS_LAUNCH_CHECK();
   return NDMPS_OK;
 }
 
-int run_general(const Plan& p, int symmetric, const int* codes_a, const void* const* cores_a, const int* codes_b,
-                const void* const* cores_b, double* d_G, const Buffers& b, hipStream_t s) {
+int run_general(const Plan& p, int symmetric, double* d_G, Buffers& b, hipStream_t s) {
   const int L = p.L, Ka = p.Ka, Kb = p.Kb;
-  std::vector<const double*> A((size_t)Ka * L), B((size_t)Kb * L);
-  for (int a = 0; a < Ka; ++a)
-    for (int j = 0; j < L; ++j) {
-      const size_t e = (size_t)a * L + j;
-      A[e] = (const double*)cores_a[e];
-      if (codes_a[a] != 2) {
-        NDMPS_TRY(widen(cores_a[e], codes_a[a], p.core_a(a, j), b.wa[e], s));
-        A[e] = b.wa[e];
-      }
-    }
-  for (int c = 0; c < Kb; ++c)
-    for (int j = 0; j < L; ++j) {
-      const size_t e = (size_t)c * L + j;
-      if (symmetric) {
-        B[e] = A[e];
-        continue;
-      }
-      B[e] = (const double*)cores_b[e];
-      if (codes_b[c] != 2) {
-        NDMPS_TRY(widen(cores_b[e], codes_b[c], p.core_b(c, j), b.wb[e], s));
-        B[e] = b.wb[e];
-      }
-    }
-  std::vector<std::pair<int, int>> pairs;
-  for (int a = 0; a < Ka; ++a)
-    for (int c = symmetric ? a : 0; c < Kb; ++c) pairs.emplace_back(a, c);
+  NDMPS_TRY(b.w.fill(p.la, p.lb, symmetric, s));
+  const std::vector<const double*>&A = b.w.A, &B = b.w.B;
+  const std::vector<int> pairs = ndmps::pair_table(Ka, Kb, symmetric);
+  const size_t n_pairs = pairs.size() / 2;
   const int chunk = p.chunk;
   std::vector<const double*> pa(chunk), pb(chunk);
   std::vector<double*> pc(chunk);
-  for (size_t p0 = 0; p0 < pairs.size(); p0 += chunk) {
-    const int n = (int)std::min<size_t>(chunk, pairs.size() - p0);
+  for (size_t p0 = 0; p0 < n_pairs; p0 += chunk) {
+    const int n = (int)std::min<size_t>(chunk, n_pairs - p0);
     int cur = 0;
     for (int j = 0; j < L; ++j) {
       // shapes of the chunk: one pair, or pairs that share every bond
-      const int a0 = pairs[p0].first, c0 = pairs[p0].second;
-      const int64_t ca = p.chi_a(a0, j), ca2 = p.chi_a(a0, j + 1), cb = p.chi_b(c0, j), cb2 = p.chi_b(c0, j + 1), d = p.dims[j];
+      const int a0 = pairs[2 * p0], c0 = pairs[2 * p0 + 1];
+      const int64_t ca = p.la.chi(a0, j), ca2 = p.la.chi(a0, j + 1), cb = p.lb.chi(c0, j), cb2 = p.lb.chi(c0, j + 1), d = p.dims[j];
       if (j > 0) {  // Z (ca x d cb2) = E_j (ca x cb) B_j (cb x d cb2); at site 0 E_0 = [1] and Z is the core itself
         for (int q = 0; q < n; ++q) {
           pa[q] = b.E[cur] + (int64_t)q * p.emax;
-          pb[q] = B[(size_t)pairs[p0 + q].second * L + j];
+          pb[q] = B[(size_t)pairs[2 * (p0 + q) + 1] * L + j];
           pc[q] = b.Z + (int64_t)q * p.zmax;
         }
         if (p.route == kRouteBatched)
@@ -274,7 +206,7 @@ int run_general(const Plan& p, int symmetric, const int* codes_a, const void* co
       }
       // E_{j+1} (ca2 x cb2) = (A_j viewed ca d x ca2)^T (Z viewed ca d x cb2); the last one is G[a, b]
       for (int q = 0; q < n; ++q) {
-        const int a = pairs[p0 + q].first, c = pairs[p0 + q].second;
+        const int a = pairs[2 * (p0 + q)], c = pairs[2 * (p0 + q) + 1];
         pa[q] = A[(size_t)a * L + j];
         pb[q] = j > 0 ? b.Z + (int64_t)q * p.zmax : B[(size_t)c * L + j];
         pc[q] = j + 1 == L ? d_G + (int64_t)a * Kb + c : b.E[cur ^ 1] + (int64_t)q * p.emax;
@@ -308,7 +240,7 @@ extern "C" int64_t ndmps_series_gram_workspace_bytes(int Ka, int Kb, int L, cons
   NDMPS_TRY(make_plan(Ka, Kb, L, h_dims, h_bonds_a, h_bonds_b, p));
   Arena ar(nullptr, 0);
   Buffers b;
-  carve(p, nullptr, nullptr, false, ar, b);
+  carve(p, false, ar, b);
   return ar.query_bytes();
 }
 
@@ -319,29 +251,20 @@ extern "C" int ndmps_series_gram(int Ka, int Kb, int symmetric, int L, const int
   NDMPS_REQUIRE(h_codes_a && h_cores_a && h_codes_b && h_cores_b && d_G, "NULL series argument");
   Plan p;
   NDMPS_TRY(make_plan(Ka, Kb, L, h_dims, h_bonds_a, h_bonds_b, p));
+  p.la.codes = h_codes_a, p.la.cores = h_cores_a;
+  p.lb.codes = h_codes_b, p.lb.cores = h_cores_b;
   symmetric = symmetric != 0;
-  if (symmetric) {
-    NDMPS_REQUIRE(Ka == Kb, "a symmetric series needs one list (Ka = %d, Kb = %d)", Ka, Kb);
-    for (int64_t e = 0; e < (int64_t)Ka * L; ++e)
-      NDMPS_REQUIRE(h_cores_a[e] == h_cores_b[e], "a symmetric series needs the same cores in both lists");
-    for (int64_t e = 0; e < (int64_t)Ka * (L + 1); ++e)
-      NDMPS_REQUIRE(h_bonds_a[e] == h_bonds_b[e], "a symmetric series needs the same bonds in both lists");
-  }
-  for (int side = 0; side < 2; ++side)
-    for (int a = 0; a < (side ? Kb : Ka); ++a) {
-      const int code = (side ? h_codes_b : h_codes_a)[a];
-      NDMPS_REQUIRE(code >= 0 && code <= 2, "list %d, chain %d: bad dtype code %d", side, a, code);
-      for (int j = 0; j < L; ++j)
-        NDMPS_REQUIRE((side ? h_cores_b : h_cores_a)[(int64_t)a * L + j], "list %d, chain %d, site %d: NULL core", side, a, j);
-    }
+  if (symmetric) NDMPS_TRY(ndmps::check_symmetric(p.la, p.lb));
+  NDMPS_TRY(ndmps::check_chain_cores(p.la, 0));
+  NDMPS_TRY(ndmps::check_chain_cores(p.lb, 1));
   Arena ar(d_ws, ws_bytes);
   Buffers b;
-  carve(p, h_codes_a, h_codes_b, symmetric, ar, b);
+  carve(p, symmetric, ar, b);
   if (!ar.fits()) {
     ndmps::set_error("series workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
     return NDMPS_EWORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (p.route == kRouteResident) return run_resident(p, symmetric, h_codes_a, h_cores_a, h_codes_b, h_cores_b, d_G, b, s);
-  return run_general(p, symmetric, h_codes_a, h_cores_a, h_codes_b, h_cores_b, d_G, b, s);
+  if (p.route == kRouteResident) return run_resident(p, symmetric, d_G, b, s);
+  return run_general(p, symmetric, d_G, b, s);
 }

@@ -40,6 +40,7 @@
 
 #include "common.h"
 #include "gram_pass.h"
+#include "pair_host.h"
 #include "pair_product.h"
 
 namespace {
@@ -75,27 +76,10 @@ struct StepArgs {
   int slot0, nsplit;    // first slot of `list` of this launch;  shares of the frames (sketch)
 };
 
-// src (rows x cols, leading dimension ld) transposed into an LDS image, img[k][m] = src[m][k], zero outside.  A wave's
-// pass reads 16 consecutive k of four rows m and writes four consecutive m of 16 image rows.
-__device__ __forceinline__ void load_transposed(double* img, const double* __restrict__ src, int rows, int cols, int64_t ld,
-                                                int tid) {
-  asm volatile("" : "+v"(tid));  // the addresses are formed here, per call: hoisted out of a kernel's loop they spill
-  const int kk = tid & 15, mm = tid >> 4;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-      const int k = 16 * kb + kk, m = 16 * mb + mm;
-      const bool ok = k < cols && m < rows;
-      const double v = src[ok ? (int64_t)m * ld + k : 0];
-      img[pair_img(k, m)] = ok ? v : 0.0;
-    }
-}
-
 // q[ks] = src[(4 ks + lr) * stride + c_off], zero where 4 ks + lr >= klim or the lane is inactive
 __device__ __forceinline__ void load_strided(double (&q)[16], const double* __restrict__ src, int stride, int c_off, int klim,
                                              int lr, bool active) {
-  asm volatile("" : "+v"(lr));  // as in load_transposed
+  asm volatile("" : "+v"(lr));  // as in pair_load_et
   double raw[16];
 #pragma unroll
   for (int ks = 0; ks < 16; ++ks) raw[ks] = src[(active && 4 * ks + lr < klim) ? (4 * ks + lr) * stride + c_off : 0];
@@ -134,7 +118,7 @@ __global__ void __launch_bounds__(256, 2) sumsketch_env_kernel(StepArgs g) {
       load_strided(bq, g.mat, 1, ((lam0 + col) * d + i) * l1 + mu0, nm, lr, own1 && col < nl);
       if (ktiles > 1 || i == 0) {  // one k-tile: Wn stays in Et for every i
         if (kt > 0) __syncthreads();
-        load_transposed(Et, f.Wn + mu0, chi2, nm, l1, tid);
+        ndmps::pair_load_et(Et, f.Wn + mu0, chi2, nm, l1, tid);
         __syncthreads();
       }
       if (own1) {
@@ -170,13 +154,7 @@ __global__ void __launch_bounds__(256, 2) sumsketch_env_kernel(StepArgs g) {
     }
     __syncthreads();  // Z and Et are rewritten by the next i
   }
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * wave + lr + 4 * r, c = 16 * nt + lc;
-      if (row < chi && c < nl) f.W[(int64_t)row * g.l0 + lam0 + c] = acc[nt][r];
-    }
+  ndmps::pair_store_strip(f.W + lam0, g.l0, acc, chi, nl, wave, lr, lc);
 }
 
 // sketch: one workgroup per (share of the frames, i, 64-row tile of rho, 64-column chunk of lam).
@@ -205,7 +183,7 @@ __global__ void __launch_bounds__(256, 2) sumsketch_sketch_kernel(StepArgs g) {
     const int chi = f.chi, chi2 = f.chi2;
     const int tiles_b = (chi2 + 15) >> 4, steps1 = (chi + 3) >> 2, steps2 = (chi2 + 3) >> 2;
     const bool own1 = wave < tiles_b;
-    load_transposed(Mt, f.M + (int64_t)rho0 * chi, nr, chi, chi, tid);
+    ndmps::pair_load_et(Mt, f.M + (int64_t)rho0 * chi, nr, chi, chi, tid);
     ndmps::pair_load_operands<false>(aq, f.core, f.code, chi, d, chi2, i, lr, col, own1);
     load_strided(bq, f.Wn, l1, lam0 + col, chi2, lr, own2 && col < nl);
     __syncthreads();
@@ -301,7 +279,7 @@ __global__ void __launch_bounds__(256, 2) sumsketch_project_kernel(StepArgs g) {
     const int nr = min(64, g.l0 - rho0);
     const int tiles_re = (nr + 15) >> 4, steps2 = (nr + 3) >> 2;
     if (i == 0) {
-      load_transposed(Et, f.M + (int64_t)rho0 * cb, nr, cb, cb, tid);
+      ndmps::pair_load_et(Et, f.M + (int64_t)rho0 * cb, nr, cb, cb, tid);
       ndmps::pair_load_operands<kTrans>(bq, B, code_b, cb, d, cb2, 0, lr, col, own1);
     }
     load_strided(aq, g.mat, d * r1, (rho0 * d + i) * r1 + rp0 + col, nr, lr, own2 && col < np);
@@ -309,13 +287,7 @@ __global__ void __launch_bounds__(256, 2) sumsketch_project_kernel(StepArgs g) {
 #include "pair_product_step.inc"
     if (++i == d) i = 0, rho0 += 64;
   }
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * wave + lr + 4 * r, c = 16 * nt + lc;
-      if (row < np && c < cb2) f.Mn[(int64_t)(rp0 + row) * cb2 + c] = acc[nt][r];
-    }
+  ndmps::pair_store_strip(f.Mn + (int64_t)rp0 * cb2, cb2, acc, np, cb2, wave, lr, lc);
 }
 
 // shares of the frames in the sketch form: a function of the layout alone (capacities, not ranks)
@@ -388,13 +360,13 @@ int general_project(const FrameRec& f, const double* A64, const double* Q, int64
 }
 
 // Host plan of a call: the checked arguments, the output layout and the workspace carve.
-struct Plan {
+struct Plan : ndmps::SketchLayout {
   int T = 0, K = 0, L = 0;
-  std::vector<int64_t> dims, ell, bonds, m, out_off, w_off;
+  std::vector<int64_t> bonds, m, w_off;
   std::vector<int64_t> pref;  // pref[a (L + 1) + k] = sum_{b < a} chi_{b,k}
   std::vector<char> wide;          // the frame has a bond above 64: the general route
   std::vector<int64_t> wide_off;   // its site k core in the fp64 copies, at wide_off[a L + k]
-  int64_t lmax = 1, r_elems = 0, w_elems = 0, mm = 1, sq = 1, part = 1, eig = 0, wide_elems = 0, gx = 0;
+  int64_t w_elems = 0, mm = 1, part = 1, wide_elems = 0, gx = 0;
   int64_t chi(int a, int k) const { return bonds[(int64_t)a * (L + 1) + k]; }
 };
 
@@ -422,19 +394,13 @@ int make_plan(int T, int K, int L, const int64_t* h_dims, const int64_t* h_bonds
       if (p.chi(a, k) > kResident) p.wide[a] = 1;
     }
   }
-  for (int k = 0; k <= L; ++k) {
+  for (int k = 0; k <= L; ++k)
     NDMPS_REQUIRE(p.ell[k] >= 1 && p.ell[k] <= kMaxSketch, "bond %d: sketch bond %lld outside [1, %d]", k, (long long)p.ell[k],
                   kMaxSketch);
-    p.lmax = std::max(p.lmax, p.ell[k]);
-  }
-  p.out_off.assign(L + 1, 0);
   p.w_off.assign(L + 1, 0);
   for (int k = 0; k < L; ++k) {
-    const int64_t cap = p.ell[k] * p.dims[k] * p.ell[k + 1];
     NDMPS_REQUIRE(p.dims[k] * ndmps::ceil_div(p.ell[k], 64) * ndmps::ceil_div(p.ell[k + 1], 64) <= kMaxGrid, "site %d: too large", k);
-    p.out_off[k + 1] = p.out_off[k] + cap;
-    p.sq = std::max(p.sq, cap);
-    p.part = std::max(p.part, sketch_split(T, p.dims[k], p.ell[k], p.ell[k + 1]) * cap);
+    p.part = std::max(p.part, sketch_split(T, p.dims[k], p.ell[k], p.ell[k + 1]) * p.ell[k] * p.dims[k] * p.ell[k + 1]);
     p.mm = std::max(p.mm, p.ell[k] * p.m[k]);
     if (k >= 1) {
       p.w_off[k] = p.w_elems;
@@ -447,10 +413,7 @@ int make_plan(int T, int K, int L, const int64_t* h_dims, const int64_t* h_bonds
       p.wide_elems += p.chi(a, k) * p.dims[k] * p.chi(a, k + 1);
       p.gx = std::max(p.gx, p.ell[k] * p.dims[k] * p.chi(a, k + 1));
     }
-  p.r_elems = p.out_off[L];
-  p.eig = ndmps_syevj_workspace_bytes(p.lmax);
-  NDMPS_REQUIRE(p.eig >= 0, "internal: eigen-solver workspace");
-  return NDMPS_OK;
+  return ndmps::fill_sketch_layout(p);
 }
 
 struct Buffers {
@@ -480,11 +443,7 @@ void carve(const Plan& p, Arena& ar, Buffers& b) {
   b.S = ar.take<double>(p.sq);
   b.Q = ar.take<double>(p.sq);
   b.P = ar.take<double>(p.part);
-  b.gw.G = ar.take<double>(p.lmax * p.lmax);
-  b.gw.V = ar.take<double>(p.lmax * p.lmax);
-  b.gw.w = ar.take<double>(p.lmax);
-  b.gw.ev = ar.take<char>(std::max<int64_t>(p.eig, 1));
-  b.gw.eig = p.eig;
+  b.gw = ndmps::carve_gram_pass(ar, p.lmax, p.eig);
   b.rec = ar.take<FrameRec>((int64_t)p.T * p.L);
   b.list = ar.take<int>(2 * (int64_t)p.T);
   if (p.wide_elems > 0) {
@@ -575,11 +534,8 @@ extern "C" int ndmps_sumsketch_step(int form, int T, int64_t d, const int64_t* h
   bool add = !hl.empty();
   for (int a = 0; a < T; ++a) {
     if (!w64[a]) continue;
-    const double* A64 = (const double*)h_cores[a];
-    if (h_codes[a] != 2) {
-      NDMPS_TRY(ndmps::widen(h_cores[a], h_codes[a], h_chi[a] * d * h_chi2[a], w64[a], s));
-      A64 = w64[a];
-    }
+    const double* A64;
+    NDMPS_TRY(ndmps::core64(h_cores[a], h_codes[a], h_chi[a] * d * h_chi2[a], w64[a], s, &A64));
     if (form == 0) NDMPS_TRY(general_env(h[a], A64, d_mat, d, l0, l1, GX, s));
     if (form == 1) NDMPS_TRY(general_sketch(h[a], A64, d, l0, l1, add, d_out, Sg, GX, s));
     if (form == 2) NDMPS_TRY(general_project(h[a], A64, d_mat, d, l0, l1, GX, s));
@@ -601,7 +557,7 @@ extern "C" int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims
     for (int k = 0; k < L; ++k) NDMPS_REQUIRE(h_cores[(int64_t)a * L + k], "frame %d, site %d: NULL core", a, k);
   }
   for (int64_t e = 0; e < (int64_t)K * T; ++e) NDMPS_REQUIRE(std::isfinite(h_weights[e]), "non-finite weight");
-  NDMPS_REQUIRE(r_len == p.r_elems, "the sketch cores have %lld elements, expected %lld", (long long)r_len, (long long)p.r_elems);
+  NDMPS_TRY(ndmps::check_sketch_cores(p, r_len));
   const int64_t chain = p.out_off[L];
   NDMPS_REQUIRE(out_elems >= K * chain, "output arena too small: %lld < %lld", (long long)out_elems, (long long)(K * chain));
   Arena ar(d_ws, ws_bytes);
@@ -640,13 +596,12 @@ extern "C" int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims
     NDMPS_CHECK_HIP(hipMemcpyAsync(b.list, env_list.data(), env_list.size() * sizeof(int), hipMemcpyHostToDevice, s));
 
   // general route: the fp64 cores of the wide frames that are used
-  auto core64 = [&](int a, int k) -> const double* {
-    return h_codes[a] == 2 ? (const double*)h_cores[(int64_t)a * L + k] : b.wcores + p.wide_off[(int64_t)a * L + k];
-  };
+  std::vector<const double*> A64((size_t)T * L, nullptr);
   for (int a : env_wide)
-    for (int k = 0; k < L && h_codes[a] != 2; ++k)
-      NDMPS_TRY(ndmps::widen(h_cores[(int64_t)a * L + k], h_codes[a], p.chi(a, k) * p.dims[k] * p.chi(a, k + 1),
-                             b.wcores + p.wide_off[(int64_t)a * L + k], s));
+    for (int k = 0; k < L; ++k) {
+      const int64_t e = (int64_t)a * L + k;
+      NDMPS_TRY(ndmps::core64(h_cores[e], h_codes[a], p.chi(a, k) * p.dims[k] * p.chi(a, k + 1), b.wcores + p.wide_off[e], s, &A64[e]));
+    }
 
   StepArgs g;
   g.list = b.list, g.slot0 = 0, g.nsplit = 1, g.out = nullptr;
@@ -656,7 +611,7 @@ extern "C" int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims
     g.n = (int)env_list.size(), g.d = (int)p.dims[k], g.l0 = (int)p.ell[k], g.l1 = (int)p.ell[k + 1];
     if (g.n > 0) NDMPS_TRY(launch_env(g, s));
     for (int a : env_wide)
-      NDMPS_TRY(general_env(h[(int64_t)k * T + a], core64(a, k), g.mat, p.dims[k], p.ell[k], p.ell[k + 1], b.GX, s));
+      NDMPS_TRY(general_env(h[(int64_t)k * T + a], A64[(int64_t)a * L + k], g.mat, p.dims[k], p.ell[k], p.ell[k + 1], b.GX, s));
   }
 
   // ---- 2. forward pass, one output row at a time
@@ -693,7 +648,7 @@ extern "C" int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims
       if (n > 0) NDMPS_TRY(launch_sketch(g, S, b.P, s));
       bool add = n > 0;
       for (int a : fwd_wide) {
-        NDMPS_TRY(general_sketch(h[(int64_t)k * T + a], core64(a, k), p.dims[k], r, p.ell[k + 1], add, S, b.Q, b.GX, s));
+        NDMPS_TRY(general_sketch(h[(int64_t)k * T + a], A64[(int64_t)a * L + k], p.dims[k], r, p.ell[k + 1], add, S, b.Q, b.GX, s));
         add = true;
       }
       if (k == L - 1) break;
@@ -709,7 +664,7 @@ extern "C" int ndmps_sumsketch_sketch(int T, int K, int L, const int64_t* h_dims
       g.mat = out + p.out_off[k];
       g.l1 = (int)r2;
       if (n > 0) NDMPS_TRY(launch_project(g, s));
-      for (int a : fwd_wide) NDMPS_TRY(general_project(h[(int64_t)k * T + a], core64(a, k), g.mat, p.dims[k], r, r2, b.GX, s));
+      for (int a : fwd_wide) NDMPS_TRY(general_project(h[(int64_t)k * T + a], A64[(int64_t)a * L + k], g.mat, p.dims[k], r, r2, b.GX, s));
       r = r2;
     }
     if (zero) {

@@ -26,14 +26,15 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_host.h"
 #include "pair_product.h"
 
 namespace {
 
 using ndmps::Arena;
+using ndmps::ChainList;
 using ndmps::grid1d;
 using ndmps::round_up;
-using ndmps::widen;
 
 constexpr int kResident = ndmps::kPairResident;  // largest inner bond of the resident sandwich
 constexpr int64_t kGemmColumns = 1 << 19;        // columns of one weight product (ndmps_dgemm: n / 16 < 65536)
@@ -41,17 +42,12 @@ constexpr int64_t kGemmColumns = 1 << 19;        // columns of one weight produc
 enum { kRouteResident = 0, kRoutePerPair = 2 };
 
 struct WgramArgs {
-  const void* const* cores_a;  // Ka x L
-  const void* const* cores_b;  // Kb x L
-  const int* bonds_a;          // Ka x (L + 1)
-  const int* bonds_b;          // Kb x (L + 1)
-  const int* codes_a;          // storage codes: 0 fp32, 1 bf16, 2 fp64
-  const int* codes_b;
-  const int* pairs;            // (a, b) of every pair of the call
-  const double* E;             // [w][pair of the chunk][slot_e]; not read at site 0
-  double* P;                   // [(w, i)][pair of the chunk][slot_p]
+  ndmps::PairListArgs t;   // the tables of both lists
+  const int* pairs;        // (a, b) of every pair of the call
+  const double* E;         // [w][pair of the chunk][slot_e]; not read at site 0
+  double* P;               // [(w, i)][pair of the chunk][slot_p]
   int64_t slot_e, slot_p;
-  int L, j, d, cw, n, p0;      // site, its physical dim, chi_{w,j}, pairs of the chunk, its first pair
+  int j, d, cw, n, p0;     // site, its physical dim, chi_{w,j}, pairs of the chunk, its first pair
 };
 
 // One workgroup's sandwich  P[w, i] = A_i^T E[w] B_i  of one pair at site j: E[w] comes from the workspace and is
@@ -64,17 +60,17 @@ __global__ void __launch_bounds__(256, 2) series_wgram_site_kernel(WgramArgs g) 
   __shared__ double Et[kLd * kLd];
   __shared__ double Z[kLd * kLd];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
-  const int d = g.d, L = g.L, j = g.j;
+  const int d = g.d, L = g.t.L, j = g.j;
   const int64_t wd = (int64_t)g.cw * d;
   const int q = (int)(blockIdx.x / wd);
   if (q >= g.n) return;
   const int rem = (int)(blockIdx.x % wd), w = rem / d, i = rem % d, i1 = i + 1;
   const int a = g.pairs[2 * (int64_t)(g.p0 + q)], b = g.pairs[2 * (int64_t)(g.p0 + q) + 1];
-  const int ca = g.bonds_a[(int64_t)a * (L + 1) + j], ca2 = g.bonds_a[(int64_t)a * (L + 1) + j + 1];
-  const int cb = g.bonds_b[(int64_t)b * (L + 1) + j], cb2 = g.bonds_b[(int64_t)b * (L + 1) + j + 1];
-  const int code_a = g.codes_a[a], code_b = g.codes_b[b];
-  const void* A = g.cores_a[(int64_t)a * L + j];
-  const void* B = g.cores_b[(int64_t)b * L + j];
+  const int ca = g.t.bonds_a[(int64_t)a * (L + 1) + j], ca2 = g.t.bonds_a[(int64_t)a * (L + 1) + j + 1];
+  const int cb = g.t.bonds_b[(int64_t)b * (L + 1) + j], cb2 = g.t.bonds_b[(int64_t)b * (L + 1) + j + 1];
+  const int code_a = g.t.codes_a[a], code_b = g.t.codes_b[b];
+  const void* A = g.t.cores_a[(int64_t)a * L + j];
+  const void* B = g.t.cores_b[(int64_t)b * L + j];
   // E is ca x cb, P ca2 x cb2
   const int tiles_re = (ca + 15) >> 4, tiles_ro = (ca2 + 15) >> 4, tiles_co = (cb2 + 15) >> 4;
   const int steps1 = (cb + 3) >> 2, steps2 = (ca + 3) >> 2;
@@ -89,8 +85,8 @@ __global__ void __launch_bounds__(256, 2) series_wgram_site_kernel(WgramArgs g) 
 
   // ---- E[w] of this pair, transposed into Et: Et[k][m] = E[m][k], zero outside ca x cb
   if (j == 0) {
-    for (int e = tid; e < kLd * kLd; e += 256) Et[e] = e == 0 ? 1.0 : 0.0;
-  } else {
+    ndmps::pair_set_unit(Et, tid);
+  } else {  // this kernel's own spelling of pair_load_et: with the helper's address pin it measured slower
     const double* E = g.E + ((int64_t)w * g.n + q) * g.slot_e;
     const int kk = tid & 15, mm = tid >> 4;
 #pragma unroll
@@ -107,6 +103,7 @@ __global__ void __launch_bounds__(256, 2) series_wgram_site_kernel(WgramArgs g) 
   __syncthreads();
 #include "pair_product_step.inc"
 
+  // and of pair_store_strip, so that the instructions stay those that were measured
   double* out = g.P + (((int64_t)w * d + i) * g.n + q) * g.slot_p;
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt)
@@ -133,13 +130,9 @@ struct Plan {
   int Ka = 0, Kb = 0, L = 0, route = 0, symmetric = 0;
   int64_t n_pairs = 0;
   std::vector<int64_t> dims;
-  const int64_t *ba = nullptr, *bb = nullptr, *bw = nullptr;
+  ChainList la, lb, lw;  // the weight is a list of one; codes and cores: set by the entry point
+  const int64_t* bw = nullptr;
   int64_t e_pair = 1, p_pair = 1, t_pair = 1;  // doubles of one pair: E (one of two), P, and T of the general route
-  int64_t chi_a(int a, int j) const { return ba[(int64_t)a * (L + 1) + j]; }
-  int64_t chi_b(int b, int j) const { return bb[(int64_t)b * (L + 1) + j]; }
-  int64_t core_a(int a, int j) const { return chi_a(a, j) * dims[j] * chi_a(a, j + 1); }
-  int64_t core_b(int b, int j) const { return chi_b(b, j) * dims[j] * chi_b(b, j + 1); }
-  int64_t core_w(int j) const { return bw[j] * dims[j] * bw[j + 1]; }
   // bytes of one pair of a chunk: two E and one P, each a whole number of 256-byte pieces
   int64_t pair_bytes() const { return 2 * round_up(8 * e_pair, 256) + round_up(8 * p_pair, 256); }
 };
@@ -153,36 +146,24 @@ int make_plan(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const
   p.Kb = Kb;
   p.L = L;
   p.symmetric = symmetric != 0;
-  p.ba = ba;
-  p.bb = bb;
+  p.la.count = Ka, p.la.L = L, p.la.dims = h_dims, p.la.bonds = ba;
+  p.lb.count = Kb, p.lb.L = L, p.lb.dims = h_dims, p.lb.bonds = bb;
+  p.lw.count = 1, p.lw.L = L, p.lw.dims = h_dims, p.lw.bonds = bw;
   p.bw = bw;
   p.dims.assign(h_dims, h_dims + L);
   for (int j = 0; j < L; ++j)
     NDMPS_REQUIRE(p.dims[j] >= 1 && p.dims[j] <= INT32_MAX, "site %d: bad physical dim %lld", j, (long long)p.dims[j]);
-  int64_t top = 1;
-  for (int side = 0; side < 3; ++side) {
-    const int64_t* bl = side == 0 ? ba : side == 1 ? bb : bw;
-    for (int a = 0; a < (side == 0 ? Ka : side == 1 ? Kb : 1); ++a) {
-      const int64_t* row = bl + (int64_t)a * (L + 1);
-      NDMPS_REQUIRE(row[0] == 1 && row[L] == 1, "list %d (2: the weight), chain %d: the outer bonds must be 1", side, a);
-      for (int j = 0; j <= L; ++j) {
-        NDMPS_REQUIRE(row[j] >= 1 && row[j] <= (1 << 20), "list %d, chain %d, bond %d: bad bond %lld", side, a, j,
-                      (long long)row[j]);
-        if (side < 2) top = std::max(top, row[j]);
-      }
-    }
-  }
-  if (p.symmetric) {
-    NDMPS_REQUIRE(Ka == Kb, "a symmetric series needs one list (Ka = %d, Kb = %d)", Ka, Kb);
-    for (int64_t e = 0; e < (int64_t)Ka * (L + 1); ++e)
-      NDMPS_REQUIRE(ba[e] == bb[e], "a symmetric series needs the same bonds in both lists");
-  }
+  int64_t top = 1;  // of the two lists: the weight's bonds are unrestricted
+  NDMPS_TRY(ndmps::check_chain_bonds(p.la, 0, " (2: the weight)", &top));
+  NDMPS_TRY(ndmps::check_chain_bonds(p.lb, 1, " (2: the weight)", &top));
+  NDMPS_TRY(ndmps::check_chain_bonds(p.lw, 2, " (2: the weight)", nullptr));
+  if (p.symmetric) NDMPS_TRY(ndmps::check_symmetric(p.la, p.lb));
   p.n_pairs = p.symmetric ? (int64_t)Ka * (Ka + 1) / 2 : (int64_t)Ka * Kb;
   p.route = top <= kResident ? kRouteResident : kRoutePerPair;
   std::vector<int64_t> amax(L + 1, 1), bmax(L + 1, 1);  // per bond, the largest of either list: bounds over all pairs
   for (int j = 0; j <= L; ++j) {
-    for (int a = 0; a < Ka; ++a) amax[j] = std::max(amax[j], p.chi_a(a, j));
-    for (int b = 0; b < Kb; ++b) bmax[j] = std::max(bmax[j], p.chi_b(b, j));
+    for (int a = 0; a < Ka; ++a) amax[j] = std::max(amax[j], p.la.chi(a, j));
+    for (int b = 0; b < Kb; ++b) bmax[j] = std::max(bmax[j], p.lb.chi(b, j));
   }
   for (int j = 0; j <= L; ++j) p.e_pair = std::max(p.e_pair, bw[j] * amax[j] * bmax[j]);
   for (int j = 0; j < L; ++j) {
@@ -194,38 +175,24 @@ int make_plan(int Ka, int Kb, int symmetric, int L, const int64_t* h_dims, const
 }
 
 struct Buffers {
-  // resident: the tables of WgramArgs
-  const void** cores = nullptr;
-  int *bonds = nullptr, *codes = nullptr, *pairs = nullptr;
-  // the widened cores (null where a core is fp64 already); a and b on the general route only
-  std::vector<double*> wa, wb, ww;
+  ndmps::ChainTables tables;  // resident: the tables of WgramArgs
+  int* pairs = nullptr;
+  ndmps::WidenedLists w;    // the general route's cores in fp64
+  std::vector<double*> ww;  // room for the weight's (null where it is fp64 already)
   // per chunk: two E, one P, and T on the general route
   double *E[2] = {nullptr, nullptr}, *P = nullptr, *T = nullptr;
 };
 
 // what does not grow with the chunk.  Without codes (the size query) every core counts as if it had to be widened.
-void carve_fixed(const Plan& p, const int* codes_a, const int* codes_b, const int* code_w, Arena& ar, Buffers& b) {
-  const int64_t K = (int64_t)p.Ka + p.Kb;
+void carve_fixed(const Plan& p, Arena& ar, Buffers& b) {
   if (p.route == kRouteResident) {
-    b.cores = ar.take<const void*>(K * p.L);
-    b.bonds = ar.take<int>(K * (p.L + 1));
-    b.codes = ar.take<int>(K);
+    b.tables.carve(p.la, p.lb, ar);
   } else {
-    b.wa.assign((size_t)p.Ka * p.L, nullptr);
-    b.wb.assign((size_t)p.Kb * p.L, nullptr);
-    for (int a = 0; a < p.Ka; ++a)
-      for (int j = 0; j < p.L; ++j)
-        if (!codes_a || codes_a[a] != 2) b.wa[(size_t)a * p.L + j] = ar.take<double>(p.core_a(a, j));
-    if (!p.symmetric || !codes_a)
-      for (int c = 0; c < p.Kb; ++c)
-        for (int j = 0; j < p.L; ++j)
-          if (!codes_b || codes_b[c] != 2) b.wb[(size_t)c * p.L + j] = ar.take<double>(p.core_b(c, j));
+    b.w.carve(p.la, p.lb, p.symmetric, ar);
     b.T = ar.take<double>(p.t_pair);
   }
   b.pairs = ar.take<int>(2 * p.n_pairs);
-  b.ww.assign((size_t)p.L, nullptr);
-  for (int j = 0; j < p.L; ++j)
-    if (!code_w || *code_w != 2) b.ww[j] = ar.take<double>(p.core_w(j));
+  ndmps::carve_list64(p.lw, ar, b.ww);
 }
 
 // the buffers of a chunk of n pairs: whole 256-byte pieces per pair, so that a cap maps to n without a remainder
@@ -236,10 +203,11 @@ void carve_chunk(const Plan& p, int64_t n, Arena& ar, Buffers& b) {
 }
 
 // pairs per chunk under a workspace of `cap` bytes: all of them if they fit, at least one, else NDMPS_EWORKSPACE
-int64_t chunk_for(const Plan& p, int64_t cap) {
+int64_t chunk_for(Plan p, int64_t cap) {
+  p.la.codes = p.lb.codes = p.lw.codes = nullptr;  // as the size query counts
   Arena ar(nullptr, 0);
   Buffers b;
-  carve_fixed(p, nullptr, nullptr, nullptr, ar, b);
+  carve_fixed(p, ar, b);
   const int64_t room = cap - 256 - round_up(ar.used, 256);
   int64_t n = room < 0 ? 0 : room / p.pair_bytes();
   if (n < 1) {
@@ -251,30 +219,6 @@ int64_t chunk_for(const Plan& p, int64_t cap) {
   int64_t grid = 1;  // the site kernel's grid is n chi_w d workgroups
   for (int j = 0; j < p.L; ++j) grid = std::max(grid, p.bw[j] * p.dims[j]);
   return std::min({n, p.n_pairs, (int64_t)INT32_MAX / grid});
-}
-
-struct Weight {
-  std::vector<const double*> W;  // the weight's cores in fp64
-};
-
-int widen_weight(const Plan& p, int code_w, const void* const* cores_w, const Buffers& b, Weight& wt, hipStream_t s) {
-  wt.W.resize(p.L);
-  for (int j = 0; j < p.L; ++j) {
-    wt.W[j] = (const double*)cores_w[j];
-    if (code_w != 2) {
-      NDMPS_TRY(widen(cores_w[j], code_w, p.core_w(j), b.ww[j], s));
-      wt.W[j] = b.ww[j];
-    }
-  }
-  return NDMPS_OK;
-}
-
-std::vector<int> pair_table(const Plan& p) {
-  std::vector<int> t;
-  t.reserve((size_t)2 * p.n_pairs);
-  for (int a = 0; a < p.Ka; ++a)
-    for (int c = p.symmetric ? a : 0; c < p.Kb; ++c) t.push_back(a), t.push_back(c);
-  return t;
 }
 
 // E' (cw2 x cols) = W_j (cw d x cw2)^T P (cw d x cols), in pieces of kGemmColumns columns (columns are independent)
@@ -293,37 +237,21 @@ int gather(const Plan& p, const double* E, int64_t slot, const int* d_pairs, int
   return NDMPS_OK;
 }
 
-int run_resident(const Plan& p, int64_t chunk, const int* codes_a, const void* const* cores_a, const int* codes_b,
-                 const void* const* cores_b, const Weight& wt, double* d_G, const Buffers& b, hipStream_t s) {
-  const int L = p.L, Ka = p.Ka, Kb = p.Kb;
-  std::vector<const void*> hc(cores_a, cores_a + (size_t)Ka * L);
-  hc.insert(hc.end(), cores_b, cores_b + (size_t)Kb * L);
-  std::vector<int> hb((size_t)(Ka + Kb) * (L + 1)), hk(codes_a, codes_a + Ka);
-  for (size_t e = 0; e < (size_t)Ka * (L + 1); ++e) hb[e] = (int)p.ba[e];
-  for (size_t e = 0; e < (size_t)Kb * (L + 1); ++e) hb[(size_t)Ka * (L + 1) + e] = (int)p.bb[e];
-  hk.insert(hk.end(), codes_b, codes_b + Kb);
-  const std::vector<int> hp = pair_table(p);
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.cores, hc.data(), hc.size() * sizeof(void*), hipMemcpyHostToDevice, s));
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.bonds, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  NDMPS_CHECK_HIP(hipMemcpyAsync(b.codes, hk.data(), hk.size() * sizeof(int), hipMemcpyHostToDevice, s));
+int run_resident(const Plan& p, int64_t chunk, const std::vector<const double*>& W, double* d_G, Buffers& b, hipStream_t s) {
+  const int L = p.L;
+  WgramArgs g;
+  NDMPS_TRY(b.tables.upload(p.la, p.lb, s, g.t));
+  const std::vector<int> hp = ndmps::pair_table(p.Ka, p.Kb, p.symmetric);
   NDMPS_CHECK_HIP(hipMemcpyAsync(b.pairs, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));  // the host vectors go out of scope; nothing waits after the launches
-  WgramArgs g;
-  g.cores_a = b.cores;
-  g.cores_b = b.cores + (size_t)Ka * L;
-  g.bonds_a = b.bonds;
-  g.bonds_b = b.bonds + (size_t)Ka * (L + 1);
-  g.codes_a = b.codes;
-  g.codes_b = b.codes + Ka;
   g.pairs = b.pairs;
-  g.L = L;
   for (int64_t p0 = 0; p0 < p.n_pairs; p0 += chunk) {
     const int64_t n = std::min(chunk, p.n_pairs - p0);
     // slot of bond j: the largest chi_a chi_b of the chunk
     std::vector<int64_t> slot(L + 1, 1);
     for (int64_t q = 0; q < n; ++q) {
       const int a = hp[2 * (p0 + q)], c = hp[2 * (p0 + q) + 1];
-      for (int j = 0; j <= L; ++j) slot[j] = std::max(slot[j], p.chi_a(a, j) * p.chi_b(c, j));
+      for (int j = 0; j <= L; ++j) slot[j] = std::max(slot[j], p.la.chi(a, j) * p.lb.chi(c, j));
     }
     int cur = 0;
     for (int j = 0; j < L; ++j) {
@@ -339,7 +267,7 @@ int run_resident(const Plan& p, int64_t chunk, const int* codes_a, const void* c
       g.p0 = (int)p0;
       hipLaunchKernelGGL(series_wgram_site_kernel, dim3((unsigned)(n * cw * d)), dim3(256), 0, s, g);
       NDMPS_LAUNCH_CHECK();
-      NDMPS_TRY(weight_product(wt.W[j], cw, d, cw2, n * slot[j + 1], b.P, b.E[cur ^ 1], s));
+      NDMPS_TRY(weight_product(W[j], cw, d, cw2, n * slot[j + 1], b.P, b.E[cur ^ 1], s));
       cur ^= 1;
     }
     NDMPS_TRY(gather(p, b.E[cur], slot[L], b.pairs, p0, n, d_G, s));
@@ -347,61 +275,24 @@ int run_resident(const Plan& p, int64_t chunk, const int* codes_a, const void* c
   return NDMPS_OK;
 }
 
-int run_general(const Plan& p, const int* codes_a, const void* const* cores_a, const int* codes_b, const void* const* cores_b,
-                const Weight& wt, double* d_G, const Buffers& b, hipStream_t s) {
-  const int L = p.L, Ka = p.Ka, Kb = p.Kb;
-  std::vector<const double*> A((size_t)Ka * L), B((size_t)Kb * L);
-  for (int a = 0; a < Ka; ++a)
-    for (int j = 0; j < L; ++j) {
-      const size_t e = (size_t)a * L + j;
-      A[e] = (const double*)cores_a[e];
-      if (codes_a[a] != 2) {
-        NDMPS_TRY(widen(cores_a[e], codes_a[a], p.core_a(a, j), b.wa[e], s));
-        A[e] = b.wa[e];
-      }
-    }
-  for (int c = 0; c < Kb; ++c)
-    for (int j = 0; j < L; ++j) {
-      const size_t e = (size_t)c * L + j;
-      if (p.symmetric) {
-        B[e] = A[e];
-        continue;
-      }
-      B[e] = (const double*)cores_b[e];
-      if (codes_b[c] != 2) {
-        NDMPS_TRY(widen(cores_b[e], codes_b[c], p.core_b(c, j), b.wb[e], s));
-        B[e] = b.wb[e];
-      }
-    }
-  const std::vector<int> hp = pair_table(p);
+int run_general(const Plan& p, const std::vector<const double*>& W, double* d_G, Buffers& b, hipStream_t s) {
+  const int L = p.L;
+  NDMPS_TRY(b.w.fill(p.la, p.lb, p.symmetric, s));
+  const std::vector<int> hp = ndmps::pair_table(p.Ka, p.Kb, p.symmetric);
   NDMPS_CHECK_HIP(hipMemcpyAsync(b.pairs, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));
   static const double one = 1.0;
-  const int batch = ndmps_gemm_batched_max();
-  std::vector<const double*> pa(batch), pb(batch);
-  std::vector<double*> pc(batch);
   for (int64_t q = 0; q < p.n_pairs; ++q) {
     const int a = hp[2 * q], c = hp[2 * q + 1];
     int cur = 0;
     NDMPS_CHECK_HIP(hipMemcpyAsync(b.E[0], &one, sizeof(double), hipMemcpyHostToDevice, s));  // E_0 = [[1]]
     for (int j = 0; j < L; ++j) {
-      const int64_t ca = p.chi_a(a, j), ca2 = p.chi_a(a, j + 1), cb = p.chi_b(c, j), cb2 = p.chi_b(c, j + 1);
+      const int64_t ca = p.la.chi(a, j), ca2 = p.la.chi(a, j + 1), cb = p.lb.chi(c, j), cb2 = p.lb.chi(c, j + 1);
       const int64_t cw = p.bw[j], cw2 = p.bw[j + 1], d = p.dims[j];
-      const double *Aj = A[(size_t)a * L + j], *Bj = B[(size_t)c * L + j];
-      // T (cw ca x d cb2) = E (cw ca x cb) B_j (cb x d cb2)
-      NDMPS_TRY(ndmps_dgemm(0, 0, cw * ca, d * cb2, cb, b.E[cur], cb, Bj, d * cb2, b.T, d * cb2, s));
-      // P[w, i] (ca2 x cb2) = A_i^T T[w][:, i, :]
-      for (int64_t t0 = 0; t0 < cw * d; t0 += batch) {
-        const int nb = (int)std::min<int64_t>(batch, cw * d - t0);
-        for (int t = 0; t < nb; ++t) {
-          const int64_t w = (t0 + t) / d, i = (t0 + t) % d;
-          pa[t] = Aj + i * ca2;
-          pb[t] = b.T + w * ca * d * cb2 + i * cb2;
-          pc[t] = b.P + (t0 + t) * ca2 * cb2;
-        }
-        NDMPS_TRY(ndmps_dgemm_batched(nb, 1, 0, ca2, cb2, ca, pa.data(), d * ca2, pb.data(), d * cb2, pc.data(), cb2, s));
-      }
-      NDMPS_TRY(weight_product(wt.W[j], cw, d, cw2, ca2 * cb2, b.P, b.E[cur ^ 1], s));
+      // T[w] = E[w] B_j over all w, then P[w, i] (ca2 x cb2) = A_i^T T[w][:, i, :]
+      NDMPS_TRY(ndmps::sandwich_forward_general(ca, ca2, cb, cb2, d, cw, b.w.A[(size_t)a * L + j], b.w.B[(size_t)c * L + j], b.E[cur],
+                                                b.P, b.T, s));
+      NDMPS_TRY(weight_product(W[j], cw, d, cw2, ca2 * cb2, b.P, b.E[cur ^ 1], s));
       cur ^= 1;
     }
     NDMPS_TRY(gather(p, b.E[cur], 1, b.pairs, q, 1, d_G, s));
@@ -427,7 +318,7 @@ extern "C" int64_t ndmps_series_wgram_workspace_bytes(int Ka, int Kb, int symmet
   if (n < 0) return n;
   Arena ar(nullptr, 0);
   Buffers b;
-  carve_fixed(p, nullptr, nullptr, nullptr, ar, b);
+  carve_fixed(p, ar, b);
   carve_chunk(p, n, ar, b);
   return ar.query_bytes();
 }
@@ -440,32 +331,27 @@ extern "C" int ndmps_series_wgram(int Ka, int Kb, int symmetric, int L, const in
   NDMPS_REQUIRE(h_codes_a && h_cores_a && h_codes_b && h_cores_b && h_cores_w && d_G, "NULL weighted series argument");
   Plan p;
   NDMPS_TRY(make_plan(Ka, Kb, symmetric, L, h_dims, h_bonds_a, h_bonds_b, h_bonds_w, p));
-  if (p.symmetric)
-    for (int64_t e = 0; e < (int64_t)Ka * L; ++e)
-      NDMPS_REQUIRE(h_cores_a[e] == h_cores_b[e], "a symmetric series needs the same cores in both lists");
-  for (int side = 0; side < 2; ++side)
-    for (int a = 0; a < (side ? Kb : Ka); ++a) {
-      const int code = (side ? h_codes_b : h_codes_a)[a];
-      NDMPS_REQUIRE(code >= 0 && code <= 2, "list %d, chain %d: bad dtype code %d", side, a, code);
-      for (int j = 0; j < L; ++j)
-        NDMPS_REQUIRE((side ? h_cores_b : h_cores_a)[(int64_t)a * L + j], "list %d, chain %d, site %d: NULL core", side, a, j);
-    }
+  p.la.codes = h_codes_a, p.la.cores = h_cores_a;
+  p.lb.codes = h_codes_b, p.lb.cores = h_cores_b;
+  p.lw.codes = &code_w, p.lw.cores = h_cores_w;
+  if (p.symmetric) NDMPS_TRY(ndmps::check_symmetric(p.la, p.lb));  // the cores: make_plan saw the rest
+  NDMPS_TRY(ndmps::check_chain_cores(p.la, 0));
+  NDMPS_TRY(ndmps::check_chain_cores(p.lb, 1));
   NDMPS_REQUIRE(code_w >= 0 && code_w <= 2, "the weight: bad dtype code %d", code_w);
   for (int j = 0; j < L; ++j) NDMPS_REQUIRE(h_cores_w[j], "the weight, site %d: NULL core", j);
   const int64_t chunk = chunk_for(p, ws_bytes);
   if (chunk < 0) return (int)chunk;
   Arena ar(d_ws, ws_bytes);
   Buffers b;
-  carve_fixed(p, h_codes_a, h_codes_b, &code_w, ar, b);
+  carve_fixed(p, ar, b);
   carve_chunk(p, chunk, ar, b);
   if (!ar.fits()) {
     ndmps::set_error("weighted series workspace too small: %lld < %lld", (long long)ws_bytes, (long long)ar.used);
     return NDMPS_EWORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  Weight wt;
-  NDMPS_TRY(widen_weight(p, code_w, h_cores_w, b, wt, s));
-  if (p.route == kRouteResident)
-    return run_resident(p, chunk, h_codes_a, h_cores_a, h_codes_b, h_cores_b, wt, d_G, b, s);
-  return run_general(p, h_codes_a, h_cores_a, h_codes_b, h_cores_b, wt, d_G, b, s);
+  std::vector<const double*> W;  // the weight's cores in fp64
+  NDMPS_TRY(ndmps::fill_list64(p.lw, b.ww, s, W));
+  if (p.route == kRouteResident) return run_resident(p, chunk, W, d_G, b, s);
+  return run_general(p, W, d_G, b, s);
 }
