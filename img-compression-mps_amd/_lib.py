@@ -125,6 +125,16 @@ SIGNATURES = {
     "ndmps_chain_contract_scatter_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, vp, i64, vp]),
     "ndmps_chain_batched_workspace_bytes": (i64, [C.c_int, C.c_int, p_i64, p_i64]),
     "ndmps_chain_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64]),
+    "ndmps_valstat_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, i64, i64]),
+    "ndmps_valstat_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, i64, p_i64]),
+    "ndmps_valstat_moments_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_double, C.c_double, p_f64, p_i64, vp, i64, vp]),
+    "ndmps_valstat_moments_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_double, C.c_double, p_f64, p_i64, vp, i64, vp]),
+    "ndmps_valstat_histogram_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, p_i64, vp, i64, vp]),
+    "ndmps_valstat_histogram_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, p_i64, vp, i64, vp]),
+    "ndmps_valstat_error_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, p_f64, p_i64, vp, i64,
+                                          vp]),
+    "ndmps_valstat_error_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, p_f64, p_i64, vp, i64,
+                                          vp]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,
                                                            i64, vp, i64, vp]),
     "ndmps_gemm_batched_max": (C.c_int, []),

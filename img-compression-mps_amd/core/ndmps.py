@@ -2141,6 +2141,88 @@ class NDMPS:
         """``to_tensor().mean(axis=axis, keepdims=keepdims)`` without decoding the whole volume; as ``sum``."""
         return self._axis_reduce(axis, keepdims, "mean", as_torch, dtype)
 
+    # ---------------------------------------------------- value statistics on the cores (core/valstat.py)
+    def _valstat_chain(self, what, with_plan=False):
+        """The chain of a statistics call (``with_plan``: and the permutation plan of its shape, for the calls that read
+        an original), or the ValueError that refuses it."""
+        if self.mode == "DCT":
+            raise ValueError(f"DCT mode stores DCT coefficients: {what} of the chain is not {what} of the volume")
+        if self.mode != "Std":
+            raise ValueError(f"{what} needs a Std mode object, this one has mode {self.mode!r}")
+        if self.mps.dtype == _torch().bfloat16:
+            raise ValueError(f"{what} runs on fp32 or fp64 cores: convert bf16 cores with astype(torch.float32) first")
+        shape = self._require_shape()
+        return (self.mps, _plan_for(shape, self.mps.device.index or 0)) if with_plan else self.mps
+
+    def value_stats(self) -> dict:
+        """``count, min, max, sum, sumsq, n_nan`` of ``to_tensor()`` and the derived ``mean``, ``std`` (population) and
+        ``norm`` (Frobenius), without decoding the volume: the chain's last product reduces its tiles instead of storing
+        them (csrc/valstat.hip), so only the small left and tail buffers of the decode are written.  Sums are fp64; NaN
+        voxels are counted in ``n_nan`` and left out of everything else; the same object gives the same bits.  The
+        voxel values are those of ``to_tensor()`` within the forward error bound of the chain, not bit for bit.
+
+        Raises ValueError for DCT mode (the chain holds coefficients), bf16 cores (``astype(torch.float32)`` first) and
+        an unknown shape.  Std mode, fp32 and fp64 cores.  No counterpart in the reference."""
+        from . import valstat as _vs
+
+        chain = self._valstat_chain("value_stats")
+        return _vs.value_stats(chain)
+
+    def min(self, axis=None):
+        """``to_tensor().min()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError."""
+        if axis is not None:
+            raise NotImplementedError("min over an axis is not implemented: only the whole volume (axis=None)")
+        return self.value_stats()["min"]
+
+    def max(self, axis=None):
+        """``to_tensor().max()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError."""
+        if axis is not None:
+            raise NotImplementedError("max over an axis is not implemented: only the whole volume (axis=None)")
+        return self.value_stats()["max"]
+
+    def histogram(self, bins=256, range=None, outliers: bool = False):
+        """``numpy.histogram(to_tensor(), bins, range)`` from the cores: ``(counts int64, edges)``.  ``bins`` is an int
+        or an explicit ascending edge array (at most 4096 bins; the edges are cast to the cores' element type and
+        returned as used); bin b holds ``edges[b] <= v < edges[b + 1]`` and the last bin its right edge too, exactly,
+        for the voxel values the chain computes.  ``range=None`` with an int runs the moments pass first for min and
+        max.  ``outliers=True`` adds ``(n_below, n_above, n_nan)``; bins and outliers always sum to the voxel count.
+
+        Raises ValueError for more than 4096 bins, edges that are not ascending, a range that is not finite, and what
+        ``value_stats`` refuses."""
+        from . import valstat as _vs
+
+        chain = self._valstat_chain("histogram")
+        return _vs.histogram(chain, bins, range, outliers)
+
+    def quantile(self, q, passes: int = 2, bins: int = 4096):
+        """The ``q``-quantile of the voxels (rank ``ceil(q N)``, numpy's ``method="inverted_cdf"``) by repeated
+        histograms from the cores: ``(value, (lo, hi))``.  After each of up to ``passes`` histograms the bracket is the
+        one bin that holds the rank, and the next pass bins inside it; the search stops early once the bracket is one
+        number.  A last pass looks inside the bracket: one distinct value there is returned exactly, otherwise
+        ``value`` is the midpoint of the bracket ``(lo, hi)``, its smallest and largest voxel.  ValueError for ``q``
+        outside [0, 1], ``bins`` outside [1, 4096] and what ``value_stats`` refuses."""
+        from . import valstat as _vs
+
+        chain = self._valstat_chain("quantile")
+        return _vs.quantile(chain, q, passes, bins)
+
+    def error_to(self, x) -> dict:
+        """The error of ``to_tensor()`` against ``x`` (NumPy array or device tensor of the object's shape, cast to the
+        cores' element type) without decoding: ``sse, mse, max_abs, ref_sumsq, ref_max, rel_frob`` (and ``n_nan``, the
+        voxels whose difference is NaN).  ``x`` is read once, through the offset tables of the fused decode.
+        ValueError for another shape and what ``value_stats`` refuses."""
+        from . import valstat as _vs
+
+        chain, plan = self._valstat_chain("error_to", with_plan=True)
+        return _vs.error_to(chain, plan, x)
+
+    def psnr_to(self, x) -> float:
+        """``compute_psnr(x, to_tensor())`` from the cores: ``10 log10(max(x)^2 / mse)``, ``inf`` at mse = 0."""
+        from . import valstat as _vs
+
+        chain, plan = self._valstat_chain("psnr_to", with_plan=True)
+        return _vs.psnr_from(_vs.error_to(chain, plan, x))
+
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):
         """Integer-truncate each MPS tensor to the given unsigned dtype (ndmps.py:182-207)."""

@@ -1,0 +1,550 @@
+// Value statistics and the error against an original, from the cores: the chain contraction whose last product is
+// reduced in registers and LDS instead of stored, so the N voxels are never written.
+//
+//   ndmps_valstat_moments_*    <- NDMPS.value_stats / min / max      (core/valstat.py)
+//   ndmps_valstat_histogram_*  <- NDMPS.histogram / quantile
+//   ndmps_valstat_error_*      <- NDMPS.error_to / psnr_to
+//
+// chain_stats_plan (valstat_plan.h) is chain_plan with the last product's destination removed and the output's
+// role as second cumulative buffer taken by ws_left2.  Every product before the last runs through ndmps_sgemm /
+// ndmps_dgemm exactly as run_chain issues them (chain.hip); the last one is valstat_product_kernel, a tiled MFMA
+// product (v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64, lane maps as in gemm.hip) on a persistent grid whose
+// accumulator tiles are handed, element by element, to one of three epilogues:
+//
+//   Moments    count, min, max, sum, sum of squares, NaN count.  NaN voxels are counted and take no part in the rest.
+//   Histogram  np.histogram against an explicit edge table held in LDS: bin b takes edges[b] <= v < edges[b + 1], the
+//              last bin is closed on the right; below / above / NaN are counted apart.  The bin is found by binary
+//              search in the table, so it is exact for the computed v.  32-bit counters in LDS per workgroup, flushed
+//              once with 64-bit integer atomics.  Before the LDS atomic, a wavefront folds the lanes that share the
+//              first lane's bin into one add (a background of equal voxels costs one atomic per wavefront).
+//   Error      y = d_ref[row_off[r] + col_off[c]] through the additive offset tables of the fused decode:
+//              sum (v - y)^2, max |v - y|, sum y^2, max y.
+//
+// Determinism: sums are fp64 and nothing floating-point is added atomically.  A thread's elements are a fixed
+// function of the shape (tile t goes to workgroup t mod grid, the grid is a function of the tile count), a
+// workgroup folds its threads by a fixed shuffle tree and writes one partial record, and valstat_fold_kernel folds
+// the records in index order: the same inputs give the same bits.  The histogram adds integers.
+#include <math.h>
+
+#include <type_traits>
+#include <vector>
+
+#include "common.h"
+#include "typed.h"
+#include "valstat_plan.h"
+
+using ndmps::ChainKind;
+using ndmps::ChainProduct;
+using ndmps::ChainStatsPlan;
+
+namespace {
+
+using ndmps::ceil_div;
+using ndmps::f64x4;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kBM = 64, kBN = 64;  // tile of a workgroup: 2 x 2 wavefronts of 32 x 32
+
+// a partial or the result of the two record epilogues (ndmps::kValstatRecordBytes)
+struct Record {
+  double s0, s1;     // moments: sum v, sum v^2            error: sum (v - y)^2, sum y^2
+  double lo;         // moments: min                       error: unused
+  double hi0, hi1;   // moments: max, unused               error: max |v - y|, max y
+  long long c0, c1;  // voxels, NaN among them (moments: v; error: v - y)
+  long long c2;      // moments: voxels inside the clip range (the ones behind the four statistics)
+};
+static_assert(sizeof(Record) == ndmps::kValstatRecordBytes, "record layout");
+
+__device__ __forceinline__ void record_clear(Record& r) {
+  r.s0 = r.s1 = 0.0;
+  r.lo = INFINITY;
+  r.hi0 = r.hi1 = -INFINITY;
+  r.c0 = r.c1 = r.c2 = 0;
+}
+__device__ __forceinline__ void record_fold(Record& a, const Record& b) {
+  a.s0 += b.s0;
+  a.s1 += b.s1;
+  a.lo = fmin(a.lo, b.lo);
+  a.hi0 = fmax(a.hi0, b.hi0);
+  a.hi1 = fmax(a.hi1, b.hi1);
+  a.c0 += b.c0;
+  a.c1 += b.c1;
+  a.c2 += b.c2;
+}
+// lane 0 <- the wavefront's 64 records, folded by a fixed tree
+__device__ __forceinline__ void record_fold_wave(Record& r) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    Record o;
+    o.s0 = __shfl_down(r.s0, off);
+    o.s1 = __shfl_down(r.s1, off);
+    o.lo = __shfl_down(r.lo, off);
+    o.hi0 = __shfl_down(r.hi0, off);
+    o.hi1 = __shfl_down(r.hi1, off);
+    o.c0 = __shfl_down(r.c0, off);
+    o.c1 = __shfl_down(r.c1, off);
+    o.c2 = __shfl_down(r.c2, off);
+    record_fold(r, o);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ epilogues
+// take() is called by every lane of every wavefront the same number of times (valid == false: a padded row or
+// column, which contributes nothing); finish() once per workgroup.
+struct RecordArgs {
+  Record* partials;         // one per workgroup
+  const void* ref;          // error: the original, C order
+  const int64_t* row_off;   // error: [m]
+  const int64_t* col_off;   // error: [n], in the column order of B as the kernel sees it
+  int64_t numel;            // error: elements of ref
+  double clip_lo, clip_hi;  // moments: only clip_lo <= v <= clip_hi enters the four statistics
+};
+
+template <typename T, bool ERR>
+struct RecordEpi {
+  typedef RecordArgs Args;
+  Record r;
+  __device__ __forceinline__ void begin(const Args&) { record_clear(r); }
+  __device__ __forceinline__ void take(const Args& a, bool valid, int64_t row, int64_t col, T v) {
+    if (!valid) return;
+    if constexpr (ERR) {
+      const int64_t at = a.row_off[row] + a.col_off[col];
+      if (at < 0 || at >= a.numel) return;  // the tables are not trusted: nothing is read outside ref
+      const double y = (double)static_cast<const T*>(a.ref)[at];
+      const double d = (double)v - y;
+      ++r.c0;
+      if (d != d) {
+        ++r.c1;
+        return;
+      }
+      r.s0 += d * d;
+      r.s1 += y * y;
+      r.hi0 = fmax(r.hi0, fabs(d));
+      r.hi1 = fmax(r.hi1, y);
+    } else {
+      ++r.c0;
+      if (v != v) {
+        ++r.c1;
+        return;
+      }
+      const double d = (double)v;
+      if (!(d >= a.clip_lo && d <= a.clip_hi)) return;
+      ++r.c2;
+      r.s0 += d;
+      r.s1 += d * d;
+      r.lo = fmin(r.lo, d);
+      r.hi0 = fmax(r.hi0, d);
+    }
+  }
+  __device__ __forceinline__ void finish(const Args& a) {
+    __shared__ Record waves[4];
+    record_fold_wave(r);
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      Record t = waves[0];
+      for (int w = 1; w < 4; ++w) record_fold(t, waves[w]);
+      a.partials[blockIdx.x] = t;
+    }
+  }
+};
+
+struct HistArgs {
+  const void* edges;              // [bins + 1] in the element type, ascending
+  unsigned long long* counts;     // [bins + 3]: the bins, then below, above, NaN
+  int bins;
+};
+
+extern __shared__ double valstat_dyn_lds[];  // histogram: the edges, then the 32-bit counters
+
+template <typename T>
+struct HistEpi {
+  typedef HistArgs Args;
+  T* e;
+  unsigned int* cnt;
+  __device__ __forceinline__ void begin(const Args& a) {
+    e = reinterpret_cast<T*>(valstat_dyn_lds);
+    cnt = reinterpret_cast<unsigned int*>(valstat_dyn_lds + ((size_t)(a.bins + 1) * sizeof(T) + 7) / 8);
+    for (int i = threadIdx.x; i <= a.bins; i += 256) e[i] = static_cast<const T*>(a.edges)[i];
+    for (int i = threadIdx.x; i < a.bins + 3; i += 256) cnt[i] = 0u;
+    __syncthreads();
+  }
+  __device__ __forceinline__ void take(const Args& a, bool valid, int64_t, int64_t, T v) {
+    const int B = a.bins;
+    int bin = -1;
+    if (valid) {
+      if (v != v) {
+        bin = B + 2;
+      } else if (v < e[0]) {
+        bin = B;
+      } else if (v > e[B]) {
+        bin = B + 1;
+      } else {
+        int lo = 0, hi = B + 1;  // e[lo] <= v, and hi == B + 1 or v < e[hi]: the largest b with e[b] <= v
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (e[mid] <= v) lo = mid; else hi = mid;
+        }
+        bin = lo == B ? B - 1 : lo;  // v == e[B]: the last bin is closed on the right
+      }
+    }
+    // the lanes that share the first lane's bin make one add; the others add for themselves
+    const int first = __builtin_amdgcn_readfirstlane(bin);
+    const bool same = bin == first;
+    const unsigned long long mask = __ballot(same);
+    if (same) {
+      if (first >= 0 && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicAdd(&cnt[first], (unsigned int)__popcll(mask));
+    } else if (bin >= 0) {
+      atomicAdd(&cnt[bin], 1u);
+    }
+  }
+  __device__ __forceinline__ void finish(const Args& a) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < a.bins + 3; i += 256)
+      if (cnt[i]) atomicAdd(&a.counts[i], (unsigned long long)cnt[i]);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------ the product
+// C = A (m x k) B (k x n), dense row-major, tile by tile on a persistent grid; column c of B is B[:, perm[c]] when
+// perm is given (the columns in memory order of the volume, for a chain whose decode has no gather buffer).  Rows
+// and columns beyond m and n are staged as zeros and handed to the epilogue as invalid.
+template <typename T, typename Epi>
+__global__ void __launch_bounds__(256)
+valstat_product_kernel(const T* __restrict__ A, const T* __restrict__ B, const int32_t* __restrict__ perm, int64_t m,
+                       int64_t n, int64_t k, const typename Epi::Args args) {
+  constexpr int BK = sizeof(T) == 4 ? 16 : 8;
+  constexpr int PAD = 4;
+  __shared__ T As[BK][kBM + PAD];  // k-major, as gemm.hip stages them: a fragment read is consecutive words
+  __shared__ T Bs[BK][kBN + PAD];
+
+  Epi epi;
+  epi.begin(args);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const int64_t tiles_n = (n + kBN - 1) / kBN, tiles = (m + kBM - 1) / kBM * tiles_n;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t m0 = (t / tiles_n) * kBM, n0 = (t % tiles_n) * kBN;
+    typename std::conditional<sizeof(T) == 4, f32x16, f64x4>::type acc[sizeof(T) == 4 ? 1 : 4];
+    for (auto& a : acc)
+      for (int r = 0; r < (sizeof(T) == 4 ? 16 : 4); ++r) a[r] = (T)0;
+
+    for (int64_t k0 = 0; k0 < k; k0 += BK) {
+      for (int e = tid; e < kBM * BK; e += 256) {
+        const int r = e / BK, kk = e % BK;
+        const int64_t gr = m0 + r, gk = k0 + kk;
+        As[kk][r] = (gr < m && gk < k) ? A[gr * k + gk] : (T)0;
+      }
+      for (int e = tid; e < BK * kBN; e += 256) {
+        const int kk = e / kBN, c = e % kBN;
+        const int64_t gk = k0 + kk;
+        int64_t gc = n0 + c;
+        bool ok = gc < n && gk < k;
+        if (ok && perm) {
+          gc = perm[gc];
+          ok = gc >= 0 && gc < n;
+        }
+        Bs[kk][c] = ok ? B[gk * n + gc] : (T)0;
+      }
+      __syncthreads();
+      if constexpr (sizeof(T) == 4) {
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2)
+          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + (lane >> 5)][wm + (lane & 31)],
+                                                        Bs[kk + (lane >> 5)][wn + (lane & 31)], acc[0], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 4) {
+          double a[2], b[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            a[i] = As[kk + (lane >> 4)][wm + 16 * i + (lane & 15)];
+            b[i] = Bs[kk + (lane >> 4)][wn + 16 * i + (lane & 15)];
+          }
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[2 * i + j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[2 * i + j], 0, 0, 0);
+        }
+      }
+      __syncthreads();
+    }
+
+    if constexpr (sizeof(T) == 4) {
+      const int64_t col = n0 + wn + (lane & 31);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        epi.take(args, row < m && col < n, row, col, acc[0][r]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int64_t col = n0 + wn + 16 * j + (lane & 15);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int64_t row = m0 + wm + 16 * i + (lane >> 4) + 4 * r;
+            epi.take(args, row < m && col < n, row, col, acc[2 * i + j][r]);
+          }
+        }
+    }
+  }
+  epi.finish(args);
+}
+
+// result <- the partial records folded in index order (one wavefront)
+__global__ void __launch_bounds__(64) valstat_fold_kernel(const Record* __restrict__ partials, int count, Record* result) {
+  Record r;
+  record_clear(r);
+  for (int i = threadIdx.x; i < count; i += 64) record_fold(r, partials[i]);
+  record_fold_wave(r);
+  if (threadIdx.x == 0) *result = r;
+}
+
+// out (rows x cols) <- the columns perm[0], perm[1], ... of in (chain.hip's gather_cols_kernel in the element type);
+// a perm entry outside [0, cols) gives a zero column
+template <typename T>
+__global__ void __launch_bounds__(256)
+valstat_gather_cols_kernel(const T* __restrict__ in, T* __restrict__ out, int64_t rows, int64_t cols,
+                           const int32_t* __restrict__ perm) {
+  const int64_t total = rows * cols;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t p = perm[e % cols];
+    out[e] = (p >= 0 && p < cols) ? in[(e / cols) * cols + p] : (T)0;
+  }
+}
+
+template <typename T>
+__global__ void valstat_unit_kernel(T* p) { *p = (T)1; }
+
+// ------------------------------------------------------------------------------------------------ host
+struct ErrorTables {
+  const void* ref;
+  const int64_t* row_off;
+  const int64_t* col_off;
+  const int32_t* col_perm;
+  int64_t n_cols;
+};
+
+// The argument check of every entry, before its first launch (chain_check's conditions on the chain itself).
+template <typename T>
+int valstat_check(const ChainStatsPlan& sp, const int64_t* dims, const int64_t* bonds, const T* const* cores,
+                  const void* d_ws, int64_t ws_bytes, const ErrorTables* err) {
+  const ndmps::ChainPlan& p = sp.chain;
+  const int L = p.L;
+  NDMPS_REQUIRE(cores, "bad valstat argument");
+  NDMPS_REQUIRE(bonds[0] == 1 && bonds[L] == 1, "open boundary bonds must be 1");
+  for (int i = 0; i < L; ++i)
+    NDMPS_REQUIRE(dims[i] >= 1 && cores[i], "dims[%d] must be positive and core %d non-NULL", i, i);
+  int64_t left = 1;
+  for (int i = 0; i < L; ++i) {
+    left *= dims[i];
+    NDMPS_REQUIRE(bonds[i + 1] >= 1 && bonds[i + 1] <= left && bonds[i + 1] <= p.numel / left,
+                  "bond %d = %lld exceeds min(%lld, %lld), the rank any unfolding can have", i + 1,
+                  (long long)bonds[i + 1], (long long)left, (long long)(p.numel / left));
+  }
+  if (!d_ws || ws_bytes < sp.total_bytes) {
+    ndmps::set_error("valstat workspace too small: %lld < %lld", (long long)ws_bytes, (long long)sp.total_bytes);
+    return NDMPS_EWORKSPACE;
+  }
+  NDMPS_REQUIRE(((uintptr_t)d_ws & 255) == 0, "valstat workspace must be 256-byte aligned");
+  if (err) {
+    NDMPS_REQUIRE(err->ref && err->row_off && err->col_off && err->col_perm, "NULL original or offset table");
+    NDMPS_REQUIRE(err->n_cols == sp.reduced.n, "offset tables are for %lld columns, the last product has %lld",
+                  (long long)err->n_cols, (long long)sp.reduced.n);
+  }
+  return NDMPS_OK;
+}
+
+struct Operands {
+  const void *A, *B;
+  const int32_t* perm;  // column order of B inside the product kernel, NULL: as stored
+};
+
+// Runs every product before the last as run_chain does and returns the operands of the last one.  gather: the
+// columns of its right operand are wanted in the order col_perm (the error epilogue).
+template <typename T>
+int valstat_run_chain(const ChainStatsPlan& sp, const T* const* cores, void* d_ws, const int32_t* col_perm, hipStream_t s,
+                      Operands* ops) {
+  const ndmps::ChainPlan& p = sp.chain;
+  char* ws = (char*)d_ws;
+  auto at = [&](int id) -> T* {
+    switch (id) {
+      case ndmps::kChainLeft: return (T*)(ws + p.off_left);
+      case ndmps::kChainLeft2: return (T*)(ws + sp.off_left2);
+      case ndmps::kChainTail0: return (T*)(ws + p.off_tail0);
+      case ndmps::kChainTail1: return (T*)(ws + p.off_tail1);
+      case ndmps::kChainUnit: return (T*)(ws + sp.off_unit);
+      default: return const_cast<T*>(cores[id]);
+    }
+  };
+  for (size_t i = 0; i + 1 < p.products.size(); ++i) {
+    const ChainProduct& q = p.products[i];
+    NDMPS_REQUIRE(q.c != ndmps::kChainOut && q.c != ndmps::kChainNone, "internal: a product of the stats plan has no buffer");
+    NDMPS_TRY(gemm_T(0, q.m, q.n, q.k, at(q.a), at(q.b), q.n, at(q.c), nullptr, 0, s));
+  }
+  const ChainProduct& q = sp.reduced;
+  NDMPS_REQUIRE(q.c == ndmps::kChainNone, "internal: the reduced product has a destination");
+  if (q.a == ndmps::kChainUnit) {
+    hipLaunchKernelGGL(valstat_unit_kernel<T>, dim3(1), dim3(1), 0, s, at(q.a));
+    NDMPS_LAUNCH_CHECK();
+  }
+  ops->A = at(q.a);
+  ops->B = at(q.b);
+  ops->perm = col_perm;
+  if (col_perm && q.spare != ndmps::kChainNone) {  // where the decode gathers: into the tail buffer that does not hold R
+    hipLaunchKernelGGL(valstat_gather_cols_kernel<T>, dim3(grid1d(q.k * q.n)), dim3(256), 0, s, at(q.b), at(q.spare), q.k,
+                       q.n, col_perm);
+    NDMPS_LAUNCH_CHECK();
+    ops->B = at(q.spare);
+    ops->perm = nullptr;
+  }
+  return NDMPS_OK;
+}
+
+inline int valstat_grid(const ChainProduct& q) {
+  const int64_t tiles = ceil_div(q.m, kBM) * ceil_div(q.n, kBN);
+  return (int)std::min<int64_t>(tiles, ndmps::kValstatMaxGroups);
+}
+
+// moments (err == NULL) or the error against an original: h_stats[4], h_counts[3]
+template <typename T>
+int valstat_record(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* const* h_cores, const ErrorTables* err,
+                   double clip_lo, double clip_hi, double* h_stats, int64_t* h_counts, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds && h_stats && h_counts, "bad valstat argument");
+  NDMPS_REQUIRE(clip_lo == clip_lo && clip_hi == clip_hi, "moments: the clip range must not be NaN");
+  const ChainStatsPlan sp = ndmps::chain_stats_plan(L, h_dims, h_bonds, sizeof(T), 0);
+  NDMPS_TRY(valstat_check(sp, h_dims, h_bonds, h_cores, d_ws, ws_bytes, err));
+  hipStream_t s = (hipStream_t)stream;
+  Operands ops;
+  NDMPS_TRY(valstat_run_chain(sp, h_cores, d_ws, err ? err->col_perm : nullptr, s, &ops));
+  const ChainProduct& q = sp.reduced;
+  const int grid = valstat_grid(q);
+  Record* partials = (Record*)((char*)d_ws + sp.off_partials);
+  Record* result = (Record*)((char*)d_ws + sp.off_result);
+  RecordArgs args{partials, nullptr, nullptr, nullptr, sp.chain.numel, clip_lo, clip_hi};
+  if (err) {
+    args.ref = err->ref;
+    args.row_off = err->row_off;
+    args.col_off = err->col_off;
+    hipLaunchKernelGGL((valstat_product_kernel<T, RecordEpi<T, true>>), dim3(grid), dim3(256), 0, s, (const T*)ops.A,
+                       (const T*)ops.B, ops.perm, q.m, q.n, q.k, args);
+  } else {
+    hipLaunchKernelGGL((valstat_product_kernel<T, RecordEpi<T, false>>), dim3(grid), dim3(256), 0, s, (const T*)ops.A,
+                       (const T*)ops.B, ops.perm, q.m, q.n, q.k, args);
+  }
+  NDMPS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(valstat_fold_kernel, dim3(1), dim3(64), 0, s, partials, grid, result);
+  NDMPS_LAUNCH_CHECK();
+  Record host;
+  NDMPS_CHECK_HIP(hipMemcpyAsync(&host, result, sizeof(Record), hipMemcpyDeviceToHost, s));
+  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+  if (err) {
+    h_stats[0] = host.s0, h_stats[1] = host.hi0, h_stats[2] = host.s1, h_stats[3] = host.hi1;
+  } else {
+    h_stats[0] = host.lo, h_stats[1] = host.hi0, h_stats[2] = host.s0, h_stats[3] = host.s1;
+  }
+  h_counts[0] = host.c0, h_counts[1] = host.c1, h_counts[2] = host.c2;
+  return NDMPS_OK;
+}
+
+template <typename T>
+int valstat_histogram(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* const* h_cores, const T* h_edges,
+                      int n_bins, int64_t* h_counts, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds && h_edges && h_counts, "bad valstat argument");
+  NDMPS_REQUIRE(n_bins >= 1 && n_bins <= ndmps::kValstatMaxBins, "histogram: %d bins outside [1, %d]", n_bins,
+                ndmps::kValstatMaxBins);
+  for (int i = 0; i <= n_bins; ++i)
+    NDMPS_REQUIRE(h_edges[i] == h_edges[i] && (i == 0 || h_edges[i] >= h_edges[i - 1]),
+                  "histogram: edges must be ascending and not NaN (edge %d)", i);
+  const ChainStatsPlan sp = ndmps::chain_stats_plan(L, h_dims, h_bonds, sizeof(T), n_bins);
+  NDMPS_TRY(valstat_check(sp, h_dims, h_bonds, h_cores, d_ws, ws_bytes, nullptr));
+  const ChainProduct& q = sp.reduced;
+  const int grid = valstat_grid(q);
+  // a workgroup counts in 32 bits until its one flush
+  NDMPS_REQUIRE(ceil_div(ceil_div(q.m, kBM) * ceil_div(q.n, kBN), grid) * kBM * kBN < (int64_t)UINT32_MAX,
+                "histogram: volume too large for 32-bit counters per workgroup");
+  hipStream_t s = (hipStream_t)stream;
+  Operands ops;
+  NDMPS_TRY(valstat_run_chain(sp, h_cores, d_ws, nullptr, s, &ops));
+  unsigned long long* counts = (unsigned long long*)((char*)d_ws + sp.off_hist);
+  T* edges = (T*)((char*)d_ws + sp.off_edges);
+  NDMPS_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)(n_bins + 3) * 8, s));
+  NDMPS_CHECK_HIP(hipMemcpyAsync(edges, h_edges, (size_t)(n_bins + 1) * sizeof(T), hipMemcpyHostToDevice, s));
+  const HistArgs args{edges, counts, n_bins};
+  const size_t lds = ((size_t)(n_bins + 1) * sizeof(T) + 7) / 8 * 8 + (size_t)(n_bins + 3) * 4;
+  hipLaunchKernelGGL((valstat_product_kernel<T, HistEpi<T>>), dim3(grid), dim3(256), lds, s, (const T*)ops.A,
+                     (const T*)ops.B, ops.perm, q.m, q.n, q.k, args);
+  NDMPS_LAUNCH_CHECK();
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "counter width");
+  NDMPS_CHECK_HIP(hipMemcpyAsync(h_counts, counts, (size_t)(n_bins + 3) * 8, hipMemcpyDeviceToHost, s));
+  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+  return NDMPS_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t ndmps_valstat_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes,
+                                                 int64_t n_bins) {
+  if (L < 1 || !h_dims || !h_bonds || (elem_bytes != 4 && elem_bytes != 8) || n_bins < 0 || n_bins > ndmps::kValstatMaxBins)
+    return 0;
+  return ndmps::chain_stats_plan(L, h_dims, h_bonds, elem_bytes, n_bins).total_bytes;
+}
+
+// The plan of a statistics call, for tests and tools (slot order: include/ndmps_hip.h).  Host arithmetic only.
+extern "C" int ndmps_valstat_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t n_bins,
+                                        int64_t* h_out) {
+  NDMPS_REQUIRE(h_out && (elem == 0 || elem == 2) && L >= 1 && h_dims && h_bonds && n_bins >= 0 &&
+                    n_bins <= ndmps::kValstatMaxBins,
+                "bad valstat plan query (elem=%d, n_bins=%lld)", elem, (long long)n_bins);
+  const ChainStatsPlan sp = ndmps::chain_stats_plan(L, h_dims, h_bonds, elem == 2 ? 8 : 4, n_bins);
+  const ndmps::ChainPlan& p = sp.chain;
+  const int64_t head[9] = {p.j0, p.tail_cols, (int64_t)p.products.size(), p.left_elems, p.tail_elems,
+                           p.total_bytes, sp.left2_bytes, sp.reduce_bytes, sp.total_bytes};
+  h_out = std::copy(head, head + 9, h_out);
+  auto put = [&](const ChainProduct& q) {
+    const int64_t row[8] = {(int64_t)q.kind, q.m, q.n, q.k, q.a, q.b, q.c, q.spare};
+    h_out = std::copy(row, row + 8, h_out);
+  };
+  for (const ChainProduct& q : p.products) put(q);
+  put(sp.reduced);
+  return NDMPS_OK;
+}
+
+extern "C" int ndmps_valstat_moments_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                                         double clip_lo, double clip_hi, double* h_stats, int64_t* h_counts, void* d_ws,
+                                         int64_t ws_bytes, ndmps_stream_t stream) {
+  return valstat_record<float>(L, h_dims, h_bonds, h_cores, nullptr, clip_lo, clip_hi, h_stats, h_counts, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_valstat_moments_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                                         double clip_lo, double clip_hi, double* h_stats, int64_t* h_counts, void* d_ws,
+                                         int64_t ws_bytes, ndmps_stream_t stream) {
+  return valstat_record<double>(L, h_dims, h_bonds, h_cores, nullptr, clip_lo, clip_hi, h_stats, h_counts, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_valstat_histogram_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                                           const float* h_edges, int n_bins, int64_t* h_counts, void* d_ws,
+                                           int64_t ws_bytes, ndmps_stream_t stream) {
+  return valstat_histogram<float>(L, h_dims, h_bonds, h_cores, h_edges, n_bins, h_counts, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_valstat_histogram_f64(int L, const int64_t* h_dims, const int64_t* h_bonds,
+                                           const double* const* h_cores, const double* h_edges, int n_bins,
+                                           int64_t* h_counts, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  return valstat_histogram<double>(L, h_dims, h_bonds, h_cores, h_edges, n_bins, h_counts, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_valstat_error_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                                       const float* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
+                                       const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts,
+                                       void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  const ErrorTables err{d_ref, d_row_off, d_col_off, d_col_perm, n_cols};
+  return valstat_record<float>(L, h_dims, h_bonds, h_cores, &err, -INFINITY, INFINITY, h_stats, h_counts, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_valstat_error_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                                       const double* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
+                                       const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts,
+                                       void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  const ErrorTables err{d_ref, d_row_off, d_col_off, d_col_perm, n_cols};
+  return valstat_record<double>(L, h_dims, h_bonds, h_cores, &err, -INFINITY, INFINITY, h_stats, h_counts, d_ws, ws_bytes, stream);
+}

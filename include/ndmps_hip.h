@@ -556,6 +556,66 @@ int ndmps_chain_contract_scatter_batched_f32(int batch, int L, const int64_t* h_
  * tail buffer the final product's right operand is gathered into by the scatter entries. */
 #define NDMPS_CHAIN_PLAN_SLOTS(L) (6 + 8 * ((L) - 1))
 int ndmps_chain_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t* h_out);
+/* Value statistics of the volume a chain decodes to, and its error against an original, WITHOUT the volume: the chain
+ * is contracted as ndmps_chain_contract_* contracts it, but the last product -- the only one that touches N
+ * elements -- hands its accumulator tiles to a reducing epilogue instead of storing them (csrc/valstat.hip).  fp32
+ * cores on the fp32 MFMA, fp64 cores on the fp64 MFMA.  Every call checks its arguments before its first launch,
+ * reads its small result record back once and returns with the stream synchronised.  The same inputs give the same
+ * bits: sums are fp64, folded in a fixed order, and only integers are added atomically.
+ *
+ * Workspace: ndmps_valstat_workspace_bytes(L, dims, bonds, elem_bytes (4 or 8), n_bins) = the decode workspace
+ * (ndmps_chain_workspace_bytes*) + a second left buffer + the reduction scratch (partial records, the result, and
+ * for n_bins > 0 the histogram's n_bins + 3 counters and n_bins + 1 edges); 0 for bad arguments.  d_ws must be
+ * 256-byte aligned.  n_bins = 0 serves the moments and error calls.  For a chain without a pre-contracted tail (and for
+ * L == 1) the decode plan's left buffer has N elements, and so has the second one: no memory is saved there.
+ *
+ * ndmps_valstat_plan_query: the plan, for tests and tools (host arithmetic only).  elem: 0 fp32, 2 fp64.  h_out
+ * receives NDMPS_VALSTAT_PLAN_SLOTS(L) values:
+ *    0 j0   1 tail columns   2 number of products (L - 1)   3 left_elems   4 tail_elems
+ *    5 decode workspace bytes   6 second left buffer bytes   7 reduction scratch bytes   8 workspace bytes (5 + 6 + 7)
+ * then the L - 1 products as ndmps_chain_plan_query lists them (same products, same order), and last the product that
+ * is reduced (the last of them again; for L == 1 core 0 as a 1 x d_0 matrix behind a unit left operand).  Buffers
+ * as there, and: -6 the second left buffer (wherever the decode plan uses the output as an intermediate),
+ * -7 the unit operand; the reduced product's destination is -5 (none).
+ *
+ * moments: h_stats = {min, max, sum, sum of squares} over the voxels with clip_lo <= v <= clip_hi (-inf, +inf: all
+ * of them; a narrower range is how a quantile search looks inside its bracket), h_counts = {voxels, NaN voxels,
+ * voxels inside the clip range}.  NaN voxels are counted and take no part in the statistics (none taken: min = +inf,
+ * max = -inf).
+ * histogram: h_edges (HOST, n_bins + 1 values in the element type, ascending, no NaN; 1 <= n_bins <= 4096) as
+ * numpy.histogram reads them: bin b holds edges[b] <= v < edges[b + 1], the last bin includes its right edge.
+ * h_counts receives n_bins + 3 values: the bins, then the voxels below edges[0], above edges[n_bins], and NaN.
+ * Binning is exact for the computed v (binary search in the edge table).
+ * error: d_ref is the original as a C-order volume in the element type; d_row_off / d_col_off / d_col_perm are the
+ * tables of ndmps_plan_split_offsets(plan, n_cols, ...) with the columns sorted by offset, as the fused decode takes
+ * them, n_cols = ndmps_chain_tail_columns, or the last site's dimension for a chain without a tail.
+ * h_stats = {sum (v - y)^2, max |v - y|, sum y^2, max y}, h_counts = {voxels, voxels whose v - y is NaN (left out
+ * of the four), 0}. */
+#define NDMPS_VALSTAT_PLAN_SLOTS(L) (9 + 8 * (L))
+int64_t ndmps_valstat_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes,
+                                      int64_t n_bins);
+int ndmps_valstat_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t n_bins,
+                             int64_t* h_out);
+int ndmps_valstat_moments_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                              double clip_lo, double clip_hi, double* h_stats, int64_t* h_counts, void* d_ws,
+                              int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_valstat_moments_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                              double clip_lo, double clip_hi, double* h_stats, int64_t* h_counts, void* d_ws,
+                              int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_valstat_histogram_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                                const float* h_edges, int n_bins, int64_t* h_counts, void* d_ws, int64_t ws_bytes,
+                                ndmps_stream_t stream);
+int ndmps_valstat_histogram_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                                const double* h_edges, int n_bins, int64_t* h_counts, void* d_ws, int64_t ws_bytes,
+                                ndmps_stream_t stream);
+int ndmps_valstat_error_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                            const float* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
+                            const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts, void* d_ws,
+                            int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_valstat_error_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                            const double* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
+                            const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts, void* d_ws,
+                            int64_t ws_bytes, ndmps_stream_t stream);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */
