@@ -62,11 +62,16 @@ def sketch_bonds(dims, bonds_a, bonds_b, max_bond, oversample) -> list:
     """``l_k = min(max_bond + oversample, m_k, prod_{j<k} d_j, prod_{j>=k} d_j)`` with ``l_0 = l_L = 1``;
     ``max_bond=None``: ``l_k = m_k`` (the exact product, nothing random).  ValueError when some ``l_k`` exceeds
     MAX_SKETCH_BOND."""
+    if len(bonds_a) != len(dims) + 1 or len(bonds_b) != len(dims) + 1:
+        raise ValueError("bonds must have one entry more than dims")
+    return sketch_bonds_of(dims, product_bonds(bonds_a, bonds_b), max_bond, oversample, "product")
+
+
+def sketch_bonds_of(dims, m, max_bond, oversample, what) -> list:
+    """The sketch bonds over the bonds ``m`` (L + 1 entries) of the chain that is sketched, the ``what`` ("product",
+    "sum") of the message: the rule of ``sketch_bonds``, shared with core/sumsketch.py."""
     dims = [int(d) for d in dims]
     L = len(dims)
-    if len(bonds_a) != L + 1 or len(bonds_b) != L + 1:
-        raise ValueError("bonds must have one entry more than dims")
-    m = product_bonds(bonds_a, bonds_b)
     if max_bond is None:
         ell = list(m)
     else:
@@ -78,7 +83,7 @@ def sketch_bonds(dims, bonds_a, bonds_b, max_bond, oversample) -> list:
     for k in range(1, L):
         if ell[k] > MAX_SKETCH_BOND:
             if max_bond is None:
-                raise ValueError(f"bond {k}: the exact product has bond {ell[k]} > {MAX_SKETCH_BOND}; pass max_bond")
+                raise ValueError(f"bond {k}: the exact {what} has bond {ell[k]} > {MAX_SKETCH_BOND}; pass max_bond")
             raise ValueError(f"bond {k}: max_bond + oversample must be <= {MAX_SKETCH_BOND}, got {cap}")
     return ell
 

@@ -28,11 +28,11 @@ def dtype_code(dtype) -> int:
     return _CODES[key]
 
 
-def work_is_f64(codes, explicit=None) -> bool:
-    """fp64 work and output when any input is fp64 (or fp64 is asked for), fp32 otherwise."""
-    if explicit is not None:
-        return dtype_code(explicit) == 2
-    return any(c == 2 for c in codes)
+def work_is_f64(codes, dtype=None) -> bool:
+    """The work type of an operation on inputs with the storage ``codes`` whose result is asked for as ``dtype`` (None or
+    a torch dtype, compared by name): fp64 when fp64 is asked for, fp32 when fp32 is asked for, and otherwise (None or
+    bf16, which rounds the finished cores) fp64 iff some input is fp64."""
+    return str(dtype) == "torch.float64" or (str(dtype) != "torch.float32" and any(c == 2 for c in codes))
 
 
 def floor_for(f64: bool) -> float:

@@ -35,6 +35,13 @@ import numpy as np
 from .. import _lib
 from ..utils import core as _core
 from ..utils import filetools as _ft
+from . import axisop as _ax
+from . import hadamard as _hd
+from . import lincomb as _lc
+from . import oncore as _oc
+from . import series as _se
+from . import sumsketch as _ss
+from . import wgram as _wg
 from .mps import DeviceMPS
 
 _PLAN_CACHE = {}
@@ -232,35 +239,22 @@ def _check_result_dtype(dtype):
 
 def _check_compatible(objs):
     """``lincomb.check_compatible`` over NDMPS objects: same qubit_size, shape, mode, device and site dims."""
-    from . import lincomb as _lc
-
     _lc.check_compatible([dict(qubit_size=o.qubit_size, shape=o._shape, mode=o.mode, device=o.mps.device,
                                dims=o.mps.dims) for o in objs])
 
 
-def _chain_list_args(lst):
-    """The C arguments of a list of objects: (bonds, storage codes, core pointers), object by object."""
-    from . import lincomb as _lc
-
-    return (_lib.i64_array([b for o in lst for b in o.mps.bonds]),
-            (C.c_int * len(lst))(*[_lc.dtype_code(o.mps.dtype) for o in lst]),
-            (C.c_void_p * (len(lst) * lst[0].mps.L))(*[c.data_ptr() for o in lst for c in o.mps.cores]))
-
-
-def _sketch_table(R):
-    """The random cores of a sketch as one flat fp64 table, site by site."""
-    return np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for r in R]))
+def _checked_list(objs, phrase):
+    """``objs`` as a list; TypeError ("<phrase> NDMPS objects, not ...") for an element that is no NDMPS."""
+    objs = list(objs)
+    for o in objs:
+        if not isinstance(o, NDMPS):
+            raise TypeError(f"{phrase} NDMPS objects, not {type(o).__name__}")
+    return objs
 
 
-def _zero_chain(dims, device):
-    """The zero MPS: bond-1 zero cores in fp64."""
-    return DeviceMPS([_torch().zeros((1, d, 1), dtype=_torch().float64, device=device) for d in dims], _trusted=True)
-
-
-def _carve_cores(arena, out_off, bonds, dims):
-    """The cores ``(bonds[k], dims[k], bonds[k + 1])`` of an output arena as views: core k starts at ``out_off[k]``."""
-    return [arena[out_off[k]: out_off[k] + bonds[k] * d * bonds[k + 1]].view(bonds[k], d, bonds[k + 1])
-            for k, d in enumerate(dims)]
+def _work_is_f64(objs, dtype=None):
+    """``lincomb.work_is_f64`` over NDMPS objects and the ``dtype`` argument of the call."""
+    return _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs], dtype)
 
 
 # ------------------------------------------------------------------------------------------------ decode tail
@@ -1067,12 +1061,7 @@ class NDMPS:
         Raises ValueError for empty or mismatched inputs, a non-finite weight, ``cutoff < 0``, ``max_bond < 1``,
         objects that differ in qubit_size, shape, mode or device, or a summed bond above 4096.
         """
-        from . import lincomb as _lc
-
-        objs = list(objs)
-        for o in objs:
-            if not isinstance(o, NDMPS):
-                raise TypeError(f"linear_combination combines NDMPS objects, not {type(o).__name__}")
+        objs = _checked_list(objs, "linear_combination combines")
         w = _lc.check_args(len(objs), weights, cutoff, max_bond)
         _check_result_dtype(dtype)
         _check_compatible(objs)
@@ -1081,52 +1070,13 @@ class NDMPS:
         return objs[0]._round_chains([o.mps for o in objs], w, cutoff, max_bond, dtype, scale)
 
     def _round_chains(self, chains, w, cutoff, max_bond, dtype, scale) -> "NDMPS":
-        """The TT-SVD rounding of ``sum_a w[a] * chains[a]`` (DeviceMPS over this object's site dims, arguments already
-        checked) through ndmps_lincomb_round, as a new object like this one: ``norm=False``, boundary_list, norm_value
-        and sweep_spectra set.  ``scale`` is the absolute scale of the storage floor."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import lincomb as _lc
-
-        bond_lists = [m.bonds for m in chains]
-        codes = [_lc.dtype_code(m.dtype) for m in chains]
-        f64 = dtype == torch.float64 or (dtype != torch.float32 and _lc.work_is_f64(codes))
-        work = torch.float64 if f64 else torch.float32
-        first = chains[0]
-        device = first.device
-        K, L = len(chains), first.L
-        dims = first.dims
-        mb = int(max_bond) if max_bond is not None else 0
-        c_dims = _lib.i64_array(dims)
-        c_bonds = _lib.i64_array([b for bl in bond_lists for b in bl])
-        out_off = (C.c_int64 * (L + 1))()
-        ws_bytes, stride = C.c_int64(0), C.c_int64(0)
-        total = _lib.check(lib.ndmps_lincomb_layout(K, L, c_dims, c_bonds, mb, out_off, C.byref(ws_bytes),
-                                                    C.byref(stride)))
-        ptrs = (C.c_void_p * (K * L))(*[c.data_ptr() for m in chains for c in m.cores])
-        out_bonds = (C.c_int64 * (L + 1))()
-        spectra = np.zeros(L * max(int(stride.value), 1), dtype=np.float64)
-        with torch.cuda.device(device):
-            arena = torch.empty(max(int(total), 1), dtype=work, device=device)
-            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
-            with _span("lincomb"):
-                rc = _lib.check(lib.ndmps_lincomb_round(
-                    K, L, c_dims, c_bonds, (C.c_int * K)(*codes), ptrs, _lib.f64_array(w), float(cutoff), mb,
-                    2 if f64 else 0, scale, arena.data_ptr(), arena.numel(), out_bonds,
-                    spectra.ctypes.data_as(_lib.p_f64), int(stride.value), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-            del ws
-        r = [int(v) for v in out_bonds]
-        cores = _carve_cores(arena, out_off, r, dims)
-        if dtype == torch.bfloat16:
-            cores = [c.to(torch.bfloat16) for c in cores]
+        """``oncore.round_chains`` of DeviceMPS chains over this object's site dims (arguments already checked) as a new
+        object like this one: ``norm=False``, boundary_list, norm_value and sweep_spectra set."""
+        cores, _, spectra, _ = _oc.round_chains(chains, w, cutoff, max_bond, dtype, scale)
         out = self._like(cores, norm=False)
         out.update_boundary_list()
         out.update_norm()
-        st = int(stride.value)
-        if rc > 0:  # the zero MPS: every bond 1 with the singular value 0
-            out.sweep_spectra = [None] + [np.zeros(1) for _ in range(1, L)]
-        else:
-            out.sweep_spectra = [None] + [spectra[k * st: k * st + r[k]].copy() for k in range(1, L)]
+        out.sweep_spectra = spectra
         return out
 
     def recompress(self, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
@@ -1141,8 +1091,6 @@ class NDMPS:
         """(axis as a non-negative int, the factor array, the axis length) for an operator along ``axis``; ValueError
         without a known shape, for the last axis of a DCT-mode object, or for cores that are not over the shape's own
         factor array."""
-        from . import axisop as _ax
-
         shape = self._require_shape()
         axis = _ax.normalize_axis(axis, len(shape))
         _ax.check_data_axis(self.mode, axis, len(shape))
@@ -1151,47 +1099,12 @@ class NDMPS:
             raise ValueError("the cores are not over the site dims of this object's shape")
         return axis, fa, int(shape[axis])
 
-    def _axis_apply(self, mpo, axis) -> DeviceMPS:
-        """The unrounded wide chain of the operator ``mpo`` (core/axisop.py AxisMPO) applied along ``axis``: bonds
-        ``D_k chi_k``, fp64 cores for fp64 storage and fp32 otherwise, computed by one launch (csrc/axisop.hip)."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import axisop as _ax
-        from . import lincomb as _lc
-
-        axis, fa, _ = self._axis_plan(axis)
-        mps = self.mps
-        _ax.check_plan(mpo, fa, axis, mps.dims)
-        _ax.check_wide_bonds(mpo.bonds, mps.bonds)
-        code = _lc.dtype_code(mps.dtype)
-        L, dims, device = mps.L, mps.dims, mps.device
-        c_dims, c_bonds = _lib.i64_array(dims), _lib.i64_array(mps.bonds)
-        c_f = _lib.i64_array(mpo.factors)
-        c_post = _lib.i64_array([post for _, _, post in _ax.site_split(fa, axis)])
-        c_D = _lib.i64_array(mpo.bonds)
-        table = np.concatenate([m.ravel() for m in mpo.cores])
-        out_off = (C.c_int64 * (L + 1))()
-        ws_bytes = C.c_int64(0)
-        total = _lib.check(lib.ndmps_axisop_layout(L, c_dims, c_bonds, c_f, c_D, out_off, C.byref(ws_bytes)))
-        with torch.cuda.device(device):
-            arena = torch.empty(int(total), dtype=torch.float64 if code == 2 else torch.float32, device=device)
-            ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=device)
-            with _span("axisop"):
-                _lib.check(lib.ndmps_axisop_apply(L, c_dims, c_bonds, code, mps._core_ptrs(), c_f, c_post, c_D,
-                                                  table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(),
-                                                  arena.numel(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-            del ws
-        wide = [d * b for d, b in zip(mpo.bonds, mps.bonds)]
-        return DeviceMPS(_carve_cores(arena, out_off, wide, dims), _trusted=True)
-
-    def _axis_rounded(self, mpo, axis, cutoff, max_bond, dtype) -> "NDMPS":
-        """The operator applied along ``axis`` and rounded like ``recompress``; the storage floor is relative to
-        ``mpo.opnorm * norm_value``, a bound on the result's norm."""
-        from . import lincomb as _lc
-
+    def _axis_rounded(self, mpo, fa, axis, cutoff, max_bond, dtype) -> "NDMPS":
+        """The operator applied along ``axis`` (``fa``, ``axis``: what ``_axis_plan`` returned) and rounded like
+        ``recompress``; the storage floor is relative to ``mpo.opnorm * norm_value``, a bound on the result's norm."""
         _lc.check_args(1, [1.0], cutoff, max_bond)
         _check_result_dtype(dtype)
-        wide = self._axis_apply(mpo, axis)
+        wide = _oc.axis_apply(self.mps, mpo, fa, axis)
         return self._round_chains([wide], [1.0], cutoff, max_bond, dtype, mpo.opnorm * float(self.norm_value))
 
     def roll(self, shift, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
@@ -1206,8 +1119,6 @@ class NDMPS:
         tuples of different lengths, for the last axis of a DCT-mode object (its digits index DCT coefficients; the
         other axes are fine) and for ``linear_combination``'s argument errors.  No counterpart in the reference.
         """
-        from . import axisop as _ax
-
         if isinstance(axis, tuple):
             shifts = shift if isinstance(shift, tuple) else (shift,) * len(axis)
             if len(shifts) != len(axis):
@@ -1221,19 +1132,17 @@ class NDMPS:
             return out
         shift = _ax.check_shift(shift)
         axis, fa, _ = self._axis_plan(axis)
-        return self._axis_rounded(_ax.roll_mpo(fa[:, axis], shift), axis, cutoff, max_bond, dtype)
+        return self._axis_rounded(_ax.roll_mpo(fa[:, axis], shift), fa, axis, cutoff, max_bond, dtype)
 
     def shift(self, shift, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
         """The volume moved by ``shift`` voxels along ``axis`` with zeros shifted in (``out[i] = x[i - shift]`` inside
         the volume); ``abs(shift) >= n`` gives the zero MPS, as ``linear_combination`` returns it.  Otherwise as
         ``roll`` with a single axis."""
-        from . import axisop as _ax
-
         shift = _ax.check_shift(shift)
         axis, fa, n = self._axis_plan(axis)
         if abs(shift) >= n:
             return NDMPS.linear_combination([self], [0.0], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
-        return self._axis_rounded(_ax.shift_mpo(fa[:, axis], shift), axis, cutoff, max_bond, dtype)
+        return self._axis_rounded(_ax.shift_mpo(fa[:, axis], shift), fa, axis, cutoff, max_bond, dtype)
 
     def correlate1d(self, weights, axis=-1, mode: str = "constant", origin: int = 0, cutoff: float = 0.0,
                     max_bond=None, dtype=None) -> "NDMPS":
@@ -1245,29 +1154,23 @@ class NDMPS:
         ``sum |weights| * norm_value``.  Raises ValueError for weights that are not a non-empty 1-D array of finite
         numbers, another ``mode``, an origin scipy refuses or a radius ``>= n``; axis errors as ``roll``.
         """
-        from . import axisop as _ax
-
         _ax.check_taps(weights)
         _ax.check_mode(mode)
         axis, fa, n = self._axis_plan(axis)
         taps = _ax.correlate_taps(weights, origin, n)
-        return self._axis_rounded(_ax.offsets_mpo(fa[:, axis], taps, mode), axis, cutoff, max_bond, dtype)
+        return self._axis_rounded(_ax.offsets_mpo(fa[:, axis], taps, mode), fa, axis, cutoff, max_bond, dtype)
 
     def cumsum(self, axis, cutoff: float = 0.0, max_bond=None, dtype=None) -> "NDMPS":
         """``np.cumsum(to_tensor(), axis)`` on the cores: an operator of bond 2, rounded like ``recompress``.  The
         operator's norm is bounded by n, so the absolute storage floor is ``1e-6 * n * norm_value`` (1e-8 for fp64
         work): directions of the result below that are dropped.  Axis errors as ``roll``."""
-        from . import axisop as _ax
-
         axis, fa, _ = self._axis_plan(axis)
-        return self._axis_rounded(_ax.cumsum_mpo(fa[:, axis]), axis, cutoff, max_bond, dtype)
+        return self._axis_rounded(_ax.cumsum_mpo(fa[:, axis]), fa, axis, cutoff, max_bond, dtype)
 
     def flip(self, axis) -> "NDMPS":
         """``np.flip(to_tensor(), axis)``: every digit of the axis reversed, a site-local permutation.  The cores are
         permuted copies in the same storage type; bonds, gauge, ``norm``, ``norm_value``, ``boundary_list`` and
         ``sweep_spectra`` are those of this object and nothing is rounded.  Axis errors as ``roll``."""
-        from . import axisop as _ax
-
         axis, fa, _ = self._axis_plan(axis)
         cores = [c.view(c.shape[0], pre, f, post, c.shape[2]).flip(2).reshape(c.shape).contiguous()
                  for c, (pre, f, post) in zip(self.mps.cores, _ax.site_split(fa, axis))]
@@ -1279,40 +1182,6 @@ class NDMPS:
         return out
 
     # ------------------------------------------------------- elementwise product on the cores (core/hadamard.py)
-    def _hadamard_sketch(self, other, ell, R) -> DeviceMPS:
-        """The unrounded sketched chain of ``self * other`` (csrc/hadamard.hip): fp64, left-orthonormal up to its last
-        site, bonds ``r_k <= ell[k]``; ``ell`` the sketch bonds and ``R`` the random cores of core/hadamard.py (host
-        fp64 arrays).  The zero product comes back as bond-1 zero cores.  ValueError when the workspace would exceed
-        ``hadamard.WS_LIMIT_BYTES``."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import hadamard as _hd
-        from . import lincomb as _lc
-
-        a, b = self.mps, other.mps
-        L, dims, device = a.L, a.dims, a.device
-        c_dims, c_ba, c_bb = _lib.i64_array(dims), _lib.i64_array(a.bonds), _lib.i64_array(b.bonds)
-        c_ell = _lib.i64_array(ell)
-        out_off = (C.c_int64 * (L + 1))()
-        ws_bytes = C.c_int64(0)
-        total = _lib.check(lib.ndmps_hadamard_layout(L, c_dims, c_ba, c_bb, c_ell, out_off, C.byref(ws_bytes)))
-        _hd.check_workspace(ws_bytes.value)
-        table = _sketch_table(R)
-        ranks = (C.c_int64 * (L + 1))()
-        with torch.cuda.device(device):
-            arena = torch.empty(max(int(total), 1), dtype=torch.float64, device=device)
-            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
-            with _span("hadamard"):
-                rc = _lib.check(lib.ndmps_hadamard_sketch(
-                    L, c_dims, c_ba, _lc.dtype_code(a.dtype), a._core_ptrs(), c_bb, _lc.dtype_code(b.dtype),
-                    b._core_ptrs(), c_ell, table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(), arena.numel(),
-                    ranks, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-            del ws
-            if rc > 0:  # the zero product
-                return _zero_chain(dims, device)
-        r = [int(v) for v in ranks]
-        return DeviceMPS(_carve_cores(arena, out_off, r, dims), _trusted=True)
-
     def multiply(self, other, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0, dtype=None) -> "NDMPS":
         """
         The elementwise (Hadamard) product ``to_tensor() * other.to_tensor()`` as a new object, computed on the cores
@@ -1334,9 +1203,6 @@ class NDMPS:
         ``dtype`` / ``cutoff`` / ``max_bond`` errors of ``linear_combination``.
         """
         torch = _torch()
-        from . import hadamard as _hd
-        from . import lincomb as _lc
-
         if not isinstance(other, NDMPS):
             raise TypeError(f"multiply takes an NDMPS, not {type(other).__name__}")
         max_bond, oversample, seed = _hd.check_args(max_bond, cutoff, oversample, seed)
@@ -1346,11 +1212,10 @@ class NDMPS:
             raise ValueError("DCT mode stores DCT coefficients: their product is not the product of the volumes")
         dims = self.mps.dims
         ell = _hd.sketch_bonds(dims, self.mps.bonds, other.mps.bonds, max_bond, oversample)
-        sketched = self._hadamard_sketch(other, ell, _hd.sketch_cores(dims, ell, seed))
+        sketched = _oc.hadamard_sketch(self.mps, other.mps, ell, _hd.sketch_cores(dims, ell, seed))
         scale = float(torch.linalg.vector_norm(sketched.cores[-1]))
         if dtype is None:
-            codes = [_lc.dtype_code(self.mps.dtype), _lc.dtype_code(other.mps.dtype)]
-            dtype = torch.float64 if _lc.work_is_f64(codes) else torch.float32
+            dtype = torch.float64 if _work_is_f64((self, other)) else torch.float32
         return self._round_chains([sketched], [1.0], cutoff, max_bond, dtype, scale)
 
     def square(self, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0, dtype=None) -> "NDMPS":
@@ -1358,48 +1223,6 @@ class NDMPS:
         return self.multiply(self, max_bond=max_bond, cutoff=cutoff, oversample=oversample, seed=seed, dtype=dtype)
 
     # ------------------------------------------------------- sums of many objects by a sketch (core/sumsketch.py)
-    @staticmethod
-    def _sum_sketch(objs, w, ell, R) -> list:
-        """The unrounded sketched chains of ``sum_a w[j, a] * objs[a]`` for every row j (csrc/sumsketch.hip): fp64,
-        left-orthonormal up to their last sites, bonds ``r_k <= ell[k]``.  ``objs``: the frames some row uses; a zero
-        output comes back as bond-1 zero cores.  ValueError when the workspace would exceed
-        ``hadamard.WS_LIMIT_BYTES``."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import hadamard as _hd
-
-        first = objs[0].mps
-        T, K, L, dims, device = len(objs), int(w.shape[0]), first.L, first.dims, first.device
-        c_dims = _lib.i64_array(dims)
-        c_bonds, codes, ptrs = _chain_list_args(objs)
-        c_ell = _lib.i64_array(ell)
-        out_off = (C.c_int64 * (L + 1))()
-        ws_bytes = C.c_int64(0)
-        total = _lib.check(lib.ndmps_sumsketch_layout(T, K, L, c_dims, c_bonds, c_ell, out_off, C.byref(ws_bytes)))
-        _hd.check_workspace(ws_bytes.value)
-        table = _sketch_table(R)
-        weights = np.ascontiguousarray(w, dtype=np.float64)
-        ranks = (C.c_int64 * (K * (L + 1)))()
-        zero = (C.c_int * K)()
-        chain = int(out_off[L])
-        with torch.cuda.device(device):
-            arena = torch.empty(max(int(total), 1), dtype=torch.float64, device=device)
-            ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=device)
-            with _span("sumsketch"):
-                _lib.check(lib.ndmps_sumsketch_sketch(
-                    T, K, L, c_dims, c_bonds, codes, ptrs, weights.ctypes.data_as(_lib.p_f64), c_ell,
-                    table.ctypes.data_as(_lib.p_f64), table.size, arena.data_ptr(), arena.numel(), ranks, zero,
-                    ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-            del ws
-            chains = []
-            for j in range(K):
-                if zero[j]:
-                    chains.append(_zero_chain(dims, device))
-                    continue
-                r = [int(v) for v in ranks[j * (L + 1):(j + 1) * (L + 1)]]
-                chains.append(DeviceMPS(_carve_cores(arena[j * chain:(j + 1) * chain], out_off, r, dims), _trusted=True))
-        return chains
-
     @staticmethod
     def linear_combinations(objs, weights, max_bond=None, cutoff: float = 0.0, oversample=None, seed: int = 0,
                             dtype=None) -> list:
@@ -1427,14 +1250,7 @@ class NDMPS:
         kernels; an object with a larger bond takes a general route through fp64 dense products.
         """
         torch = _torch()
-        from . import hadamard as _hd
-        from . import lincomb as _lc
-        from . import sumsketch as _ss
-
-        objs = list(objs)
-        for o in objs:
-            if not isinstance(o, NDMPS):
-                raise TypeError(f"linear_combinations combines NDMPS objects, not {type(o).__name__}")
+        objs = _checked_list(objs, "linear_combinations combines")
         w = _ss.check_weights(len(objs), weights)
         max_bond, oversample, seed = _hd.check_args(max_bond, cutoff, oversample, seed)
         _check_result_dtype(dtype)
@@ -1442,15 +1258,14 @@ class NDMPS:
         first = objs[0]
         dims = first.mps.dims
         if dtype is None:
-            dtype = torch.float64 if _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]) else torch.float32
+            dtype = torch.float64 if _work_is_f64(objs) else torch.float32
         used = _ss.used_frames(w)
         if used:
-            frames = [objs[a] for a in used]
-            bond_lists = [o.mps.bonds for o in frames]
-            ell = _ss.sketch_bonds(dims, bond_lists, max_bond, oversample)
-            chains = NDMPS._sum_sketch(frames, w[:, used], ell, _hd.sketch_cores(dims, ell, seed))
+            frames = [objs[a].mps for a in used]
+            ell = _ss.sketch_bonds(dims, [m.bonds for m in frames], max_bond, oversample)
+            chains = _oc.sum_sketch(frames, w[:, used], ell, _hd.sketch_cores(dims, ell, seed))
         else:
-            chains = [_zero_chain(dims, first.mps.device) for _ in range(w.shape[0])]
+            chains = [_oc.zero_chain(dims, first.mps.device) for _ in range(w.shape[0])]
         out = []
         for sketched in chains:
             scale = float(torch.linalg.vector_norm(sketched.cores[-1]))
@@ -1467,20 +1282,13 @@ class NDMPS:
         so a series of any length is accepted and all outputs share the right environments.  ``max_bond``, ``cutoff``,
         ``oversample``, ``seed`` and ``dtype`` as in ``linear_combinations``.  Returns a ``SeriesPCA``.
         """
-        torch = _torch()
-        from . import hadamard as _hd
-        from . import lincomb as _lc
-        from . import series as _se
-
         objs = list(objs)
         _se.check_components(n_components)
         _hd.check_args(max_bond, cutoff, oversample, seed)
         _check_result_dtype(dtype)
         G = NDMPS.gram(objs)
         T = len(objs)
-        f64 = dtype == torch.float64 or (dtype != torch.float32
-                                         and _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]))
-        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(f64))
+        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(_work_is_f64(objs, dtype)))
         rows = [W[:, k] for k in range(len(sigma))] + ([np.full(T, 1.0 / T)] if center else [])
         outs = NDMPS.linear_combinations(objs, np.stack(rows), max_bond=max_bond, cutoff=cutoff, oversample=oversample,
                                          seed=seed, dtype=dtype) if rows else []
@@ -1489,35 +1297,18 @@ class NDMPS:
 
     # ------------------------------------------------------- Gram matrix and PCA of a series (core/series.py)
     @staticmethod
-    def _series_args(objs, others):
-        """Checked lists and the C arguments of the ndmps_series_gram* calls."""
-        from . import series as _se
-
+    def _gram_chains(objs, others, weight):
+        """The checked arguments of ``gram`` / ``gram_route`` as chains: (rows, columns or None, weight chain or None)."""
         objs = list(objs)
-        rows = objs if others is None else objs + list(others)
-        for o in rows:
-            if not isinstance(o, NDMPS):
-                raise TypeError(f"gram takes NDMPS objects, not {type(o).__name__}")
+        rows = _checked_list(objs if others is None else objs + list(others), "gram takes")
         _se.check_lists(len(objs), None if others is None else len(rows) - len(objs))
         _check_compatible(rows)
-        cols = objs if others is None else rows[len(objs):]
-        sa = _chain_list_args(objs)
-        sb = sa if others is None else _chain_list_args(cols)
-        return objs, cols, _lib.i64_array(objs[0].mps.dims), sa, sb
-
-    @staticmethod
-    def _weight_args(rows, weight):
-        """The checks of a ``weight=`` argument against the objects of the call, and its C arguments (bonds, storage
-        code, core pointers)."""
-        from . import lincomb as _lc
-        from . import wgram as _wg
-
-        _wg.check_weight_type(weight, NDMPS)
-        _check_compatible(list(rows) + [weight])
-        _wg.check_mode(weight.mode)
-        L = weight.mps.L
-        return (_lib.i64_array(weight.mps.bonds), _lc.dtype_code(weight.mps.dtype),
-                (C.c_void_p * L)(*[c.data_ptr() for c in weight.mps.cores]))
+        if weight is not None:
+            _wg.check_weight_type(weight, NDMPS)
+            _check_compatible(rows + [weight])
+            _wg.check_mode(weight.mode)
+        return ([o.mps for o in objs], None if others is None else [o.mps for o in rows[len(objs):]],
+                None if weight is None else weight.mps)
 
     @staticmethod
     def gram_route(objs, others=None, *, weight=None) -> str:
@@ -1525,16 +1316,7 @@ class NDMPS:
         per pair), "batched" (larger bonds, equal in all objects) or "per-pair" (larger ragged bonds).  With a
         ``weight`` (csrc/wgram.hip): "resident" (every inner bond of the objects <= 64, whatever the weight's bonds)
         or "per-pair"."""
-        from . import series as _se
-
-        objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
-        lib = _lib.load()
-        if weight is not None:
-            sw = NDMPS._weight_args(objs if others is None else objs + cols, weight)
-            return _se.ROUTES[_lib.check(lib.ndmps_series_wgram_route(len(objs), len(cols), objs[0].mps.L, c_dims, sa[0],
-                                                                      sb[0], sw[0]))]
-        return _se.ROUTES[_lib.check(lib.ndmps_series_gram_route(len(objs), len(cols), objs[0].mps.L, c_dims,
-                                                                 sa[0], sb[0]))]
+        return _oc.gram_route(*NDMPS._gram_chains(objs, others, weight))
 
     @staticmethod
     def gram(objs, others=None, as_torch: bool = False, *, weight=None):
@@ -1557,32 +1339,7 @@ class NDMPS:
         a weight in DCT mode (a product of coefficient volumes is not the product of the volumes) and when a single
         pair does not fit the workspace limit.
         """
-        torch = _torch()
-        lib = _lib.load()
-        objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
-        Ka, Kb, L = len(objs), len(cols), objs[0].mps.L
-        device = objs[0].mps.device
-        sym = 1 if others is None else 0
-        lists = sa + sb
-        if weight is not None:
-            from . import wgram as _wg
-
-            sw = NDMPS._weight_args(objs if others is None else objs + cols, weight)
-            nbytes = lib.ndmps_series_wgram_workspace_bytes(Ka, Kb, sym, L, c_dims, sa[0], sb[0], sw[0], _wg.WS_LIMIT_BYTES)
-            if nbytes != _lib.EWORKSPACE:
-                _lib.check(nbytes)
-            nbytes = _wg.check_workspace(nbytes)
-            span, entry, lists = "wgram", lib.ndmps_series_wgram, lists + sw
-        else:
-            nbytes = int(_lib.check(lib.ndmps_series_gram_workspace_bytes(Ka, Kb, L, c_dims, sa[0], sb[0])))
-            span, entry = "gram", lib.ndmps_series_gram
-        with torch.cuda.device(device):
-            G = torch.empty((Ka, Kb), dtype=torch.float64, device=device)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-            with _span(span):
-                _lib.check(entry(Ka, Kb, sym, L, c_dims, *lists, G.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-            del ws
-        return G if as_torch else G.cpu().numpy()
+        return _oc.gram(*NDMPS._gram_chains(objs, others, weight), as_torch=as_torch)
 
     def inner(self, other, *, weight=None) -> float:
         """``<self, other>``: the entry of ``NDMPS.gram([self], [other])``; with ``weight`` the entry of
@@ -1608,18 +1365,12 @@ class NDMPS:
         The weight should be non-negative: a weight with negative values can make ``G_w`` indefinite, and its negative
         eigenvalues are clipped to zero like rounding noise.
         """
-        torch = _torch()
-        from . import lincomb as _lc
-        from . import series as _se
-
         objs = list(objs)
         _se.check_components(n_components)
         _lc.check_args(max(len(objs), 1), [0.0] * max(len(objs), 1), cutoff, max_bond)
         G = NDMPS.gram(objs, weight=weight)
         K = len(objs)
-        f64 = dtype == torch.float64 or (dtype != torch.float32
-                                         and _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs]))
-        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(f64))
+        sigma, U, W = _se.pca_weights(G, n_components, center, _lc.floor_for(_work_is_f64(objs, dtype)))
         components = [NDMPS.linear_combination(objs, W[:, k], cutoff=cutoff, max_bond=max_bond, dtype=dtype)
                       for k in range(len(sigma))]
         mean = NDMPS.linear_combination(objs, [1.0 / K] * K, cutoff=cutoff, max_bond=max_bond, dtype=dtype) if center else None
@@ -1849,10 +1600,7 @@ class NDMPS:
     def _region_series_objs(objs):
         """The checked list of a series call: TypeError for a non-NDMPS, ValueError for an empty list, objects that
         differ (``lincomb.check_compatible``) or an unknown shape."""
-        objs = list(objs)
-        for o in objs:
-            if not isinstance(o, NDMPS):
-                raise TypeError(f"a series takes NDMPS objects, not {type(o).__name__}")
+        objs = _checked_list(objs, "a series takes")
         if not objs:
             raise ValueError("a series needs at least one object")
         _check_compatible(objs)

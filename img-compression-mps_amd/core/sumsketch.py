@@ -20,8 +20,6 @@ pass.  The cost is linear in T and no eigenproblem exceeds ``max_bond + oversamp
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
 from . import hadamard as _hd
@@ -65,26 +63,10 @@ def sketch_bonds(dims, bond_lists, max_bond, oversample, frames=None) -> list:
     """``l_k = min(max_bond + oversample, m_k, prod_{j<k} d_j, prod_{j>=k} d_j)`` with ``l_0 = l_L = 1`` and ``m_k``
     over ``frames``; ``max_bond=None``: ``l_k = m_k`` (the exact sum, nothing truncated by the sketch).  ValueError when
     some ``l_k`` exceeds ``hadamard.MAX_SKETCH_BOND``."""
-    dims = [int(d) for d in dims]
-    L = len(dims)
-    if any(len(bl) != L + 1 for bl in bond_lists):
+    if any(len(bl) != len(dims) + 1 for bl in bond_lists):
         raise ValueError("bonds must have one entry more than dims")
-    m = summed_bonds(bond_lists, frames)
-    if max_bond is None:
-        ell = [max(1, v) for v in m]
-        cap = None
-    else:
-        if oversample < 0:
-            raise ValueError("oversample must be a non-negative integer")
-        cap = int(max_bond) + int(oversample)
-        ell = [max(1, min(cap, m[k], math.prod(dims[:k]), math.prod(dims[k:]))) for k in range(L + 1)]
-    ell[0] = ell[L] = 1
-    for k in range(1, L):
-        if ell[k] > _hd.MAX_SKETCH_BOND:
-            if cap is None:
-                raise ValueError(f"bond {k}: the exact sum has bond {ell[k]} > {_hd.MAX_SKETCH_BOND}; pass max_bond")
-            raise ValueError(f"bond {k}: max_bond + oversample must be <= {_hd.MAX_SKETCH_BOND}, got {cap}")
-    return ell
+    # a bond no frame reaches (m_k = 0, no frames) is sketched as bond 1
+    return _hd.sketch_bonds_of(dims, [max(1, v) for v in summed_bonds(bond_lists, frames)], max_bond, oversample, "sum")
 
 
 def emulate(cores_per_frame, weights, dims, ell, R):

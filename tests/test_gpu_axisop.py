@@ -2,7 +2,7 @@
 
 Bars, and where they come from:
 
-* Kernel: ``_axis_apply`` (the unrounded wide chain) against ``core.axisop.emulate`` in fp64 on the same cores.  roll,
+* Kernel: ``oncore.axis_apply`` (the unrounded wide chain) against ``core.axisop.emulate`` in fp64 on the same cores.  roll,
   shift and flip have at most one term per output, so the device must return ``emulate``'s values exactly, absent
   entries as exact zeros.  Stencils and cumsum: per element ``(t + 1) u sum |M| |X|``, the standard bound of a sum of
   ``t`` products rounded once more into the work type (u = 2**-24 for fp32 work, 2**-53 for fp64; t = the largest
@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 from imgcompressionmps_amd import NDMPS  # noqa: E402
 from imgcompressionmps_amd.core import axisop as ax  # noqa: E402
+from imgcompressionmps_amd.core import oncore  # noqa: E402
 from imgcompressionmps_amd.core.mps import DeviceMPS  # noqa: E402
 from imgcompressionmps_amd.utils import core as _core  # noqa: E402
 from oracle.metrics import synthetic_mri  # noqa: E402
@@ -109,7 +110,7 @@ def test_kernel_against_emulate(shape, chi, storage):
         single = [ax.roll_mpo(fs, 1), ax.roll_mpo(fs, -1), ax.roll_mpo(fs, 5), ax.roll_mpo(fs, n + 3), ax.shift_mpo(fs, 3),
                   ax.shift_mpo(fs, -2), ax.flip_mpo(fs)]
         for mpo in single:
-            got = obj._axis_apply(mpo, axis)
+            got = oncore.axis_apply(obj.mps, mpo, fa, axis)
             want = ax.emulate(cores, mpo, fa, axis)
             assert got.bonds == [d * b for d, b in zip(mpo.bonds, bonds)]
             for g, w in zip(got.cores, want):
@@ -119,7 +120,7 @@ def test_kernel_against_emulate(shape, chi, storage):
         several = [ax.offsets_mpo(fs, {s: float(trng.standard_normal()) for s in range(-r, r + 1)}, mode)
                    for r in (1, 2, 4) if r < n for mode in ax.MODES] + [ax.cumsum_mpo(fs)]
         for mpo in several:
-            got = obj._axis_apply(mpo, axis)
+            got = oncore.axis_apply(obj.mps, mpo, fa, axis)
             want = ax.emulate(cores, mpo, fa, axis)
             mag = ax.emulate([np.abs(c) for c in cores], ax.AxisMPO([np.abs(m) for m in mpo.cores], mpo.opnorm), fa, axis)
             for g, w, a, m in zip(got.cores, want, mag, mpo.cores):

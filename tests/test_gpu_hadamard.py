@@ -9,7 +9,7 @@ Bars, and where they come from:
   exact in every storage type, so all storages share one reference; ``E`` is Gaussian on a grid of 2**-10, which keeps
   every partial sum of the NumPy reference exact in fp64 (40 bits at most), so the bound is held against the device's
   error alone.  The output buffer is pre-filled with a sentinel and everything past the results keeps it.
-* Sketch (``_hadamard_sketch``) against ``core.hadamard.emulate`` with the same random cores: identical ranks, and
+* Sketch (``oncore.hadamard_sketch``) against ``core.hadamard.emulate`` with the same random cores: identical ranks, and
   the decoded chains agree within ``1e-9 |product|`` (the projector is gauge-free and both sides work in fp64).
 * End to end: ``|a.multiply(b).to_tensor() - a.to_tensor() * b.to_tensor()| <= tol |product|`` (Frobenius), tol from
   tests/test_gpu_lincomb.py (1e-5 for fp32 / bf16 work, 1e-7 for fp64).
@@ -28,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 from imgcompressionmps_amd import NDMPS, _lib  # noqa: E402
 from imgcompressionmps_amd.core import hadamard as hd  # noqa: E402
+from imgcompressionmps_amd.core import oncore  # noqa: E402
 from imgcompressionmps_amd.core.mps import DeviceMPS  # noqa: E402
 from imgcompressionmps_amd.utils import core as _core  # noqa: E402
 from oracle.metrics import synthetic_mri  # noqa: E402
@@ -158,7 +159,7 @@ def _sketch_and_emulate(a_cores, b_cores, shape, storage, max_bond, oversample, 
     dims = a.mps.dims
     ell = hd.sketch_bonds(dims, a.mps.bonds, b.mps.bonds, max_bond, oversample)
     R = hd.sketch_cores(dims, ell, seed)
-    got = a._hadamard_sketch(b, ell, R)
+    got = oncore.hadamard_sketch(a.mps, b.mps, ell, R)
     want, ranks = hd.emulate(ah, bh, dims, ell, R)
     return got, want, ranks, hc.dense_product(ah, bh)
 

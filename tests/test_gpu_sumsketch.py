@@ -6,7 +6,7 @@ Bars, and where they come from:
   and fp64, and every partial sum stays below 2**53 (at most 8 * 64 * 130 terms of at most 64), so the fp64 results
   equal NumPy's exactly whatever the order of summation; the output buffer is pre-filled with a sentinel and
   everything past the results keeps it.
-* Sketch (``_sum_sketch``) against ``core.sumsketch.emulate`` with the same random cores: identical ranks, and the
+* Sketch (``oncore.sum_sketch``) against ``core.sumsketch.emulate`` with the same random cores: identical ranks, and the
   decoded chains agree within ``1e-9 |sum|`` (the bar tests/test_gpu_hadamard.py uses for the same comparison).
 * End to end on planted ranks: ``|out.to_tensor() - dense sum| <= tol |sum|`` (Frobenius), tol 1e-5 for fp32 / bf16 work
   and 1e-7 for fp64 (tests/test_gpu_hadamard.py, tests/test_gpu_lincomb.py).
@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 
 from imgcompressionmps_amd import NDMPS, _lib  # noqa: E402
 from imgcompressionmps_amd.core import hadamard as hd  # noqa: E402
+from imgcompressionmps_amd.core import oncore  # noqa: E402
 from imgcompressionmps_amd.core import sumsketch as ss  # noqa: E402
 from imgcompressionmps_amd.core.mps import DeviceMPS  # noqa: E402
 from imgcompressionmps_amd.utils import core as _core  # noqa: E402
@@ -157,7 +158,7 @@ def _sketch_and_emulate(frames, w, shape, storage, max_bond, oversample, seed):
     dims = objs[0].mps.dims
     ell = ss.sketch_bonds(dims, [o.mps.bonds for o in objs], max_bond, oversample)
     R = hd.sketch_cores(dims, ell, seed)
-    got = NDMPS._sum_sketch(objs, np.asarray(w, dtype=np.float64), ell, R)
+    got = oncore.sum_sketch([o.mps for o in objs], np.asarray(w, dtype=np.float64), ell, R)
     return got, ss.emulate(held, w, dims, ell, R), [sc.dense_sum(held, row) for row in w]
 
 

@@ -27,6 +27,7 @@ pytestmark = pytest.mark.gpu
 
 import wgram_cases as wc  # noqa: E402
 from imgcompressionmps_amd import NDMPS, _lib  # noqa: E402
+from imgcompressionmps_amd.core import oncore  # noqa: E402
 from imgcompressionmps_amd.core import series as se  # noqa: E402
 from imgcompressionmps_amd.core import wgram as wg  # noqa: E402
 from imgcompressionmps_amd.core.mps import DeviceMPS  # noqa: E402
@@ -61,8 +62,11 @@ def _objects(name, case=None):
 def _abi(objs, others, weight, cap=None, fill=None):
     """G_w through the C ABI: the workspace the query asks for under ``cap``, optionally pre-filled with a byte."""
     lib = _lib.load()
-    objs, cols, c_dims, sa, sb = NDMPS._series_args(objs, others)
-    sw = NDMPS._weight_args(objs if others is None else objs + cols, weight)
+    cols, c_dims = objs if others is None else others, _lib.i64_array(objs[0].mps.dims)
+    sa = oncore.chain_list_args([o.mps for o in objs])
+    sb = sa if others is None else oncore.chain_list_args([o.mps for o in others])
+    bonds_w, codes_w, ptrs_w = oncore.chain_list_args([weight.mps])
+    sw = (bonds_w, codes_w[0], ptrs_w)
     Ka, Kb, L, sym = len(objs), len(cols), objs[0].mps.L, 1 if others is None else 0
     nbytes = _lib.check(lib.ndmps_series_wgram_workspace_bytes(Ka, Kb, sym, L, c_dims, sa[0], sb[0], sw[0],
                                                                wg.WS_LIMIT_BYTES if cap is None else cap))

@@ -181,6 +181,26 @@ def test_rank_rule():
     assert lc.work_is_f64([0, 1, 2]) and not lc.work_is_f64([0, 1])
 
 
+@pytest.mark.parametrize("dtype,with_f64,without_f64", [
+    (None, True, False),               # the inputs decide
+    ("torch.float32", False, False),   # fp32 asked for: fp32 work whatever the inputs
+    ("torch.bfloat16", True, False),   # bf16 only rounds the finished cores: the inputs decide
+    ("torch.float64", True, True),     # fp64 asked for
+])
+def test_work_type_truth_table(dtype, with_f64, without_f64):
+    """``work_is_f64(codes, dtype)`` on all eight rows: dtype in {None, fp32, bf16, fp64} x {some fp64 input, none}."""
+    assert lc.work_is_f64([0, 2, 1], dtype) is with_f64
+    assert lc.work_is_f64([0, 1, 1], dtype) is without_f64
+
+
+def test_work_type_takes_torch_dtypes():
+    torch = pytest.importorskip("torch")
+    for dtype in (None, torch.float32, torch.bfloat16, torch.float64):
+        for codes in ([0, 2], [1, 0]):
+            assert lc.work_is_f64(codes, dtype) == lc.work_is_f64(codes, None if dtype is None else str(dtype))
+    assert lc.work_is_f64([0], torch.float64) and not lc.work_is_f64([2], torch.float32)
+
+
 @pytest.mark.parametrize("K", [361, 362, 400, 4096])
 def test_many_inputs_pass_validation(K):
     """K (K + 1) / 2 pair tasks exceed one launch's 65535 from K = 362 on; the host accepts such K whenever the summed
