@@ -162,6 +162,7 @@ SIGNATURES = {
     "ndmps_potrf_lower_f64": (C.c_int, [vp, i64, vp, C.POINTER(C.c_int), vp]),
     "ndmps_syevd_topk_workspace_bytes": (i64, [i64, C.c_int, i64]),
     "ndmps_syevd_topk_stamps_offset": (i64, [i64, C.c_int, i64]),
+    "ndmps_syevd_topk_reduction_offsets": (C.c_int, [i64, C.c_int, i64, p_i64]),
     "ndmps_syevd_topk_values_f64": (C.c_int, [C.c_int, vp, i64, p_i64, vp, i64, vp, i64, i64, vp, i64, vp]),
     "ndmps_syevd_topk_vectors_f64": (C.c_int, [C.c_int, p_i64, p_i64, i64, vp, i64, p_int, vp]),
     "ndmps_syevd_topk_vectors_auto_f64": (C.c_int, [C.c_int, p_i64, i64, C.c_double, vp, vp, i64, vp, vp, i64, vp]),

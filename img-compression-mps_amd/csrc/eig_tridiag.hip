@@ -156,18 +156,26 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 
 // Householder vector of x = (alpha, rest) with sigma = |rest|^2:  H x = beta e_1,  H = I - tau v v^T, v_1 = 1,
 // v_rest = rest * scale.  sigma == 0 gives H = I (LAPACK dlarfg).
+// A column of norm below 2^-450 was squared into the subnormal range: its sigma carries no digits and a reflector
+// built from it is not orthogonal (found on c h h^T with |h_i| = 1, where every entry of the trailing matrix rounds alike:
+// what a step leaves is again of rank one, 2^-53 times smaller, column after column down to the subnormals).  Such a
+// column is taken for zero -- H = I, its entries below the sub-diagonal are dropped: 2^-450 against inputs of 2^+-250.
+constexpr double kHouseholderFloor = 0x1p-900;
 __device__ __forceinline__ void householder(double alpha, double sigma, double& beta, double& tau, double& scale) {
-  if (sigma == 0.0) {
+  const double h2 = fma(alpha, alpha, sigma);
+  if (sigma == 0.0 || h2 < kHouseholderFloor) {
     beta = alpha;
     tau = 0.0;
     scale = 0.0;
     return;
   }
-  const double h2 = fma(alpha, alpha, sigma);
   const double rs = fast_rsqrt<2>(h2);
   const double nrm = h2 * rs;
   beta = alpha >= 0.0 ? -nrm : nrm;
-  tau = (beta - alpha) * (alpha >= 0.0 ? -rs : rs);
+  // (beta - alpha) / beta lies in [1, 2]; the rounded product with rs may miss an end by an ulp (alpha == 0 gives
+  // h2 rs rs).  The comparisons leave a NaN a NaN.
+  const double t = (beta - alpha) * (alpha >= 0.0 ? -rs : rs);
+  tau = t < 1.0 ? 1.0 : (t > 2.0 ? 2.0 : t);
   scale = fast_rcp<2>(alpha - beta);
 }
 
@@ -1052,10 +1060,11 @@ __global__ void __launch_bounds__(512) trd_tail_reg_kernel(const TrdDesc* __rest
   __shared__ double yv[kTail];      // y = S v_j of the pass, for the prologue wave
   __shared__ double red_s[8];
 
-  // the reflectors of the tail are zero outside rows J .. n - 1: written once, the loop stores the live part only
+  // the reflectors of the tail are zero outside rows J .. n - 1: written once, the loop stores the live part only;
+  // row n - 1 holds no reflector and is zero throughout (as trd_tail_kernel leaves it)
   for (int64_t e = tid; e < (int64_t)m * lda; e += 512) {
     const int i = (int)(e % lda);
-    if (i < J || i >= n) Vh[(int64_t)J * lda + e] = 0.0;
+    if (i < J || i >= n || e >= (int64_t)(m - 1) * lda) Vh[(int64_t)J * lda + e] = 0.0;
   }
   // pending update of the last column of the resident part
   if (J >= 1) {
@@ -2402,6 +2411,7 @@ TrdSwitches trd_switches() {
 struct TrdLayout {
   int64_t n_max, lda, kp, total;
   int64_t off_stamps, off_desc, off_desc2;  // what the size queries report
+  int64_t off_vh, off_tau, off_d, off_e;    // ... and ndmps_syevd_topk_reduction_offsets
   TrdWork w;                                // the buffers the kernels see
   TrdDesc *desc, *desc2;  // desc2: the trailing blocks the resident kernel finishes behind the panels
   // more than kMaxK vectors, or one or two big matrices (eig_wide.inc)
@@ -2425,15 +2435,15 @@ TrdLayout trd_layout(int64_t n_max, int64_t batch, int64_t k_max, const TrdSwitc
     return off;
   };
   take(w.A, batch * n_max * l.lda * 8);
-  take(w.Vh, batch * n_max * l.lda * 8);
+  l.off_vh = take(w.Vh, batch * n_max * l.lda * 8);
   take(w.y, batch * 2 * l.lda * 8);
   take(w.xc, batch * 2 * l.lda * 8);
   take(w.yr, batch * 2 * l.lda * 16);
   take(w.xr, batch * 2 * l.lda * 16);
   take(w.sync, batch * (int64_t)sizeof(TeamSync));
-  take(w.tau, batch * n_max * 8);
-  take(w.d, batch * n_max * 8);
-  take(w.e, batch * n_max * 8);
+  l.off_tau = take(w.tau, batch * n_max * 8);
+  l.off_d = take(w.d, batch * n_max * 8);
+  l.off_e = take(w.e, batch * n_max * 8);
   take(w.lam, batch * n_max * 8);
   take(w.mu, batch * n_max * 8);
   take(w.bound, batch * 8);
@@ -3137,6 +3147,17 @@ int trd_prepare(int batch, const int64_t* h_n, const int64_t* h_k, int64_t k_max
 extern "C" int64_t ndmps_syevd_topk_stamps_offset(int64_t n_max, int batch, int64_t k_max) {
   if (n_max <= 0 || n_max > kMaxN || batch <= 0 || k_max <= 0 || k_max > kMaxN) return -1;
   return trd_layout(n_max, batch, std::min(k_max, n_max), trd_switches()).off_stamps;
+}
+// test hook: where phase 1 leaves its result in the workspace -- byte offsets of Vh, tau, d, e, and lda in doubles
+// (members n_max * lda, n_max, n_max, n_max doubles apart); host arithmetic only
+extern "C" int ndmps_syevd_topk_reduction_offsets(int64_t n_max, int batch, int64_t k_max, int64_t* h_out) {
+  NDMPS_REQUIRE(h_out && n_max > 0 && n_max <= kMaxN && batch > 0 && k_max > 0 && k_max <= kMaxN,
+                "NULL output, or n_max=%lld, batch=%d or k_max=%lld outside the solver's range", (long long)n_max, batch,
+                (long long)k_max);
+  const TrdLayout l = trd_layout(n_max, batch, std::min(k_max, n_max), trd_switches());
+  const int64_t out[5] = {l.off_vh, l.off_tau, l.off_d, l.off_e, l.lda};
+  std::copy(out, out + 5, h_out);
+  return NDMPS_OK;
 }
 extern "C" int64_t ndmps_syevd_topk_max_n(void) { return kMaxN; }
 extern "C" int64_t ndmps_syevd_topk_max_k(void) { return kMaxK; }

@@ -311,6 +311,19 @@ int64_t ndmps_syevd_topk_workspace_bytes(int64_t n_max, int batch, int64_t k_max
 /* byte offset, inside the workspace, of 16 int64 wall-clock marks (100 MHz) per matrix left by the vectors
  * phase (profiling aid, tools/trd_probe.py) */
 int64_t ndmps_syevd_topk_stamps_offset(int64_t n_max, int batch, int64_t k_max);
+/* TEST HOOK: where ndmps_syevd_topk_values_f64 leaves the tridiagonalisation Q^T A Q = T of A = (G + G^T) / 2 in the
+ * workspace (tests/trd_cases.py).  h_out[0..3] = byte offsets of Vh, tau, d and e, h_out[4] = lda in doubles (n_max
+ * rounded up to 2); member b lies b * n_max * lda (Vh) and b * n_max (tau, d, e) doubles further on.  Host arithmetic
+ * only, no GPU call, no effect on any launch; NDMPS_TRD_BAND / _SYM are read as _workspace_bytes reads them (they do
+ * not move these buffers).  For a member of order n, by every one-stage reduction:
+ *   Q = H_0 H_1 ... H_{n-2},  H_j = I - tau[j] v_j v_j^T,  v_j = row j of Vh (lda doubles per row);
+ *   v_j is 0.0 at the indices 0 .. j, exactly 1.0 at j + 1, and 0.0 at n .. lda - 1; tau[j] is 0 (H_j = I) or in [1, 2];
+ *   d[j] = T[j][j], e[j] = T[j + 1][j]; e[n - 1] = tau[n - 1] = 0 and row n - 1 of Vh is zero.
+ * A column whose part below the diagonal has a norm under 2^-450 is taken for zero (H_j = I): the reduction squares
+ * entries without rescaling, and matrices are expected within 2^+-250.
+ * The two-stage reductions (NDMPS_TRD_BAND) leave d and e alike; their Vh holds the block reflectors of the first
+ * stage only, in another format. */
+int ndmps_syevd_topk_reduction_offsets(int64_t n_max, int batch, int64_t k_max, int64_t* h_out);
 /* Cholesky factor S = L L^T of a symmetric positive definite matrix (lower triangle read, L with zeros above written in
  * place; blocked, fp64 MFMA): the square root compress() needs of G2 = T2 T2^T (core/ndmps.py:104-106; quimb takes an LQ of
  * T2 there).  d_scratch: ndmps_potrf_scratch_elems(n) doubles.  Synchronises; *h_status = 1: not positive definite. */
