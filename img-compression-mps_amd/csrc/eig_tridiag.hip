@@ -387,9 +387,10 @@ trd_column_kernel(const TrdDesc* __restrict__ desc, TrdWork w, int j) {
 // in its registers (16 tiles of 4 doubles per lane = 128 KB per workgroup, two workgroups per CU), so the
 // column launches' traffic -- one read and one write of the trailing matrix per column, the bound of
 // trd_column_kernel -- disappears; what remains per column is the exchange the kernel boundary
-// used to provide: every workgroup publishes its 32 entries of y_j = A v_j, the owner of column j + 1 publishes
-// that column (row j + 1 by symmetry), the matrix's workgroups meet at a counter in global memory and each
-// reads the two n-vectors back.  Exchange data moves with agent-scope atomic stores / loads (write-through,
+// used to provide: every workgroup publishes its 32 entries of y_j = A v_j and its 32 entries of row j + 1 (column
+// j + 1 by symmetry; nobody selects and stores a whole column while the team waits -- the kernels with tagged records
+// or 8-column blocks still have the owner of column j + 1 publish it), the matrix's workgroups meet at a counter in
+// global memory and each reads the two n-vectors back.  Six barriers per column.  Exchange data moves with agent-scope atomic stores / loads (write-through,
 // never served from a stale L2 line of another XCD); release / acquire fences order them around the counter.
 //
 // The workgroups of a matrix (its team, 16 at n = 512) must be resident together.  Liveness rests on three
@@ -419,6 +420,15 @@ __device__ __forceinline__ double team_load(const double* p) {
 __device__ __forceinline__ void team_store(double* p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// two neighbouring values in one 16-byte write-through store (16-byte aligned).  The instruction is hidden from the
+// compiler: the two wait states behind it keep the next instruction off its data registers, and the storing wave
+// drains it with the s_waitcnt vmcnt(0) in front of the meeting.
+typedef double team_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void team_store2(double* p, double v0, double v1) {
+  const team_f64x2 q = {v0, v1};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(q) : "memory");
 }
 
 // (value, tag) records: ONE 16-byte agent-scope store / load each, so a reader sees either the old record or the
@@ -511,6 +521,9 @@ trd_team_kernel(TrdDesc* __restrict__ desc, TrdWork w, int b0, unsigned epoch) {
   constexpr int RPW = 64 / LPR;      // rows per wave instruction
   constexpr int RPI = 4 * RPW;       // rows per tile of the workgroup
   constexpr int NT = MR / RPI;       // tiles per lane: MR rows
+  // the 32-column counter kernel: every live workgroup publishes its 32 entries of row j + 1; the others keep the
+  // owner's column (tagged records are polled row by row, and 8-column blocks would send 64 workgroups to one line)
+  constexpr bool kRowPublish = !TAGGED && CW == 32 && NR == 2;
   int member, team;
   if (!team_place(w, member, team)) return;
   TrdDesc& d = desc[b0 + team];
@@ -787,6 +800,31 @@ trd_team_kernel(TrdDesc* __restrict__ desc, TrdWork w, int b0, unsigned epoch) {
       }
     }
     TEAM_STAMP(4)
+    // ---- row j + 1 of the updated matrix (column j + 1 by symmetry), 32 entries from every live workgroup: the row
+    //      sits in tile u0 of the eight lanes of one wave that hold it, four columns each.  u0 is uniform: one scalar
+    //      branch into NT copies of two 16-byte stores from fixed registers (a run-time register index would send the
+    //      tiles to scratch).  Issued here, the stores are acknowledged while the column sums fold.
+    if constexpr (kRowPublish) {
+      if (j + 1 < J) {
+        double* out = xc + ((j + 1) & 1) * lda + c;
+        const bool mine = row0 == (j + 1) % RPI;
+        const bool lo = mine && c < lda, hi = mine && c + 2 < lda;  // lda is even, c a multiple of 4
+#define NDMPS_TEAM_ROW(U)                              \
+  case U:                                              \
+    if (lo) team_store2(out, a[U][0], a[U][1]);        \
+    if (hi) team_store2(out + 2, a[U][2], a[U][3]);    \
+    break;
+        static_assert(NT == 16, "one case per tile");
+        switch (u0) {
+          NDMPS_TEAM_ROW(0) NDMPS_TEAM_ROW(1) NDMPS_TEAM_ROW(2) NDMPS_TEAM_ROW(3)
+          NDMPS_TEAM_ROW(4) NDMPS_TEAM_ROW(5) NDMPS_TEAM_ROW(6) NDMPS_TEAM_ROW(7)
+          NDMPS_TEAM_ROW(8) NDMPS_TEAM_ROW(9) NDMPS_TEAM_ROW(10) NDMPS_TEAM_ROW(11)
+          NDMPS_TEAM_ROW(12) NDMPS_TEAM_ROW(13) NDMPS_TEAM_ROW(14) NDMPS_TEAM_ROW(15)
+          default: break;
+        }
+#undef NDMPS_TEAM_ROW
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] = ndmps_lanes::sum_adjacent<RPW>(acc[k]);
     if (q == 0) {
@@ -803,7 +841,7 @@ trd_team_kernel(TrdDesc* __restrict__ desc, TrdWork w, int b0, unsigned epoch) {
     if (j + 1 >= J) break;  // the tail kernel continues from the stored matrix
     // ---- column j + 1 of the updated matrix, by its owner (publishing it before the column sums are folded gains
     //      nothing at orders <= 1024 and costs the 32-column kernel its last registers)
-    if (member == (j + 1) / CW) {
+    if (!kRowPublish && member == (j + 1) / CW) {
       const int kk = j + 1 - c0;
       if (p == kk / 4) {
         double* out = xc + ((j + 1) & 1) * lda;
