@@ -135,6 +135,12 @@ SIGNATURES = {
                                           vp]),
     "ndmps_valstat_error_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, vp, vp, i64, p_f64, p_i64, vp, i64,
                                           vp]),
+    "ndmps_axisext_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64,
+                                    vp]),
+    "ndmps_axisext_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64,
+                                    vp]),
+    "ndmps_argext_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
+    "ndmps_argext_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,
                                                            i64, vp, i64, vp]),
     "ndmps_gemm_batched_max": (C.c_int, []),

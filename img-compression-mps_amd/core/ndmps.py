@@ -1917,16 +1917,51 @@ class NDMPS:
         return _vs.value_stats(chain)
 
     def min(self, axis=None):
-        """``to_tensor().min()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError."""
+        """``to_tensor().min()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError: ``amin`` takes one."""
         if axis is not None:
             raise NotImplementedError("min over an axis is not implemented: only the whole volume (axis=None)")
         return self.value_stats()["min"]
 
     def max(self, axis=None):
-        """``to_tensor().max()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError."""
+        """``to_tensor().max()`` from the cores (``value_stats``); an ``axis`` raises NotImplementedError: ``amax`` takes one."""
         if axis is not None:
             raise NotImplementedError("max over an axis is not implemented: only the whole volume (axis=None)")
         return self.value_stats()["max"]
+
+    def amax(self, axis=None, keepdims: bool = False, as_torch: bool = False):
+        """``to_tensor().max(axis, keepdims=keepdims)`` from the cores, in the cores' element type: a maximum-intensity
+        projection without the volume (core/axisext.py).  ``axis``: an int or a tuple of ints, negative values from the
+        end; None or every axis gives the scalar of ``value_stats``.  A NumPy array, or a device tensor with
+        ``as_torch``.  NaN voxels take no part (``np.fmax.reduce``); a ray of NaN only gives NaN.  numpy's AxisError for
+        an axis out of range, ValueError for a repeated axis and what ``value_stats`` refuses."""
+        from . import axisext as _ax
+
+        chain, plan = self._valstat_chain("amax", with_plan=True)
+        return _ax.reduce_values(chain, plan, "max", axis, keepdims, as_torch)
+
+    def amin(self, axis=None, keepdims: bool = False, as_torch: bool = False):
+        """``to_tensor().min(axis, keepdims=keepdims)`` from the cores; as ``amax``."""
+        from . import axisext as _ax
+
+        chain, plan = self._valstat_chain("amin", with_plan=True)
+        return _ax.reduce_values(chain, plan, "min", axis, keepdims, as_torch)
+
+    def argmax(self, axis=None, keepdims: bool = False, as_torch: bool = False, return_values: bool = False):
+        """``np.argmax(to_tensor(), axis, keepdims=keepdims)`` from the cores: an int64 array of the first occurrence
+        along an int ``axis``, or with ``axis=None`` the flat C-order index as an int.  ``return_values=True`` returns
+        ``(indices, values)`` from the same call.  NaN voxels take no part; a ray (or a volume) of NaN only has index
+        -1.  TypeError for a tuple ``axis``, as NumPy's; otherwise the refusals of ``amax``."""
+        from . import axisext as _ax
+
+        chain, plan = self._valstat_chain("argmax", with_plan=True)
+        return _ax.reduce_index(chain, plan, "max", axis, keepdims, as_torch, return_values)
+
+    def argmin(self, axis=None, keepdims: bool = False, as_torch: bool = False, return_values: bool = False):
+        """``np.argmin(to_tensor(), axis, keepdims=keepdims)`` from the cores; as ``argmax``."""
+        from . import axisext as _ax
+
+        chain, plan = self._valstat_chain("argmin", with_plan=True)
+        return _ax.reduce_index(chain, plan, "min", axis, keepdims, as_torch, return_values)
 
     def histogram(self, bins=256, range=None, outliers: bool = False):
         """``numpy.histogram(to_tensor(), bins, range)`` from the cores: ``(counts int64, edges)``.  ``bins`` is an int

@@ -4,12 +4,15 @@
 //   ndmps_valstat_moments_*    <- NDMPS.value_stats / min / max      (core/valstat.py)
 //   ndmps_valstat_histogram_*  <- NDMPS.histogram / quantile
 //   ndmps_valstat_error_*      <- NDMPS.error_to / psnr_to
+//   ndmps_axisext_*            <- NDMPS.amax / amin / argmax / argmin along axes   (core/axisext.py)
+//   ndmps_argext_*             <- NDMPS.argmax / argmin of the whole volume
 //
 // chain_stats_plan (valstat_plan.h) is chain_plan with the last product's destination removed and the output's
 // role as second cumulative buffer taken by ws_left2.  Every product before the last runs through ndmps_sgemm /
 // ndmps_dgemm exactly as run_chain issues them (chain.hip); the last one is valstat_product_kernel, a tiled MFMA
 // product (v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64, lane maps as in gemm.hip) on a persistent grid whose
-// accumulator tiles are handed, element by element, to one of three epilogues:
+// accumulator tiles are handed, element by element, to an epilogue: the three below, and the two of the extremes
+// (AxisEpi, ArgEpi: described where they stand):
 //
 //   Moments    count, min, max, sum, sum of squares, NaN count.  NaN voxels are counted and take no part in the rest.
 //   Histogram  np.histogram against an explicit edge table held in LDS: bin b takes edges[b] <= v < edges[b + 1], the
@@ -23,7 +26,8 @@
 // Determinism: sums are fp64 and nothing floating-point is added atomically.  A thread's elements are a fixed
 // function of the shape (tile t goes to workgroup t mod grid, the grid is a function of the tile count), a
 // workgroup folds its threads by a fixed shuffle tree and writes one partial record, and valstat_fold_kernel folds
-// the records in index order: the same inputs give the same bits.  The histogram adds integers.
+// the records in index order: the same inputs give the same bits.  The histogram adds integers, and the extremes
+// along axes take integer maxima of order-preserving keys: both are associative and commutative.
 #include <math.h>
 
 #include <type_traits>
@@ -205,6 +209,173 @@ struct HistEpi {
   }
 };
 
+// ---- extremes along axes, and the place of the global extreme (core/axisext.py)
+// A voxel becomes an unsigned key whose integer order is the order of the values: the bits with the sign bit set for
+// v >= 0 and all bits flipped for v < 0, complemented once more when the minimum is wanted, so that "the extreme" is
+// always the largest key.  -0 is made +0 first (v + 0), so the two compare equal.  NaN takes no part and gets key 0,
+// which no other value maps to (-inf maps to 0x007F..., and so does +inf after the complement).
+template <typename T>
+struct KeyOf {
+  typedef typename std::conditional<sizeof(T) == 4, unsigned int, unsigned long long>::type type;
+};
+template <typename T, bool MIN>
+__host__ __device__ __forceinline__ typename KeyOf<T>::type ext_key(T v) {
+  typedef typename KeyOf<T>::type K;
+  if (v != v) return (K)0;
+  v = v + (T)0;
+  K b;
+  __builtin_memcpy(&b, &v, sizeof(T));
+  const K sign = (K)1 << (8 * sizeof(T) - 1);
+  b ^= (b & sign) ? ~(K)0 : sign;
+  return MIN ? (K)~b : b;
+}
+// the value of a key; key 0 (nothing taken) is NaN
+template <typename T>
+__host__ __device__ __forceinline__ T ext_value(typename KeyOf<T>::type key, bool min) {
+  typedef typename KeyOf<T>::type K;
+  if (key == 0) return (T)NAN;
+  if (min) key = (K)~key;
+  const K sign = (K)1 << (8 * sizeof(T) - 1);
+  key ^= (key & sign) ? sign : ~(K)0;
+  T v;
+  __builtin_memcpy(&v, &key, sizeof(T));
+  return v;
+}
+
+struct AxisArgs {
+  const int64_t* row_out;    // [m]  offset into the projected array = row_out[r] + col_out[c]
+  const int64_t* col_out;    // [n]  in the column order of B as the kernel sees it: equal entries are adjacent
+  const int32_t* row_idx;    // [m]  coordinate along the reduced axis = row_idx[r] + col_idx[c] (index modes only)
+  const int32_t* col_idx;    // [n]
+  void* keys;                // [out_numel] KEYS: keys of the element type's width.  PACKED: 64-bit (key << 32 | ~index)
+                             //             MATCH: the finished 64-bit keys of the first pass, read only
+  unsigned long long* index; // [out_numel] MATCH: the smallest index whose key equals the stored one
+  int64_t out_numel;
+};
+
+enum { kAxisKeys = 0, kAxisPacked = 1, kAxisMatch = 2 };
+
+// Every cell of the projected array is the integer maximum of the scores sent to it, so the result does not depend
+// on the order of arrival.  KEYS: score = key.  PACKED (fp32): score = key << 32 | (0xFFFFFFFF - index), the larger
+// value and among equal values the smaller index.  MATCH (fp64, second pass of the same product): score =
+// UINT64_MAX - index where the element's key equals the finished key of its cell, and the cell takes the minimum
+// index.  Score 0 is "nothing".  Before the atomic, the lanes of one row that share a cell (their columns are
+// adjacent: the planner sorts them so) fold by a segmented shuffle, only the first lane of a segment goes on, and it
+// holds its score back while the next elements it takes have the same cell.
+template <typename T, bool MIN, int MODE>
+struct AxisEpi {
+  typedef AxisArgs Args;
+  typedef typename KeyOf<T>::type K;
+  typedef typename std::conditional<MODE == kAxisKeys, K, unsigned long long>::type S;
+  static constexpr int W = sizeof(T) == 4 ? 32 : 16;  // lanes of one row of an accumulator tile
+  int64_t held_at;
+  S held;
+
+  __device__ __forceinline__ void begin(const Args&) {
+    held_at = -1;
+    held = 0;
+  }
+  __device__ __forceinline__ void send(const Args& a, int64_t at, S score) {
+    if constexpr (MODE == kAxisKeys) {
+      atomicMax(static_cast<K*>(a.keys) + at, score);
+    } else if constexpr (MODE == kAxisPacked) {
+      atomicMax(static_cast<unsigned long long*>(a.keys) + at, score);
+    } else {
+      atomicMin(a.index + at, ~score);
+    }
+  }
+  __device__ __forceinline__ void take(const Args& a, bool valid, int64_t row, int64_t col, T v) {
+    // a padded element has cell -1 and score 0: it shares a segment with padding only, and sends nothing
+    int64_t at = -1;
+    S score = 0;
+    if (valid) {
+      at = a.row_out[row] + a.col_out[col];
+      if (at < 0 || at >= a.out_numel) at = -1;  // the tables are not trusted: nothing is touched outside the result
+    }
+    if (at >= 0) {
+      const K key = ext_key<T, MIN>(v);
+      if constexpr (MODE == kAxisKeys) {
+        score = key;
+      } else {
+        const unsigned int idx = (unsigned int)(a.row_idx[row] + a.col_idx[col]);
+        if constexpr (MODE == kAxisPacked)
+          score = key ? ((unsigned long long)key << 32) | (0xFFFFFFFFu - idx) : 0ull;
+        else
+          score = (key && key == static_cast<const K*>(a.keys)[at]) ? ~(unsigned long long)idx : 0ull;
+      }
+    }
+    // the W lanes of one row: segments of equal cells are contiguous, so doubling over "the lane `off` further on has
+    // my cell" folds each segment into its first lane
+    const int pos = (int)(threadIdx.x & (W - 1));
+#pragma unroll
+    for (int off = 1; off < W; off <<= 1) {
+      const int64_t o_at = __shfl_down((long long)at, off, W);
+      const S o_score = __shfl_down(score, off, W);
+      if (pos + off < W && o_at == at && o_score > score) score = o_score;
+    }
+    const int64_t before = __shfl_up((long long)at, 1, W);
+    const bool head = pos == 0 || before != at;
+    if (!head || at < 0 || score == 0) return;
+    if (at == held_at) {
+      if (score > held) held = score;
+      return;
+    }
+    if (held_at >= 0) send(a, held_at, held);
+    held_at = at;
+    held = score;
+  }
+  __device__ __forceinline__ void finish(const Args& a) {
+    if (held_at >= 0) send(a, held_at, held);
+  }
+};
+
+// the place of the global extreme: one (key, offset) per thread, the smaller offset on equal keys, no atomics
+struct ArgRec {
+  unsigned long long key;  // 0: nothing taken
+  long long at;            // row_off[r] + col_off[c], the flat C-order index
+};
+__device__ __forceinline__ void argrec_fold(ArgRec& a, const ArgRec& b) {
+  if (b.key > a.key || (b.key == a.key && b.key != 0 && b.at < a.at)) a = b;
+}
+__device__ __forceinline__ void argrec_fold_wave(ArgRec& r) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    ArgRec o;
+    o.key = __shfl_down(r.key, off);
+    o.at = __shfl_down(r.at, off);
+    argrec_fold(r, o);
+  }
+}
+
+struct ArgArgs {
+  ArgRec* partials;        // one per workgroup
+  const int64_t* row_off;  // [m]
+  const int64_t* col_off;  // [n], in the column order of B as the kernel sees it
+};
+
+template <typename T, bool MIN>
+struct ArgEpi {
+  typedef ArgArgs Args;
+  ArgRec r;
+  __device__ __forceinline__ void begin(const Args&) { r.key = 0, r.at = -1; }
+  __device__ __forceinline__ void take(const Args& a, bool valid, int64_t row, int64_t col, T v) {
+    if (!valid) return;
+    const ArgRec mine{(unsigned long long)ext_key<T, MIN>(v), (long long)(a.row_off[row] + a.col_off[col])};
+    argrec_fold(r, mine);
+  }
+  __device__ __forceinline__ void finish(const Args& a) {
+    __shared__ ArgRec waves[4];
+    argrec_fold_wave(r);
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      ArgRec t = waves[0];
+      for (int w = 1; w < 4; ++w) argrec_fold(t, waves[w]);
+      a.partials[blockIdx.x] = t;
+    }
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ the product
 // C = A (m x k) B (k x n), dense row-major, tile by tile on a persistent grid; column c of B is B[:, perm[c]] when
 // perm is given (the columns in memory order of the volume, for a chain whose decode has no gather buffer).  Rows
@@ -319,6 +490,42 @@ valstat_gather_cols_kernel(const T* __restrict__ in, T* __restrict__ out, int64_
 
 template <typename T>
 __global__ void valstat_unit_kernel(T* p) { *p = (T)1; }
+
+template <typename K>
+__global__ void __launch_bounds__(256) axisext_fill_kernel(K* __restrict__ p, int64_t count, K value) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (int64_t)gridDim.x * 256) p[e] = value;
+}
+
+// keys -> values, in place (the key buffer is the result buffer); an untouched cell becomes NaN.  index (may be
+// NULL, fp64 with indices): a cell no pass touched still holds INT64_MAX and becomes -1.
+template <typename T>
+__global__ void __launch_bounds__(256)
+axisext_decode_kernel(void* __restrict__ values, long long* __restrict__ index, int64_t count, bool min) {
+  typedef typename KeyOf<T>::type K;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (int64_t)gridDim.x * 256) {
+    const K key = static_cast<const K*>(values)[e];
+    static_cast<T*>(values)[e] = ext_value<T>(key, min);
+    if (index && index[e] == INT64_MAX) index[e] = -1;
+  }
+}
+
+// fp32 with indices: packed[e] = key << 32 | (0xFFFFFFFF - index) -> values[e] and, in place, the int64 index
+__global__ void __launch_bounds__(256)
+axisext_unpack_kernel(unsigned long long* __restrict__ packed, float* __restrict__ values, int64_t count, bool min) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (int64_t)gridDim.x * 256) {
+    const unsigned long long p = packed[e];
+    values[e] = ext_value<float>((unsigned int)(p >> 32), min);
+    reinterpret_cast<long long*>(packed)[e] = p ? (long long)(0xFFFFFFFFu - (unsigned int)p) : -1ll;
+  }
+}
+
+// result <- the partial places folded in index order (one wavefront)
+__global__ void __launch_bounds__(64) argext_fold_kernel(const ArgRec* __restrict__ partials, int count, ArgRec* result) {
+  ArgRec r{0ull, -1ll};
+  for (int i = threadIdx.x; i < count; i += 64) argrec_fold(r, partials[i]);
+  argrec_fold_wave(r);
+  if (threadIdx.x == 0) *result = r;
+}
 
 // ------------------------------------------------------------------------------------------------ host
 struct ErrorTables {
@@ -485,7 +692,130 @@ int valstat_histogram(int L, const int64_t* h_dims, const int64_t* h_bonds, cons
   return NDMPS_OK;
 }
 
+template <typename T, typename Epi>
+int axisext_product(const ChainProduct& q, const Operands& ops, const typename Epi::Args& args, hipStream_t s) {
+  hipLaunchKernelGGL((valstat_product_kernel<T, Epi>), dim3(valstat_grid(q)), dim3(256), 0, s, (const T*)ops.A,
+                     (const T*)ops.B, ops.perm, q.m, q.n, q.k, args);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
+
+// the extreme (op 0: max, 1: min) of every cell of the projected array, and with the index tables its place along
+// the one reduced axis
+template <typename T>
+int axisext_run(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* const* h_cores, int op,
+                const int64_t* d_row_out, const int64_t* d_col_out, const int32_t* d_col_perm, int64_t n_cols,
+                const int32_t* d_row_idx, const int32_t* d_col_idx, int64_t out_numel, T* d_values, int64_t* d_index,
+                void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  typedef typename KeyOf<T>::type K;
+  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds, "bad axisext argument");
+  NDMPS_REQUIRE(op == 0 || op == 1, "axisext: op %d is neither 0 (max) nor 1 (min)", op);
+  NDMPS_REQUIRE(d_row_out && d_col_out && d_col_perm && d_values && out_numel >= 1, "axisext: NULL table or result");
+  const bool index = d_index != nullptr;
+  NDMPS_REQUIRE((d_row_idx != nullptr) == index && (d_col_idx != nullptr) == index,
+                "axisext: the index tables and d_index are given together or not at all");
+  const ChainStatsPlan sp = ndmps::chain_stats_plan(L, h_dims, h_bonds, sizeof(T), 0);
+  // valstat_check's table conditions (none NULL, n_cols is the last product's); the result stands where the original does
+  const ErrorTables tables{d_values, d_row_out, d_col_out, d_col_perm, n_cols};
+  NDMPS_TRY(valstat_check(sp, h_dims, h_bonds, h_cores, d_ws, ws_bytes, &tables));
+  hipStream_t s = (hipStream_t)stream;
+  Operands ops;
+  NDMPS_TRY(valstat_run_chain(sp, h_cores, d_ws, d_col_perm, s, &ops));
+  const ChainProduct& q = sp.reduced;
+  const bool min = op == 1;
+  const dim3 flat(grid1d(out_numel)), threads(256);
+  AxisArgs args{d_row_out, d_col_out, d_row_idx, d_col_idx, d_values, (unsigned long long*)d_index, out_numel};
+  if constexpr (sizeof(T) == 4) {
+    if (index) {  // one pass, the packed keys in d_index
+      args.keys = d_index;
+      hipLaunchKernelGGL(axisext_fill_kernel<unsigned long long>, flat, threads, 0, s, (unsigned long long*)d_index, out_numel, 0ull);
+      NDMPS_LAUNCH_CHECK();
+      NDMPS_TRY(min ? (axisext_product<T, AxisEpi<T, true, kAxisPacked>>(q, ops, args, s))
+                    : (axisext_product<T, AxisEpi<T, false, kAxisPacked>>(q, ops, args, s)));
+      hipLaunchKernelGGL(axisext_unpack_kernel, flat, threads, 0, s, (unsigned long long*)d_index, (float*)d_values, out_numel, min);
+      NDMPS_LAUNCH_CHECK();
+      return NDMPS_OK;
+    }
+  }
+  hipLaunchKernelGGL(axisext_fill_kernel<K>, flat, threads, 0, s, (K*)d_values, out_numel, (K)0);
+  NDMPS_LAUNCH_CHECK();
+  NDMPS_TRY(min ? (axisext_product<T, AxisEpi<T, true, kAxisKeys>>(q, ops, args, s))
+                : (axisext_product<T, AxisEpi<T, false, kAxisKeys>>(q, ops, args, s)));
+  if constexpr (sizeof(T) == 8) {
+    if (index) {  // the same product again: an element whose key is its cell's finished key offers its index
+      hipLaunchKernelGGL(axisext_fill_kernel<unsigned long long>, flat, threads, 0, s, (unsigned long long*)d_index, out_numel,
+                         (unsigned long long)INT64_MAX);
+      NDMPS_LAUNCH_CHECK();
+      NDMPS_TRY(min ? (axisext_product<T, AxisEpi<T, true, kAxisMatch>>(q, ops, args, s))
+                    : (axisext_product<T, AxisEpi<T, false, kAxisMatch>>(q, ops, args, s)));
+    }
+  }
+  hipLaunchKernelGGL(axisext_decode_kernel<T>, flat, threads, 0, s, (void*)d_values, (long long*)d_index, out_numel, min);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
+}
+
+// the global extreme and its flat C-order index (-1 and NaN for a volume of NaN only)
+template <typename T>
+int argext_run(int L, const int64_t* h_dims, const int64_t* h_bonds, const T* const* h_cores, int op,
+               const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
+               double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  typedef typename KeyOf<T>::type K;
+  NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds && h_value && h_flat_index, "bad argext argument");
+  NDMPS_REQUIRE(op == 0 || op == 1, "argext: op %d is neither 0 (max) nor 1 (min)", op);
+  const ChainStatsPlan sp = ndmps::chain_stats_plan(L, h_dims, h_bonds, sizeof(T), 0);
+  const ErrorTables tables{d_row_off, d_row_off, d_col_off, d_col_perm, n_cols};  // no original: the row table stands in
+  NDMPS_TRY(valstat_check(sp, h_dims, h_bonds, h_cores, d_ws, ws_bytes, &tables));
+  hipStream_t s = (hipStream_t)stream;
+  Operands ops;
+  NDMPS_TRY(valstat_run_chain(sp, h_cores, d_ws, d_col_perm, s, &ops));
+  const ChainProduct& q = sp.reduced;
+  static_assert(sizeof(ArgRec) <= ndmps::kValstatRecordBytes, "a place fits a record slot");
+  ArgRec* partials = (ArgRec*)((char*)d_ws + sp.off_partials);
+  ArgRec* result = (ArgRec*)((char*)d_ws + sp.off_result);
+  const ArgArgs args{partials, d_row_off, d_col_off};
+  NDMPS_TRY(op == 1 ? (axisext_product<T, ArgEpi<T, true>>(q, ops, args, s))
+                    : (axisext_product<T, ArgEpi<T, false>>(q, ops, args, s)));
+  hipLaunchKernelGGL(argext_fold_kernel, dim3(1), dim3(64), 0, s, partials, valstat_grid(q), result);
+  NDMPS_LAUNCH_CHECK();
+  ArgRec host;
+  NDMPS_CHECK_HIP(hipMemcpyAsync(&host, result, sizeof(ArgRec), hipMemcpyDeviceToHost, s));
+  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+  *h_value = (double)ext_value<T>((K)host.key, op == 1);
+  *h_flat_index = host.key ? (int64_t)host.at : -1;
+  return NDMPS_OK;
+}
+
 }  // namespace
+
+extern "C" int ndmps_axisext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores, int op,
+                                 const int64_t* d_row_out, const int64_t* d_col_out, const int32_t* d_col_perm,
+                                 int64_t n_cols, const int32_t* d_row_idx, const int32_t* d_col_idx, int64_t out_numel,
+                                 float* d_values, int64_t* d_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  return axisext_run<float>(L, h_dims, h_bonds, h_cores, op, d_row_out, d_col_out, d_col_perm, n_cols, d_row_idx, d_col_idx,
+                            out_numel, d_values, d_index, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_axisext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
+                                 const int64_t* d_row_out, const int64_t* d_col_out, const int32_t* d_col_perm,
+                                 int64_t n_cols, const int32_t* d_row_idx, const int32_t* d_col_idx, int64_t out_numel,
+                                 double* d_values, int64_t* d_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream) {
+  return axisext_run<double>(L, h_dims, h_bonds, h_cores, op, d_row_out, d_col_out, d_col_perm, n_cols, d_row_idx, d_col_idx,
+                             out_numel, d_values, d_index, d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_argext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores, int op,
+                                const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                                int64_t n_cols, double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes,
+                                ndmps_stream_t stream) {
+  return argext_run<float>(L, h_dims, h_bonds, h_cores, op, d_row_off, d_col_off, d_col_perm, n_cols, h_value, h_flat_index,
+                           d_ws, ws_bytes, stream);
+}
+extern "C" int ndmps_argext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
+                                const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                                int64_t n_cols, double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes,
+                                ndmps_stream_t stream) {
+  return argext_run<double>(L, h_dims, h_bonds, h_cores, op, d_row_off, d_col_off, d_col_perm, n_cols, h_value, h_flat_index,
+                            d_ws, ws_bytes, stream);
+}
 
 extern "C" int64_t ndmps_valstat_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes,
                                                  int64_t n_bins) {

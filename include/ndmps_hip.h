@@ -629,6 +629,36 @@ int ndmps_valstat_error_f64(int L, const int64_t* h_dims, const int64_t* h_bonds
                             const double* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
                             const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts, void* d_ws,
                             int64_t ws_bytes, ndmps_stream_t stream);
+/* ---- Extremes along axes and the place of the global extreme, from the cores (csrc/valstat.hip, core/axisext.py).
+ * The same chain contraction and the same workspace as the value statistics (ndmps_valstat_workspace_bytes with
+ * n_bins = 0); the last product's epilogue turns every voxel into an unsigned key whose integer order is the order of
+ * the values and combines the keys of one output cell with integer atomic maxima, so the same inputs give the same
+ * bits.  NaN voxels take no part.  op: 0 max, 1 min.  Every argument check returns before the first launch.
+ *
+ * axisext: the projected array has out_numel cells; element (r, c) of the last product belongs to cell
+ * d_row_out[r] + d_col_out[c] (an offset outside [0, out_numel) updates nothing) and has the coordinate
+ * d_row_idx[r] + d_col_idx[c] along the reduced axis.  The column tables are in the order d_col_perm (site-order
+ * column of the c-th table entry), which must make columns of equal d_col_out adjacent; n_cols as for the error
+ * entry.  d_values (device, out_numel elements) receives the extremes, NaN for a cell nothing reached.  d_row_idx,
+ * d_col_idx and d_index (device, out_numel int64) are given together or all NULL: d_index receives the smallest
+ * coordinate at which the extreme sits, -1 where d_values is NaN.  The call returns without synchronising.
+ * argext: the tables of ndmps_plan_split_offsets as the error entry takes them; *h_value receives the extreme of the
+ * whole volume and *h_flat_index the smallest C-order index it sits at (NaN and -1 for a volume of NaN only).
+ * Returns with the stream synchronised. */
+int ndmps_axisext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores, int op,
+                      const int64_t* d_row_out, const int64_t* d_col_out, const int32_t* d_col_perm, int64_t n_cols,
+                      const int32_t* d_row_idx, const int32_t* d_col_idx, int64_t out_numel, float* d_values,
+                      int64_t* d_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_axisext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
+                      const int64_t* d_row_out, const int64_t* d_col_out, const int32_t* d_col_perm, int64_t n_cols,
+                      const int32_t* d_row_idx, const int32_t* d_col_idx, int64_t out_numel, double* d_values,
+                      int64_t* d_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_argext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores, int op,
+                     const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
+                     double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_argext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
+                     const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
+                     double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */
