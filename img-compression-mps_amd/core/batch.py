@@ -43,7 +43,8 @@ def conv_to_mps(tensor_list: Sequence, mode: str = "DCT", norm: bool = False, ma
     import torch
 
     from .. import _lib
-    from .ndmps import NDMPS, _plan_for
+    from .ndmps import NDMPS
+    from .plan import _plan_for
 
     _lib.require_device()  # the product never computes on the CPU: the same loud failure as from_tensor
     tensor_list = list(tensor_list)

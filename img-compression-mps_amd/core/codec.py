@@ -165,7 +165,8 @@ def loads(data: bytes, device=None):
 
     from .. import _lib
     from .mps import DeviceMPS
-    from .ndmps import NDMPS, _plan_for
+    from .ndmps import NDMPS
+    from .plan import _plan_for
 
     header, off = _header(data)
     shape, name, bonds, dims = _checked_layout(header)

@@ -20,7 +20,6 @@ reference is fp64 end to end (ndmps.py:56).
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import gzip
 import io
@@ -39,194 +38,14 @@ from . import axisop as _ax
 from . import hadamard as _hd
 from . import lincomb as _lc
 from . import oncore as _oc
+from . import pool as _pool
+from . import readout as _ro
+from . import region as _region
 from . import series as _se
 from . import sumsketch as _ss
 from . import wgram as _wg
-from .mps import DeviceMPS
-
-_PLAN_CACHE = {}
-_DCT_CACHE = {}
-
-
-class StageTimer:
-    """Optional per-stage device timing with HIP events on the stream the kernels run on
-    (bench.py installs one with ``set_stage_timer``; ``None`` = no events recorded)."""
-
-    def __init__(self):
-        self.spans = []
-
-    @contextlib.contextmanager
-    def span(self, name):
-        torch = _torch()
-        start = torch.cuda.Event(enable_timing=True)
-        stop = torch.cuda.Event(enable_timing=True)
-        start.record()
-        try:
-            yield
-        finally:
-            stop.record()
-            self.spans.append((name, start, stop))
-
-    def totals_ms(self):
-        """{stage: (total ms, count)}; synchronises the device."""
-        _torch().cuda.synchronize()
-        out = {}
-        for name, a, b in self.spans:
-            t, c = out.get(name, (0.0, 0))
-            out[name] = (t + a.elapsed_time(b), c + 1)
-        return out
-
-    def reset(self):
-        self.spans = []
-
-
-_TIMER = None
-
-
-def set_stage_timer(timer):
-    global _TIMER
-    _TIMER = timer
-
-
-def _span(name):
-    return _TIMER.span(name) if _TIMER is not None else contextlib.nullcontext()
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-class _Plan:
-    """Permutation plan (device offset tables) for one tensor shape.  ``factor_arr`` (L, ndim): an explicit factor
-    array whose columns multiply to the shape (the coarse chains of core/pool.py); ``get_factorlist(shape)`` if None."""
-
-    def __init__(self, shape, reverse_sites=False, factor_arr=None):
-        lib = _lib.load()
-        self.shape = tuple(int(s) for s in shape)
-        if factor_arr is None:
-            self.factor_arr, _ = _core.get_factorlist(self.shape)
-        else:
-            self.factor_arr = np.array(factor_arr, dtype=np.int64)
-        self.qubit_size = np.prod(self.factor_arr, axis=1)
-        handle = C.c_void_p()
-        fa = np.ascontiguousarray(self.factor_arr, dtype=np.int64)
-        # reverse_sites: destination = the site-order tensor with its axes reversed (the mirrored chain a
-        # left-to-right sweep is run on); qubit_size stays in the reference's order
-        create = lib.ndmps_plan_create_reversed if reverse_sites else lib.ndmps_plan_create
-        _lib.check(create(
-            C.byref(handle), len(self.shape), _lib.i64_array(self.shape), fa.shape[0],
-            fa.ctypes.data_as(_lib.p_i64)))
-        self.handle = handle
-        self.numel = int(np.prod(self.shape, dtype=np.int64))
-
-        self._split = {}
-        self._split_vec4 = {}
-        self._sorted_rows = {}
-
-    def split_tables(self, n_cols, device):
-        """Device tables for the site-order tensor viewed as (numel / n_cols) x n_cols: element (r, c) sits at
-        row_off[r] + col_off[c] of the C-order volume (offsets are additive over sites).  Returned with the
-        columns in memory order: (row_off, col_off ascending, col_perm = site-order column of the c-th smallest
-        offset), int64 / int64 / int32.  Built once per (n_cols, device), with synchronous uploads."""
-        torch = _torch()
-        key = (int(n_cols), str(device))
-        with _CACHE_LOCK:
-            if key not in self._split:
-                rows = self.numel // int(n_cols)
-                row_off = np.empty(rows, dtype=np.int64)
-                col_off = np.empty(int(n_cols), dtype=np.int64)
-                _lib.check(_lib.load().ndmps_plan_split_offsets(
-                    self.handle, int(n_cols), row_off.ctypes.data_as(_lib.p_i64), col_off.ctypes.data_as(_lib.p_i64)))
-                perm = np.argsort(col_off, kind="stable")
-                col_sorted = np.ascontiguousarray(col_off[perm])
-                # 16-byte gathers are possible when the sorted offsets come in aligned runs of four
-                quads = col_sorted.reshape(-1, 4) if n_cols % 4 == 0 else None
-                self._split_vec4[key] = bool(
-                    quads is not None and np.all(quads[:, 0] % 4 == 0) and np.all(np.diff(quads, axis=1) == 1)
-                    and np.all(row_off % 4 == 0))
-                self._split[key] = (torch.from_numpy(row_off).to(device),
-                                    torch.from_numpy(col_sorted).to(device),
-                                    torch.from_numpy(perm.astype(np.int32)).to(device))
-                torch.cuda.synchronize(device)
-            return self._split[key]
-
-    def sorted_rows(self, n_cols, device):
-        """(split_tables' row offsets in ascending order, int64; the row each of them belongs to, int32): the order in
-        which the Gram kernels and the streamed projection of the fused sweep visit the rows, so that they read the
-        volume front to back.  Built once per (n_cols, device)."""
-        torch = _torch()
-        key = (int(n_cols), str(device))
-        row_off = self.split_tables(n_cols, device)[0]
-        with _CACHE_LOCK:
-            if key not in self._sorted_rows:
-                srt, order = torch.sort(row_off)
-                self._sorted_rows[key] = (srt.contiguous(), order.to(torch.int32).contiguous())
-                torch.cuda.synchronize(device)
-            return self._sorted_rows[key]
-
-    def gather_tables(self, n_cols, device):
-        """split_tables when the volume can be read through them 16 bytes at a time, else None."""
-        tables = self.split_tables(n_cols, device)
-        return tables if self._split_vec4[(int(n_cols), str(device))] else None
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ndmps_plan_destroy(self.handle)
-        except Exception:
-            pass
-
-
-_CACHE_LOCK = threading.Lock()  # concurrent groups (core/batch.py) reach the caches from several host threads
-
-
-def _plan_for(shape, device_index, reverse_sites=False, factor_arr=None):
-    key = (tuple(int(s) for s in shape), device_index) + (("reversed",) if reverse_sites else ())
-    if factor_arr is not None:
-        fa = np.asarray(factor_arr, dtype=np.int64)
-        key = key + (("factors", fa.shape, tuple(int(v) for v in fa.ravel())),)
-    with _CACHE_LOCK:
-        if key not in _PLAN_CACHE:
-            _PLAN_CACHE[key] = _Plan(shape, reverse_sites, factor_arr)  # plan tables are uploaded with synchronous copies
-        return _PLAN_CACHE[key]
-
-
-def _ptr_array(tensors):
-    """Host array of the tensors' device pointers (the pointer tables of the library's group-wide launches)."""
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _dct_basis(n, device, f64=False):
-    torch = _torch()
-    key = (int(n), str(device), bool(f64))
-    with _CACHE_LOCK:
-        if key not in _DCT_CACHE:
-            basis = torch.empty((n, n), dtype=torch.float64 if f64 else torch.float32, device=device)
-            fill = _lib.load().ndmps_dct_basis_f64 if f64 else _lib.load().ndmps_dct_basis_f32
-            _lib.check(fill(basis.data_ptr(), n, _lib.stream_ptr()))
-            # the basis is shared by every stream from now on: finish the fill before publishing it
-            torch.cuda.current_stream().synchronize()
-            _DCT_CACHE[key] = basis
-        return _DCT_CACHE[key]
-
-
-_POOL_DCT_CACHE = {}
-
-
-def _pooled_dct_basis(n, block, op, device, f64=False):
-    """(n / block, n) basis that turns DCT coefficient rows into block means (sums) of the voxels: y W^T."""
-    torch = _torch()
-    key = (int(n), int(block), op, str(device), bool(f64))
-    with _CACHE_LOCK:
-        if key not in _POOL_DCT_CACHE:
-            basis = torch.empty((n // block, n), dtype=torch.float64 if f64 else torch.float32, device=device)
-            fill = _lib.load().ndmps_pool_dct_basis_f64 if f64 else _lib.load().ndmps_pool_dct_basis_f32
-            _lib.check(fill(basis.data_ptr(), n, block, 1.0 / block if op == "mean" else 1.0, _lib.stream_ptr()))
-            torch.cuda.current_stream().synchronize()  # shared by every stream from now on
-            _POOL_DCT_CACHE[key] = basis
-        return _POOL_DCT_CACHE[key]
+from .mps import DeviceMPS, _torch
+from .plan import StageTimer, _dct_basis, _plan_for, _ptr_array, _span, set_stage_timer  # noqa: F401  (re-exported)
 
 
 # ------------------------------------------------------------------------------------------------ on the cores
@@ -257,70 +76,10 @@ def _work_is_f64(objs, dtype=None):
     return _lc.work_is_f64([_lc.dtype_code(o.mps.dtype) for o in objs], dtype)
 
 
-# ------------------------------------------------------------------------------------------------ decode tail
-def _fused_tail_columns(dtype, dims):
-    """Columns of the chain's last product that scatter straight into the C-order volume (the fused decode of fp32
-    cores); 0: contract the chain in site order and permute afterwards."""
-    if dtype != _torch().float32 or os.environ.get("NDMPS_NO_FUSED_DECODE"):  # the switch: A/B timing
-        return 0
-    return int(_lib.load().ndmps_chain_tail_columns(len(dims), _lib.i64_array(dims)))
-
-
-def _decode_chain(chain, plan, shape):
-    """One chain (a DeviceMPS whose site-order tensor ``plan`` maps onto ``shape``) as a C-order device tensor in the
-    chain's own type.  Runs on the chain's device, which the caller has made current."""
-    torch = _torch()
-    device = chain.device
-    n_tail = _fused_tail_columns(chain.dtype, chain.dims)
-    if n_tail > 0:
-        # fp32: the inverse permutation rides on the last product of the chain; no site-order tensor
-        out = torch.empty(shape, dtype=torch.float32, device=device)
-        with _span("chain"):
-            chain.to_volume(out, n_tail, plan.split_tables(n_tail, device))
-    else:
-        with _span("chain"):
-            dense = chain.to_dense()
-        out = torch.empty(shape, dtype=dense.dtype, device=device)
-        with _span("decode_permute"):
-            _lib.check(_lib.load().ndmps_decode_permute(plan.handle, dense.data_ptr(), out.data_ptr(),
-                                                        dense.element_size(), _lib.stream_ptr()))
-    return out
-
-
-def _decode_chains_f32(batch, L, cdims, bonds, cores, n_tail, plan, shape, device, dct):
-    """``batch`` fp32 chains of one shape -- ``cores``: batch x L device pointers, ``bonds``: batch x (L + 1) -- as one
-    (batch,) + shape tensor, inverse DCT included (``dct``): ONE library call issues the launches of every volume.
-    Buffers are taken in the order reconstruction, chain workspace, IDCT output, and the workspace is held until the
-    IDCT is enqueued (the encode path depends on that order: the allocator note in NDMPS._encode_group)."""
-    torch = _torch()
-    lib = _lib.load()
-    row_off, col_off, col_perm = plan.split_tables(n_tail, device)
-    out = torch.empty((batch,) + tuple(shape), dtype=torch.float32, device=device)
-    ws_bytes = int(lib.ndmps_chain_batched_workspace_bytes(batch, L, cdims, bonds))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    base, step = out.data_ptr(), plan.numel * 4
-    outs = (C.c_void_p * batch)(*[base + b * step for b in range(batch)])
-    with _span("chain"):
-        _lib.check(lib.ndmps_chain_contract_scatter_batched_f32(
-            batch, L, cdims, bonds, cores, outs, row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(),
-            n_tail, ws.data_ptr(), ws_bytes, _lib.stream_ptr()))
-    # the volumes sit back to back in `out`: their rows are the rows of one tall matrix, one launch
-    return _idct_last(out, shape[-1]) if dct else out
-
-
-def _idct_last(x, n):
-    """Inverse DCT along rows of length ``n`` that lie contiguous in ``x`` (a volume's last axis, the volumes of a
-    group back to back, the rows of a region), as a new tensor of x's shape: float64 for float64, float32 otherwise."""
-    torch = _torch()
-    lib = _lib.load()
-    f64 = x.dtype == torch.float64
-    if not f64:
-        x = x.to(torch.float32)  # the IDCT kernel is fp32 (bf16 storage: upcast copy)
-    rec = torch.empty_like(x)
-    idct = lib.ndmps_idct_last_f64 if f64 else lib.ndmps_idct_last_f32
-    _lib.check(idct(x.data_ptr(), rec.data_ptr(), x.numel() // n, n, _dct_basis(n, x.device, f64).data_ptr(),
-                    _lib.stream_ptr()))
-    return rec
+def _bf16_std(objs):
+    """``readout.as_result``'s flag: every object has bf16 cores and the mode is Std (as_torch then gives bf16)."""
+    bf16 = _torch().bfloat16
+    return objs[0].mps.dtype == bf16 and objs[0].mode == "Std" and all(o.mps.dtype == bf16 for o in objs)
 
 
 class _GroupState:
@@ -580,14 +339,14 @@ class _SweptGroup:
         """``reconstruct=True``, where the batched fused decode serves: decode straight from the arena -- padded cores
         are valid cores of the cap bonds (zeros beyond the rank).  Otherwise ``finish()`` decodes from the objects."""
         batch, L, esize = self.batch, self.L, self.esize
-        n_tail = _fused_tail_columns(self.store, self.dims) if self.reconstruct and batch > 1 and not self.mirrored else 0
+        n_tail = _ro.fused_tail_columns(self.store, self.dims) if self.reconstruct and batch > 1 and not self.mirrored else 0
         if n_tail <= 0:
             return
         dec_bonds = _lib.i64_array([v for b in range(batch) for v in (self.caps if self.padded else self.bonds_np[b])])
         dec_cores = (C.c_void_p * (batch * L))(*[self.arena_base + (b * self.core_total + self.offs[i]) * esize
                                                  for b in range(batch) for i in range(L)])
-        out = _decode_chains_f32(batch, L, self.cdims, dec_bonds, dec_cores, n_tail, self.ref_plan, self.shape, self.device,
-                                 self.mode == "DCT")
+        out = _ro.decode_chains_f32(batch, L, self.cdims, dec_bonds, dec_cores, n_tail, self.ref_plan, self.shape,
+                                    self.device, self.mode == "DCT")
         self.recs = list(out.unbind(0))
 
     def mark_enqueued(self):
@@ -1441,12 +1200,10 @@ class NDMPS:
         shape = self._require_shape()
         device = self.mps.device
         with _torch().cuda.device(device):
-            out = _decode_chain(self.mps, _plan_for(shape, device.index or 0), shape)
-            if self.mode == "DCT":
-                out = _idct_last(out, shape[-1])
-            elif self.mode != "Std":
-                return None  # ndmps.py:150-153: unknown modes fall through
-        return self._result(out, as_torch, dtype)
+            out = _ro.decode(self.mps, _plan_for(shape, device.index or 0), shape, self.mode == "DCT")
+        if self.mode not in ("Std", "DCT"):
+            return None  # ndmps.py:150-153: unknown modes fall through
+        return _ro.as_result(out, as_torch, dtype, _bf16_std([self]))
 
     @staticmethod
     def to_tensors(objs, as_torch: bool = False):
@@ -1466,68 +1223,12 @@ class NDMPS:
                          and o.mps.device == first.mps.device and o.mps.dims == first.mps.dims for o in objs))
         if not group:
             return [o.to_tensor(as_torch=as_torch) for o in objs]
-        lib = _lib.load()
-        device, shape, batch = first.mps.device, tuple(first._shape), len(objs)
-        dims_list = first.mps.dims
-        n_tail = _fused_tail_columns(first.mps.dtype, dims_list)
+        device, shape = first.mps.device, tuple(first._shape)
         with torch.cuda.device(device):
-            plan = _plan_for(shape, device.index or 0)
-            if n_tail > 0:
-                L = len(dims_list)
-                bonds = _lib.i64_array([k for o in objs for k in o.mps.bonds])
-                cores = _ptr_array([c for o in objs for c in o.mps.cores])
-                out = _decode_chains_f32(batch, L, _lib.i64_array(dims_list), bonds, cores, n_tail, plan, shape, device,
-                                         first.mode == "DCT")
-            else:
-                # bf16 / fp64 cores (or the fused decode switched off): a chain per volume, then the inverse permutation and
-                # the IDCT of the whole group in one launch each (to_tensor's steps, ndmps.py:140-153)
-                with _span("chain"):
-                    denses = [o.mps.to_dense() for o in objs]
-                out = torch.empty((batch,) + shape, dtype=denses[0].dtype, device=device)
-                with _span("decode_permute"):
-                    _lib.check(lib.ndmps_decode_permute_many(plan.handle, batch, _ptr_array(denses),
-                                                             _ptr_array(list(out.unbind(0))), denses[0].element_size(),
-                                                             _lib.stream_ptr()))
-                del denses
-                if first.mode == "DCT":
-                    out = _idct_last(out, shape[-1])
-        return [o._result(r, as_torch, None) for o, r in zip(objs, out.unbind(0))]
+            out = _ro.decode_many([o.mps for o in objs], _plan_for(shape, device.index or 0), shape, first.mode == "DCT")
+        return [_ro.as_result(r, as_torch, None, _bf16_std([o])) for o, r in zip(objs, out.unbind(0))]
 
     # ---------------------------------------------------------------- region decode
-    def _region_values(self, plan):
-        """The plan's output elements (core/region.py) contracted from the cores (ndmps_region_contract_*): a flat
-        device tensor, fp64 for fp64 cores, fp32 otherwise (bf16 cores are upcast as for the overlap)."""
-        torch = _torch()
-        lib = _lib.load()
-        mps = self.mps
-        f64 = mps.dtype == torch.float64
-        keep, ptrs = mps._ptrs_as(torch.float64 if f64 else torch.float32)
-        L = len(mps.cores)
-        dims, bonds = _lib.i64_array(mps.dims), _lib.i64_array(mps.bonds)
-        nodes, tiles = _lib.i64_array(plan.nodes), _lib.i64_array(plan.n_tiles)
-        device = mps.device
-        tables = torch.from_numpy(plan.tables()).to(device)  # every table in one upload
-        ws_bytes = int(lib.ndmps_region_workspace_bytes(L, bonds, nodes, 8 if f64 else 4))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
-        out = torch.empty(plan.n_out, dtype=torch.float64 if f64 else torch.float32, device=device)
-        fn = lib.ndmps_region_contract_f64 if f64 else lib.ndmps_region_contract_f32
-        with _span("region"):
-            _lib.check(fn(L, dims, bonds, ptrs, nodes, tiles, tables.data_ptr(), tables.numel(), plan.n_out,
-                          out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()))
-        del keep
-        return out
-
-    def _result(self, res, as_torch, dtype):
-        """A decoded device tensor as what the caller asked for -- to_tensor's result types: float64 for fp64 cores, float32 otherwise; as_torch with bf16 cores in Std mode
-        gives bf16 like to_tensor's bf16 chain (the NumPy result keeps the fp32 contraction unrounded)."""
-        torch = _torch()
-        if as_torch:
-            if dtype is None and self.mps.dtype == torch.bfloat16 and self.mode == "Std":
-                dtype = torch.bfloat16
-            return res if dtype is None else res.to(dtype)
-        arr = (res if res.dtype == torch.float64 else res.to(torch.float32)).cpu().numpy()
-        return arr[()] if arr.ndim == 0 else arr  # all-int keys give a NumPy scalar, as to_tensor()[i, j, k]
-
     def decode_region(self, key, as_torch: bool = False, dtype=None):
         """
         ``to_tensor(as_torch, dtype)[key]`` without decoding the whole volume.
@@ -1544,27 +1245,8 @@ class NDMPS:
         DCT mode stores the last axis in the DCT domain: the last axis is decoded in full for every selected row,
         transformed back, then indexed.  A region restricted only on the last axis costs a full decode there.
         """
-        torch = _torch()
         shape = tuple(self._require_shape())
-        from . import region as _region
-
-        idx, keep = _region.normalize_key(key, shape)
-        if self.mode not in ("Std", "DCT"):
-            return None
-        out_shape = [i.size for i, k in zip(idx, keep) if k]
-        device = self.mps.device
-        with torch.cuda.device(device):
-            f64 = self.mps.dtype == torch.float64
-            if any(i.size == 0 for i in idx):
-                res = torch.empty(out_shape, dtype=torch.float64 if f64 else torch.float32, device=device)
-            elif self.mode == "Std":
-                res = self._region_values(_region.plan_outer(shape, idx)).view(out_shape)
-            else:
-                n = shape[-1]
-                rows = self._region_values(_region.plan_outer(shape, idx[:-1] + [np.arange(n, dtype=np.int64)]))
-                rec = _idct_last(rows, n).view(-1, n)
-                res = rec.index_select(1, torch.from_numpy(idx[-1]).to(device)).reshape(out_shape)
-        return self._result(res, as_torch, dtype)
+        return NDMPS._region(_ro.region_outer, [self], (), shape, _region.normalize_key(key, shape), as_torch, dtype)
 
     def values_at(self, coords, as_torch: bool = False, dtype=None):
         """
@@ -1572,28 +1254,9 @@ class NDMPS:
         decoding the whole volume: an (N,) result of to_tensor's dtype.  Errors as ``decode_region``; in DCT mode every
         distinct row of the last axis that the points touch is decoded in full.
         """
-        torch = _torch()
         shape = tuple(self._require_shape())
-        from . import region as _region
-
         pts = _region.normalize_points(coords, shape)
-        if self.mode not in ("Std", "DCT"):
-            return None
-        N = pts.shape[1]
-        device = self.mps.device
-        with torch.cuda.device(device):
-            f64 = self.mps.dtype == torch.float64
-            if N == 0:
-                res = torch.empty(0, dtype=torch.float64 if f64 else torch.float32, device=device)
-            elif self.mode == "Std":
-                res = self._region_values(_region.plan_points(shape, pts))
-            else:
-                n = shape[-1]
-                full, sel = _region.full_rows_of_points(shape, pts)
-                rows = self._region_values(_region.plan_points(shape, full))
-                rec = _idct_last(rows, n).view(-1, n)
-                res = rec.reshape(-1).index_select(0, torch.from_numpy(sel).to(device))
-        return self._result(res, as_torch, dtype)
+        return NDMPS._region(_ro.region_points, [self], (), shape, (pts,), as_torch, dtype)
 
     # ------------------------------------------------- region decode of a series (one plan, one upload)
     @staticmethod
@@ -1608,55 +1271,19 @@ class NDMPS:
         return objs
 
     @staticmethod
-    def _series_is_f64(objs):
-        torch = _torch()
-        return any(o.mps.dtype == torch.float64 for o in objs)
-
-    @staticmethod
-    def _region_series_values(objs, plan):
-        """``plan``'s output elements of every frame (ndmps_region_series_contract_*): a (T, n_out) device tensor, fp64
-        if any frame has fp64 cores (the others are widened exactly), fp32 otherwise (bf16 cores upcast as in
-        ``_region_values``).  The tables are uploaded once; each chunk of frames (``region.plan_series``) uploads its
-        records -- core pointers, then bonds -- in one copy and issues L launches."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import region as _region
-
-        f64 = NDMPS._series_is_f64(objs)
-        work = torch.float64 if f64 else torch.float32
-        elem = 8 if f64 else 4
-        first = objs[0].mps
-        T, L, device = len(objs), len(first.cores), first.device
-        keep = [[c if c.dtype == work else c.to(work) for c in o.mps.cores] for o in objs]
-        ptrs = np.array([[c.data_ptr() for c in frame] for frame in keep], dtype=np.int64).reshape(T, L)
-        bonds = np.array([[1] + [c.shape[2] for c in frame] for frame in keep], dtype=np.int64).reshape(T, L + 1)
-        layout = _region.plan_series(bonds, plan, elem)
-        dims = _lib.i64_array(first.dims)
-        nodes, tiles = _lib.i64_array(plan.nodes), _lib.i64_array(plan.n_tiles)
-        tables = torch.from_numpy(plan.tables()).to(device)  # every table in one upload, once for the series
-        ws = torch.empty(max(layout.ws_bytes, 1), dtype=torch.uint8, device=device)
-        out = torch.empty((T, plan.n_out), dtype=work, device=device)
-        fn = lib.ndmps_region_series_contract_f64 if f64 else lib.ndmps_region_series_contract_f32
-        with _span("region_series"):
-            for a, b in layout.chunks:
-                records = torch.from_numpy(np.concatenate([ptrs[a:b].ravel(), bonds[a:b].ravel()])).to(device)
-                h_bonds = np.ascontiguousarray(bonds[a:b])
-                _lib.check(fn(b - a, L, dims, h_bonds.ctypes.data_as(_lib.p_i64), nodes, tiles, tables.data_ptr(),
-                              tables.numel(), records.data_ptr(), plan.n_out, out[a].data_ptr(), ws.data_ptr(),
-                              layout.ws_bytes, _lib.stream_ptr()))
-        del keep
-        return out
-
-    @staticmethod
-    def _series_result(objs, res, as_torch, dtype):
-        """``_result`` for a (T, ...) tensor of a series: float64 if the call contracted in fp64, float32 otherwise;
-        as_torch gives bf16 only when every frame is bf16 and the mode is Std."""
-        torch = _torch()
-        if as_torch:
-            if dtype is None and objs[0].mode == "Std" and all(o.mps.dtype == torch.bfloat16 for o in objs):
-                dtype = torch.bfloat16
-            return res if dtype is None else res.to(dtype)
-        return (res if res.dtype == torch.float64 else res.to(torch.float32)).cpu().numpy()
+    def _region(skeleton, objs, lead, shape, selection, as_torch, dtype):
+        """``skeleton`` (``readout.region_outer`` / ``region_points``) of the normalised ``selection``, converted for the
+        caller: over the chain of one object through the single entry (``lead = ()``), or over a series' chains
+        (``lead = (T,)``).  None for modes other than Std / DCT, before anything runs on the device."""
+        if objs[0].mode not in ("Std", "DCT"):
+            return None
+        first, chains = objs[0].mps, [o.mps for o in objs]
+        contract = ((lambda rplan: _ro.region_series_values(chains, rplan)) if lead else
+                    (lambda rplan: _ro.region_values(first, rplan)))
+        with _torch().cuda.device(first.device):
+            res = skeleton(contract, lead, shape, *selection, objs[0].mode == "DCT", _ro.series_work_dtype(chains),
+                           first.device)
+        return _ro.as_result(res, as_torch, dtype, _bf16_std(objs))
 
     @staticmethod
     def decode_regions(objs, key, as_torch: bool = False, dtype=None):
@@ -1675,31 +1302,10 @@ class NDMPS:
         ``as_torch=True`` gives bf16 only when every frame is bf16 in Std mode.  An empty region gives an empty result
         without a launch; modes other than Std / DCT return None.  No counterpart in the reference.
         """
-        torch = _torch()
-        from . import region as _region
-
         objs = NDMPS._region_series_objs(objs)
-        first = objs[0]
-        shape = tuple(first._shape)
-        idx, keep = _region.normalize_key(key, shape)
-        if first.mode not in ("Std", "DCT"):
-            return None
-        T = len(objs)
-        out_shape = [T] + [i.size for i, k in zip(idx, keep) if k]
-        device = first.mps.device
-        with torch.cuda.device(device):
-            if any(i.size == 0 for i in idx):
-                res = torch.empty(out_shape, dtype=torch.float64 if NDMPS._series_is_f64(objs) else torch.float32,
-                                  device=device)
-            elif first.mode == "Std":
-                res = NDMPS._region_series_values(objs, _region.plan_outer(shape, idx)).view(out_shape)
-            else:
-                n = shape[-1]
-                rows = NDMPS._region_series_values(
-                    objs, _region.plan_outer(shape, idx[:-1] + [np.arange(n, dtype=np.int64)]))
-                rec = _idct_last(rows, n).view(T, -1, n)  # the rows of all frames lie back to back: one launch
-                res = rec.index_select(2, torch.from_numpy(idx[-1]).to(device)).reshape(out_shape)
-        return NDMPS._series_result(objs, res, as_torch, dtype)
+        shape = tuple(objs[0]._shape)
+        selection = _region.normalize_key(key, shape)
+        return NDMPS._region(_ro.region_outer, objs, (len(objs),), shape, selection, as_torch, dtype)
 
     @staticmethod
     def values_at_many(objs, coords, as_torch: bool = False, dtype=None):
@@ -1708,36 +1314,15 @@ class NDMPS:
         ``objs[t].values_at(coords, as_torch, dtype)``, bit for bit.  Arguments, errors, mixed storage and result types
         as ``decode_regions``; ``N == 0`` gives a (T, 0) result without a launch.
         """
-        torch = _torch()
-        from . import region as _region
-
         objs = NDMPS._region_series_objs(objs)
-        first = objs[0]
-        shape = tuple(first._shape)
+        shape = tuple(objs[0]._shape)
         pts = _region.normalize_points(coords, shape)
-        if first.mode not in ("Std", "DCT"):
-            return None
-        T, N = len(objs), pts.shape[1]
-        device = first.mps.device
-        with torch.cuda.device(device):
-            if N == 0:
-                res = torch.empty((T, 0), dtype=torch.float64 if NDMPS._series_is_f64(objs) else torch.float32,
-                                  device=device)
-            elif first.mode == "Std":
-                res = NDMPS._region_series_values(objs, _region.plan_points(shape, pts))
-            else:
-                full, sel = _region.full_rows_of_points(shape, pts)
-                rows = NDMPS._region_series_values(objs, _region.plan_points(shape, full))
-                rec = _idct_last(rows, shape[-1]).view(T, -1)
-                res = rec.index_select(1, torch.from_numpy(sel).to(device))
-        return NDMPS._series_result(objs, res, as_torch, dtype)
+        return NDMPS._region(_ro.region_points, objs, (len(objs),), shape, (pts,), as_torch, dtype)
 
     # ------------------------------------------------------------ block-averaged decode
     def _pool_levels(self, levels):
         """(factor_arr, normalised levels) for this object's shape; ValueError without one."""
         shape = self._require_shape()
-        from . import pool as _pool
-
         fa = _core.get_factorlist(tuple(shape))[0]
         return fa, _pool.normalize_levels(levels, len(shape), fa.shape[0])
 
@@ -1745,96 +1330,8 @@ class NDMPS:
         """Block size ``B_a = prod(factor_arr[L - levels[a]:, a])`` per axis: the voxels that ``downsample(levels)``
         averages into one value.  ``levels`` is an int in ``[0, L]`` (L = number of sites) or one int per axis.
         Host only."""
-        from . import pool as _pool
-
         fa, lev = self._pool_levels(levels)
         return _pool.block_shape(fa, lev)
-
-    @staticmethod
-    def _rank_safe(cores):
-        """The chain with every bond at most the product of the site dims on either side of it (what ndmps_chain_*
-        require; a reduced chain can have wider bonds): the two sites around a wider bond are contracted into one.
-        The site-order tensor is unchanged."""
-        torch = _torch()
-        lib = _lib.load()
-        dims = [int(c.shape[1]) for c in cores]
-        numel = int(np.prod(dims, dtype=np.int64))
-        out, left = [cores[0]], dims[0]
-        for c in cores[1:]:
-            chi = int(c.shape[0])
-            if chi > left or chi > numel // left:
-                prev = out.pop()
-                m, n = int(prev.shape[0]) * int(prev.shape[1]), int(c.shape[1]) * int(c.shape[2])
-                merged = torch.empty((int(prev.shape[0]), int(prev.shape[1]) * int(c.shape[1]), int(c.shape[2])),
-                                     dtype=c.dtype, device=c.device)
-                gemm = lib.ndmps_dgemm if c.dtype == torch.float64 else lib.ndmps_sgemm
-                _lib.check(gemm(0, 0, m, n, chi, prev.data_ptr(), chi, c.data_ptr(), n, merged.data_ptr(), n,
-                                _lib.stream_ptr()))
-                out.append(merged)
-            else:
-                out.append(c)
-            left *= int(c.shape[1])
-        return out
-
-    def _pooled(self, fa, lev, op):
-        """The volume reduced over the blocks of ``lev`` (core/pool.py) as a device tensor of the plan's out_shape,
-        fp64 for fp64 cores, fp32 otherwise (bf16 cores are reduced and contracted in fp32)."""
-        torch = _torch()
-        lib = _lib.load()
-        from . import pool as _pool
-
-        mps = self.mps
-        plan = _pool.PoolPlan(fa, lev, op, dct=self.mode == "DCT")
-        device = mps.device
-        f64 = mps.dtype == torch.float64
-        work = torch.float64 if f64 else torch.float32
-        code = 2 if f64 else 1 if mps.dtype == torch.bfloat16 else 0
-        L, Lk = plan.L, plan.L_keep
-        bonds = mps.bonds
-        outs = []
-        for l in range(max(Lk, 1)):
-            if Lk == 0:
-                outs.append(torch.empty((1, 1, 1), dtype=work, device=device))
-            elif l == Lk - 1 and Lk < L:
-                outs.append(torch.empty((bonds[l], int(plan.dprime[l]), 1), dtype=work, device=device))
-            elif plan.passthrough[l] and mps.cores[l].dtype == work:
-                outs.append(None)  # nothing reduced: the core itself
-            else:
-                outs.append(torch.empty((bonds[l], int(plan.dprime[l]), bonds[l + 1]), dtype=work, device=device))
-        ptrs = mps._core_ptrs()
-        with torch.cuda.device(device):
-            stream = _lib.stream_ptr()
-            offs = torch.from_numpy(plan.offsets).to(device)  # every site's offsets in one upload
-            ws_bytes = int(lib.ndmps_pool_workspace_bytes(L, _lib.i64_array(bonds))) if Lk < L else 0
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
-            out_ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() if o is not None else None for o in outs])
-            with _span("pool"):
-                _lib.check(lib.ndmps_pool_cores(code, L, _lib.i64_array(mps.dims), _lib.i64_array(bonds), ptrs, Lk,
-                                                _lib.i64_array(plan.sites.ravel()), _lib.f64_array(plan.weight),
-                                                offs.data_ptr(), offs.numel(), out_ptrs, ws.data_ptr(), ws_bytes,
-                                                stream))
-            if Lk == 0:
-                res = outs[0].view(plan.coarse_shape)
-            else:
-                cores = self._rank_safe([o if o is not None else mps.cores[l] for l, o in enumerate(outs)])
-                cplan = _plan_for(plan.coarse_shape, device.index or 0, factor_arr=plan.out_factor)
-                res = _decode_chain(DeviceMPS(cores, _trusted=True), cplan, plan.coarse_shape)
-            if self.mode == "DCT" and lev[-1] < L:
-                n = int(self._shape[-1])
-                rows = res.numel() // n
-                if plan.dct_pool > 1:
-                    # coefficient rows times the pooled basis (n / B, n): about 1 / prod_{a < last} B_a of the
-                    # full decode's transform
-                    nb = n // plan.dct_pool
-                    basis = _pooled_dct_basis(n, plan.dct_pool, op, device, f64)
-                    rec = torch.empty(rows * nb, dtype=work, device=device)
-                    gemm = lib.ndmps_dgemm if f64 else lib.ndmps_sgemm
-                    _lib.check(gemm(0, 1, rows, nb, n, res.data_ptr(), n, basis.data_ptr(), n, rec.data_ptr(), nb,
-                                    stream))
-                    res = rec
-                else:
-                    res = _idct_last(res, n)
-        return res.view(plan.out_shape)
 
     def downsample(self, levels=1, op: str = "mean", as_torch: bool = False, dtype=None):
         """
@@ -1859,12 +1356,10 @@ class NDMPS:
         if self.mode not in ("Std", "DCT"):
             return None
         with _torch().cuda.device(self.mps.device):
-            res = self._pooled(fa, lev, op)
-        return self._result(res, as_torch, dtype)
+            res = _ro.pooled(self.mps, self._shape, fa, lev, op, self.mode == "DCT")
+        return _ro.as_result(res, as_torch, dtype, _bf16_std([self]))
 
     def _axis_reduce(self, axis, keepdims, op, as_torch, dtype):
-        from . import pool as _pool
-
         shape = self._require_shape()
         ndim = len(shape)
         axes = _pool.normalize_axes(axis, ndim)
@@ -1873,10 +1368,10 @@ class NDMPS:
         if self.mode not in ("Std", "DCT"):
             return None
         with _torch().cuda.device(self.mps.device):
-            res = self._pooled(fa, lev, op)
+            res = _ro.pooled(self.mps, self._shape, fa, lev, op, self.mode == "DCT")
             if not keepdims:
                 res = res.reshape([n for a, n in enumerate(res.shape) if a not in axes])
-        return self._result(res, as_torch, dtype)
+        return _ro.as_result(res, as_torch, dtype, _bf16_std([self]))
 
     def sum(self, axis=None, keepdims: bool = False, as_torch: bool = False, dtype=None):
         """``to_tensor().sum(axis=axis, keepdims=keepdims)`` without decoding the whole volume (``downsample`` with

@@ -17,6 +17,7 @@ from . import lincomb as _lc
 from . import series as _se
 from . import wgram as _wg
 from .mps import DeviceMPS, _torch
+from .plan import _span
 
 
 def chain_list_args(chains):
@@ -55,8 +56,6 @@ def _launch(total, ws_bytes, dtype, device, span, launch):
     ``launch(arena, ws)`` runs under the stage span, and the workspace is released before anything else is allocated
     (what is carved out of the arena keeps it alive).  Returns (arena, the launch's return code)."""
     torch = _torch()
-    from .ndmps import _span
-
     with torch.cuda.device(device):
         arena = torch.empty(max(total, 1), dtype=dtype, device=device)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)

@@ -19,7 +19,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from imgcompressionmps_amd import NDMPS, _lib  # noqa: E402
-from imgcompressionmps_amd.core import region  # noqa: E402
+from imgcompressionmps_amd.core import readout, region  # noqa: E402
 from oracle import chain_bound as cb  # noqa: E402
 from oracle import chain_cases as cc  # noqa: E402
 from oracle import index_map as im  # noqa: E402
@@ -305,7 +305,8 @@ def test_empty_selections_and_errors_launch_nothing(monkeypatch):
     def _no_launch(*a, **k):
         raise AssertionError("the series contraction was reached")
 
-    monkeypatch.setattr(NDMPS, "_region_series_values", staticmethod(_no_launch))
+    monkeypatch.setattr(readout, "region_series_values", _no_launch)
+    monkeypatch.setattr(readout, "region_values", _no_launch)
     got = NDMPS.decode_regions(objs, (slice(3, 3),))
     assert got.shape == (3, 0, 45, 20) and got.dtype == np.float32
     got = NDMPS.decode_regions(objs, (2, Ellipsis, slice(7, 7)), as_torch=True)
