@@ -141,6 +141,12 @@ SIGNATURES = {
                                     vp]),
     "ndmps_argext_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
     "ndmps_argext_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
+    "ndmps_labelstat_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, i64, i64]),
+    "ndmps_labelstat_scales": (C.c_int, [C.c_double, i64, p_int, p_int]),
+    "ndmps_labelstat_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, vp, vp, vp,
+                                      vp, vp, i64, vp]),
+    "ndmps_labelstat_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, vp, vp, vp,
+                                      vp, vp, i64, vp]),
     "ndmps_chain_contract_scatter_batched_f32": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, vp, vp,
                                                            i64, vp, i64, vp]),
     "ndmps_gemm_batched_max": (C.c_int, []),

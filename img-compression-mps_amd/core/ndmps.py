@@ -1501,6 +1501,35 @@ class NDMPS:
         chain, plan = self._valstat_chain("psnr_to", with_plan=True)
         return _vs.psnr_from(_vs.error_to(chain, plan, x))
 
+    def label_stats(self, labels, n_labels=None) -> dict:
+        """Statistics of ``to_tensor()`` under each label of an atlas or segmentation, without decoding: ``labels`` is an
+        integer NumPy array or device tensor of the object's shape, and the result a dict of arrays of length
+        ``n_labels`` (None: ``max(labels) + 1``; at most 4096): ``count``, ``n_nan``, ``sum``, ``sumsq``, ``min``,
+        ``max``, ``mean``, ``std`` (population; NaN for a label without a voxel), and the scalars ``outside`` (voxels
+        whose label is negative or not below ``n_labels``), ``s`` and ``s2`` (core/labelstat.py).  The sums are 64-bit
+        fixed-point integers scaled by ``2**-s`` and ``2**-s2``, added in integer arithmetic: the same inputs give
+        the same bits.  NaN voxels are counted per label and left out of the rest.
+
+        Raises TypeError for labels that are not integers, ValueError for another shape, labels beyond int32, more
+        than 4096 labels, an infinite voxel, and what ``value_stats`` refuses."""
+        from . import labelstat as _ls
+
+        chain, plan = self._valstat_chain("label_stats", with_plan=True)
+        return _ls.label_stats(chain, plan, labels, n_labels)
+
+    @staticmethod
+    def label_stats_many(objs, labels, n_labels=None) -> dict:
+        """``label_stats`` of every frame of a series against one atlas: the same dict with arrays of shape
+        ``(T, n_labels)``, so ``["mean"]`` holds the parcel time courses; ``outside``, ``s`` and ``s2`` have length T.
+        The atlas and the offset tables go to the device once and one workspace serves every frame; row t equals
+        ``objs[t].label_stats(labels, n_labels)`` bit for bit.  Bonds and storage types (fp32, fp64) may differ between
+        frames.  The list checks are those of ``decode_regions``; otherwise the refusals of ``label_stats``."""
+        from . import labelstat as _ls
+
+        objs = NDMPS._region_series_objs(objs)
+        pairs = [o._valstat_chain("label_stats_many", with_plan=True) for o in objs]
+        return _ls.label_stats_many([chain for chain, _ in pairs], pairs[0][1], labels, n_labels)
+
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):
         """Integer-truncate each MPS tensor to the given unsigned dtype (ndmps.py:182-207)."""

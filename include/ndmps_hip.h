@@ -659,6 +659,41 @@ int ndmps_argext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const
 int ndmps_argext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
                      const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
                      double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+/* ---- Statistics per label of an atlas, from the cores (csrc/valstat.hip, core/labelstat.py).
+ * The chain contraction of the value statistics; the last product runs twice over the same operands.  The first run is
+ * the moments pass, whose minimum and maximum fix on the device the two power-of-two scales s and s2; the second hands
+ * every voxel v with its label d_labels[d_row_off[r] + d_col_off[c]] (the tables of the error entry; an offset outside
+ * the volume reads nothing) to an epilogue that adds llrint(v 2^s) and llrint(v v 2^s2) into 64-bit integers and takes
+ * integer maxima of order-preserving keys for min and max.  Only integers are added atomically: the same inputs give
+ * the same bits.  NaN voxels are counted per label and take no part in the rest; an infinite voxel is refused with
+ * NDMPS_EINVAL ("label statistics need finite voxels").  A label outside [0, n_labels) is counted in `outside`.
+ *
+ * The scales (ndmps_labelstat_scales, host arithmetic only; the device applies the same function): with
+ * nb = ceil(log2 numel) and maxabs < 2^e by frexp, s = 61 - nb - e; s2 = 61 - nb - e2 with e2 from the fp64 product
+ * maxabs * maxabs (2 e where that product leaves the fp64 range); both clamped to [-1000, 1000]; maxabs = 0 gives
+ * s = s2 = 0.  Then numel * |v| 2^s <= 2^61: no sum can overflow.
+ *
+ * Workspace: ndmps_labelstat_workspace_bytes = ndmps_valstat_workspace_bytes(..., n_bins = 0) + the label table,
+ * 8 * (6 * n_labels + 5) bytes rounded up to 256: six 64-bit slots per label (sum, sum of squares, count, NaN count,
+ * min key, max key), then outside, overflow, s, s2 and the non-finite flag.  0 for bad arguments.
+ * d_labels: device, C order of the volume, label_elem_bytes 1 (uint8), 2 (int16) or 4 (int32).  1 <= n_labels <= 4096;
+ * more than 1024 labels run the labelled pass once per window of 1024.
+ * Results (HOST): h_sums[n_labels] the integer sums (value = h_sums[l] 2^-s), h_sumsq[n_labels] (2^-s2),
+ * h_counts[2 n_labels] the non-NaN counts then the NaN counts, h_minmax[2 n_labels] the minima then the maxima as
+ * doubles (NaN where the count is 0), h_info = {outside, s, s2, voxels}.  Returns with the stream synchronised. */
+int64_t ndmps_labelstat_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes,
+                                        int64_t n_labels);
+int ndmps_labelstat_scales(double maxabs, int64_t numel, int* s, int* s2);
+int ndmps_labelstat_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                        const void* d_labels, int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off,
+                        const int32_t* d_col_perm, int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq,
+                        int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws, int64_t ws_bytes,
+                        ndmps_stream_t stream);
+int ndmps_labelstat_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                        const void* d_labels, int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off,
+                        const int32_t* d_col_perm, int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq,
+                        int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws, int64_t ws_bytes,
+                        ndmps_stream_t stream);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */
