@@ -1530,6 +1530,61 @@ class NDMPS:
         pairs = [o._valstat_chain("label_stats_many", with_plan=True) for o in objs]
         return _ls.label_stats_many([chain for chain, _ in pairs], pairs[0][1], labels, n_labels)
 
+    # ---------------------------------------------------- statistics of two objects on the cores (core/pairstat.py)
+    def _pairstat_chains(self, other, what):
+        """The two chains of a pair call, or the error that refuses it: TypeError for a non-NDMPS, ValueError naming what
+        differs (shape, mode, qubit_size -- the factor array --, device, site dims) and what ``value_stats`` refuses."""
+        if not isinstance(other, NDMPS):
+            raise TypeError(f"{what} takes NDMPS objects, not {type(other).__name__}")
+        chains = self._valstat_chain(what), other._valstat_chain(what)
+        _check_compatible([self, other])
+        return chains
+
+    def pair_stats(self, other) -> dict:
+        """Moments of this volume (a) and ``other`` (b) over the voxels where neither is NaN, from the cores of both,
+        with neither volume decoded (csrc/pairstat.hip): ``count`` (those voxels), ``n_nan`` (the others), ``sum_a,
+        sum_b, sumsq_a, sumsq_b, sum_ab, sse`` (``sum (a - b)^2``), ``max_abs_diff, min_a, max_a, min_b, max_b``, and
+        derived on the host in fp64 ``mean_a, mean_b, cov, pearson, mse, rel_frob`` (``||a - b|| / ||b||``).  Sums are
+        fp64; the same objects give the same bits.  One fp32 and one fp64 object make the call fp64.
+
+        Raises TypeError for a non-NDMPS, ValueError for objects that differ in shape, mode, qubit_size, device or site
+        dims, and what ``value_stats`` refuses of either (DCT mode, bf16 cores, an unknown shape)."""
+        from . import pairstat as _ps
+
+        return _ps.pair_stats(*self._pairstat_chains(other, "pair_stats"))
+
+    def joint_histogram(self, other, bins=64, range=None, outliers: bool = False):
+        """``numpy.histogram2d(self.to_tensor().ravel(), other.to_tensor().ravel(), bins, range)`` from the cores of
+        both: ``(counts int64 (bins_a, bins_b), edges_a, edges_b)``.  ``bins`` is an int, a pair of ints or a pair of
+        explicit ascending edge arrays (at most 1024 bins per axis and 16384 cells); ``range`` is None or
+        ``((lo_a, hi_a), (lo_b, hi_b))``, and with None an int takes that object's own min and max from a moments
+        pass.  The edges of an axis are those ``histogram`` builds from the same arguments, and the row and column sums
+        are the single histograms bit for bit.  ``outliers=True`` adds ``(outside, n_nan)``: the voxels with either
+        value out of range, and those with either value NaN; cells and outliers always sum to the voxel count.
+        Errors as ``pair_stats`` and ``histogram``."""
+        from . import pairstat as _ps
+
+        return _ps.joint_histogram(*self._pairstat_chains(other, "joint_histogram"), bins, range, outliers)
+
+    def mutual_information(self, other, bins=64, range=None, normalized: bool = False) -> float:
+        """Mutual information of the two volumes in nats, from ``joint_histogram(other, bins, range)`` on the host in
+        fp64: ``sum p_ij ln(p_ij / (p_i. p_.j))`` over the non-empty cells, p over the binned voxels -- the similarity
+        measure of multi-modal registration, where the cross-correlation of ``inner`` fails.  ``normalized=True``
+        returns ``(H(a) + H(b)) / H(a, b)`` (Studholme), 1.0 when ``H(a, b) == 0``."""
+        from . import pairstat as _ps
+
+        return _ps.mutual_information(*self._pairstat_chains(other, "mutual_information"), bins, range, normalized)
+
+    @staticmethod
+    def mutual_information_many(objs, ref, bins=64, range=None, normalized: bool = False):
+        """``objs[t].mutual_information(ref, ...)`` for every frame as a ``(T,)`` fp64 array.  The edges of ``ref`` are
+        fixed once; entry t equals the single call with those edges bit for bit.  A loop of single calls."""
+        from . import pairstat as _ps
+
+        objs = _checked_list(objs, "mutual_information_many takes")
+        pairs = [o._pairstat_chains(ref, "mutual_information_many") for o in objs]
+        return _ps.mutual_information_many([a for a, _ in pairs], pairs[0][1] if pairs else None, bins, range, normalized)
+
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):
         """Integer-truncate each MPS tensor to the given unsigned dtype (ndmps.py:182-207)."""

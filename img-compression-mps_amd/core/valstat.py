@@ -118,10 +118,10 @@ def bin_counts(chain, edges):
     return counts[:n_bins].copy(), int(counts[n_bins]), int(counts[n_bins + 1]), int(counts[n_bins + 2])
 
 
-def histogram(chain, bins=256, range=None, outliers=False):
-    """``numpy.histogram(volume, bins, range)``: (counts int64, edges in the element type), and with ``outliers`` also
-    ``(n_below, n_above, n_nan)``.  ``bins``: an int (equal-width bins over ``range``, or over the volume's min and
-    max, which costs a moments pass first) or an explicit ascending edge array."""
+def edges_for(chain, bins, range=None):
+    """The checked edge table of a histogram call on ``chain``, in its element type.  ``bins``: an int (equal-width bins
+    over ``range``, or over the volume's min and max, which costs a moments pass first) or an explicit ascending edge
+    array.  ``histogram`` and the axes of ``pairstat.joint_histogram`` both come here: equal arguments, equal edges."""
     np_type, _ = _element(chain)
     if isinstance(bins, (int, np.integer)) and not isinstance(bins, bool):
         if bins < 1:
@@ -140,9 +140,15 @@ def histogram(chain, bins=256, range=None, outliers=False):
             raise ValueError("histogram edges must be ascending: range[0] > range[1]")
         if lo == hi:
             lo, hi = lo - 0.5, hi + 0.5  # numpy's rule for an empty range
-        edges = check_edges(np.linspace(lo, hi, int(bins) + 1), np_type)
-    else:
-        edges = check_edges(bins, np_type)
+        return check_edges(np.linspace(lo, hi, int(bins) + 1), np_type)
+    return check_edges(bins, np_type)
+
+
+def histogram(chain, bins=256, range=None, outliers=False):
+    """``numpy.histogram(volume, bins, range)``: (counts int64, edges in the element type), and with ``outliers`` also
+    ``(n_below, n_above, n_nan)``.  ``bins``: an int (equal-width bins over ``range``, or over the volume's min and
+    max, which costs a moments pass first) or an explicit ascending edge array."""
+    edges = edges_for(chain, bins, range)
     counts, below, above, nan = bin_counts(chain, edges)
     return (counts, edges, (below, above, nan)) if outliers else (counts, edges)
 

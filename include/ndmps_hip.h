@@ -694,6 +694,52 @@ int ndmps_labelstat_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, co
                         const int32_t* d_col_perm, int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq,
                         int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws, int64_t ws_bytes,
                         ndmps_stream_t stream);
+/* ---- Statistics of TWO chains of one shape and one factorisation, from the cores (csrc/pairstat.hip,
+ * core/pairstat.py): the pair moments and the joint histogram of the two volumes, with neither written.  Both chains
+ * have the site dims h_dims, so their last products have the same rows and columns (the split depends on the dims
+ * alone) and differ only in k; one kernel forms both accumulator tiles of a tile index and hands the voxel pairs to
+ * a reducing epilogue.  A voxel's value is computed exactly as the ndmps_valstat_* entries compute it.  fp32 or fp64,
+ * both chains in the same element type.  Every call checks its arguments before its first launch, reads its result
+ * back once and returns with the stream synchronised; the same inputs give the same bits.
+ *
+ * Workspace: ndmps_pairstat_workspace_bytes(L, dims, bonds_a, bonds_b, elem_bytes (4 or 8), bins_a, bins_b) =
+ * ndmps_valstat_workspace_bytes(.., bonds_a, .., 0) + the same for bonds_b + the pair scratch (512 partial records of
+ * 128 bytes, 256 bytes for the result, and for a histogram bins_a * bins_b + 2 counters and the two edge tables, each
+ * rounded up to 256 bytes); bins 0, 0 serves the moments call; 0 for bad arguments.  An axis takes at most 1024
+ * bins, the two together at most 16384 cells.  d_ws must be 256-byte aligned.
+ *
+ * ndmps_pairstat_plan_query: the plan, for tests and tools (host arithmetic only).  elem: 0 fp32, 2 fp64.  h_out
+ * receives NDMPS_PAIRSTAT_PLAN_SLOTS values:
+ *    0 m   1 n   2 k of a   3 k of b (the last products)   4 workspace bytes of a   5 of b
+ *    6 offset of b's workspace   7 of the partial records   8 of the result   9 of the counters   10 of the edges of a
+ *    11 of the edges of b   12 pair scratch bytes   13 workspace bytes
+ *
+ * moments: h_stats = {sum a, sum b, sum a^2, sum b^2, sum a b, sum (a - b)^2, min a, max a, min b, max b,
+ * max |a - b|} over the voxels where neither value is NaN, h_counts = {their number, the voxels where either is}.
+ * histogram: h_edges_a[bins_a + 1] / h_edges_b[bins_b + 1] are HOST arrays in the element type, ascending, no NaN;
+ * cell (ia, ib) takes edges_a[ia] <= a < edges_a[ia + 1] and edges_b[ib] <= b < edges_b[ib + 1], the last bin of
+ * either axis closed on the right (numpy.histogram2d).  h_counts[bins_a * bins_b + 2] (HOST): the cells row-major
+ * (ia * bins_b + ib), then the voxels with either value out of range, then the voxels with either value NaN (NaN
+ * wins over out of range). */
+#define NDMPS_PAIRSTAT_PLAN_SLOTS 14
+int64_t ndmps_pairstat_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                                       int64_t elem_bytes, int64_t bins_a, int64_t bins_b);
+int ndmps_pairstat_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                              int64_t bins_a, int64_t bins_b, int64_t* h_out);
+int ndmps_pairstat_moments_f32(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                               const float* const* h_cores_a, const float* const* h_cores_b, double* h_stats,
+                               int64_t* h_counts, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_pairstat_moments_f64(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                               const double* const* h_cores_a, const double* const* h_cores_b, double* h_stats,
+                               int64_t* h_counts, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_pairstat_histogram_f32(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                                 const float* const* h_cores_a, const float* const* h_cores_b, const float* h_edges_a,
+                                 int bins_a, const float* h_edges_b, int bins_b, int64_t* h_counts, void* d_ws,
+                                 int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_pairstat_histogram_f64(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                                 const double* const* h_cores_a, const double* const* h_cores_b, const double* h_edges_a,
+                                 int bins_a, const double* h_edges_b, int bins_b, int64_t* h_counts, void* d_ws,
+                                 int64_t ws_bytes, ndmps_stream_t stream);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */
