@@ -1,6 +1,6 @@
 """Extremes of the volume a chain decodes to along axes, and where they sit, from the cores.
 
-The host side of the two extreme epilogues of csrc/valstat.hip (``ndmps_axisext_*``, ``ndmps_argext_*``): the chain is
+The host side of the two extreme epilogues of csrc/axisext.hip (``ndmps_axisext_*``, ``ndmps_argext_*``): the chain is
 contracted as ``to_tensor`` contracts it, and the last product -- the only one that touches N elements -- sends every
 voxel to the cell of the projected array it belongs to instead of storing it.  ``NDMPS.amax`` / ``amin`` / ``argmax`` /
 ``argmin`` are thin methods over ``extreme`` and ``arg_extreme`` below.
@@ -33,10 +33,7 @@ _TABLES = weakref.WeakKeyDictionary()  # plan -> {(axes, n_cols, device): Tables
 _LOCK = threading.Lock()
 
 
-def _torch():
-    import torch
-
-    return torch
+_torch = _vs._torch
 
 
 class Tables:
@@ -110,10 +107,10 @@ def extreme(chain, plan, axes, op, index=False):
         call = _vs._Call(chain)
         values = torch.empty(t.out_shape, dtype=chain.dtype, device=device)
         where = torch.empty(t.out_shape, dtype=torch.int64, device=device) if index else None
-        entry = getattr(call.lib, f"ndmps_axisext_{call.suffix}")
-        _lib.check(entry(*call.head(), OPS[op], t.row_out.data_ptr(), t.col_out.data_ptr(), t.col_perm.data_ptr(), n_cols,
-                         _ptr(t.row_idx) if index else None, _ptr(t.col_idx) if index else None, t.out_numel,
-                         values.data_ptr(), _ptr(where), *call.tail()))
+        _lib.check(call.entry("axisext")(*call.head(), OPS[op], t.row_out.data_ptr(), t.col_out.data_ptr(),
+                                         t.col_perm.data_ptr(), n_cols, _ptr(t.row_idx) if index else None,
+                                         _ptr(t.col_idx) if index else None, t.out_numel, values.data_ptr(), _ptr(where),
+                                         *call.tail()))
     return values, where
 
 
@@ -127,9 +124,8 @@ def arg_extreme(chain, plan, op):
         row_off, col_off, col_perm = plan.split_tables(n_cols, device)
         call = _vs._Call(chain)
         value, flat = C.c_double(), C.c_int64()
-        entry = getattr(call.lib, f"ndmps_argext_{call.suffix}")
-        _lib.check(entry(*call.head(), OPS[op], row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(), n_cols,
-                         C.byref(value), C.byref(flat), *call.tail()))
+        _lib.check(call.entry("argext")(*call.head(), OPS[op], row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(),
+                                        n_cols, C.byref(value), C.byref(flat), *call.tail()))
     return float(value.value), int(flat.value)
 
 

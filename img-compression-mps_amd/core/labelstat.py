@@ -1,7 +1,7 @@
 """Statistics per label of an atlas or segmentation, from the cores: count, mean, std, min and max of the voxels under
 each label, and the (T, n_labels) table of a series (the parcel time courses), without decoding a volume.
 
-The host side of the label epilogue of csrc/valstat.hip.  The chain is contracted as ``value_stats`` contracts it; its
+The host side of the label epilogue of csrc/labelstat.hip.  The chain is contracted as ``value_stats`` contracts it; its
 last product runs as the moments pass, whose extremes fix two power-of-two scales on the device, and then again over
 the same operands with the label of every voxel read through the offset tables of the fused decode
 (``_Plan.split_tables``), as ``error_to`` reads its original.  Sums are 64-bit fixed-point integers, ``sum = int 2^-s``
@@ -26,10 +26,7 @@ _AS_THEY_ARE = ("bool", "uint8", "int16", "int32")
 _I32 = (-2 ** 31, 2 ** 31 - 1)
 
 
-def _torch():
-    import torch
-
-    return torch
+_torch = _vs._torch
 
 
 def _type_name(labels):
@@ -97,16 +94,14 @@ def scales(maxabs, numel):
 
 def _one(chain, lab, tables, n_cols, n_labels, ws):
     """The library call on one chain: the raw result arrays."""
-    _, suffix = _vs._element(chain)
+    call = _vs._Call(chain, ws=ws)
     row_off, col_off, col_perm = tables
     n = n_labels
     sums, sumsq = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint64)
     counts, minmax, info = np.zeros(2 * n, dtype=np.int64), np.zeros(2 * n, dtype=np.float64), np.zeros(4, dtype=np.int64)
-    entry = getattr(_lib.load(), f"ndmps_labelstat_{suffix}")
-    _lib.check(entry(chain.L, _lib.i64_array(chain.dims), _lib.i64_array(chain.bonds), chain._core_ptrs(), lab.data_ptr(),
-                     lab.element_size(), row_off.data_ptr(), col_off.data_ptr(), col_perm.data_ptr(), n_cols, n,
-                     sums.ctypes.data, sumsq.ctypes.data, counts.ctypes.data, minmax.ctypes.data, info.ctypes.data,
-                     ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+    _lib.check(call.entry("labelstat")(*call.head(), lab.data_ptr(), lab.element_size(), row_off.data_ptr(),
+                                       col_off.data_ptr(), col_perm.data_ptr(), n_cols, n, sums.ctypes.data, sumsq.ctypes.data,
+                                       counts.ctypes.data, minmax.ctypes.data, info.ctypes.data, *call.tail()))
     return sums, sumsq, counts, minmax, info
 
 

@@ -1400,7 +1400,7 @@ class NDMPS:
     def value_stats(self) -> dict:
         """``count, min, max, sum, sumsq, n_nan`` of ``to_tensor()`` and the derived ``mean``, ``std`` (population) and
         ``norm`` (Frobenius), without decoding the volume: the chain's last product reduces its tiles instead of storing
-        them (csrc/valstat.hip), so only the small left and tail buffers of the decode are written.  Sums are fp64; NaN
+        them (csrc/valstat.hip, csrc/valstat_device.h), so only the small left and tail buffers of the decode are written.  Sums are fp64; NaN
         voxels are counted in ``n_nan`` and left out of everything else; the same object gives the same bits.  The
         voxel values are those of ``to_tensor()`` within the forward error bound of the chain, not bit for bit.
 

@@ -26,10 +26,7 @@ MAX_AXIS_BINS = 1024
 MAX_CELLS = 16384
 
 
-def _torch():
-    import torch
-
-    return torch
+_torch = _vs._torch
 
 
 def pair_chains(a, b):
@@ -70,25 +67,12 @@ def workspace_bytes(a, b, bins_a=0, bins_b=0):
                                                           int(bins_a), int(bins_b)))
 
 
-class _Call:
-    """The arguments both entries share, and a workspace with room for ``bins_a`` x ``bins_b`` cells."""
-
-    def __init__(self, a, b, bins_a=0, bins_b=0):
-        torch = _torch()
-        self.np_type, self.suffix = _vs._element(a)
-        self.lib = _lib.load()
-        self.head = (a.L, _lib.i64_array(a.dims), _lib.i64_array(a.bonds), _lib.i64_array(b.bonds), a._core_ptrs(),
-                     b._core_ptrs())
-        self.ws_bytes = workspace_bytes(a, b, bins_a, bins_b)
-        if self.ws_bytes <= 0:
-            raise ValueError("the library refuses the workspace query of this pair")
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=a.device)
-
-    def entry(self, name):
-        return getattr(self.lib, f"ndmps_pairstat_{name}_{self.suffix}")
-
-    def tail(self):
-        return self.ws.data_ptr(), self.ws_bytes, _lib.stream_ptr()
+def _call(a, b, bins_a=0, bins_b=0):
+    """``valstat._Call`` of both chains with a workspace with room for ``bins_a`` x ``bins_b`` cells."""
+    ws_bytes = workspace_bytes(a, b, bins_a, bins_b)
+    if ws_bytes <= 0:
+        raise ValueError("the library refuses the workspace query of this pair")
+    return _vs._Call(a, other=b, ws_bytes=ws_bytes)
 
 
 RAW_FIELDS = ("sum_a", "sum_b", "sumsq_a", "sumsq_b", "sum_ab", "sse", "min_a", "max_a", "min_b", "max_b", "max_abs_diff")
@@ -97,10 +81,10 @@ RAW_FIELDS = ("sum_a", "sum_b", "sumsq_a", "sumsq_b", "sum_ab", "sse", "min_a", 
 def pair_moments(a, b):
     """The raw record of a checked pair: ``count`` (voxels where neither value is NaN), ``n_nan`` (the others) and
     RAW_FIELDS over the counted voxels."""
-    call = _Call(a, b)
+    call = _call(a, b)
     stats, counts = (C.c_double * 11)(), (C.c_int64 * 2)()
     with _torch().cuda.device(a.device):
-        _lib.check(call.entry("moments")(*call.head, stats, counts, *call.tail()))
+        _lib.check(call.entry("pairstat_moments")(*call.head(), stats, counts, *call.tail()))
     out = dict(count=int(counts[0]), n_nan=int(counts[1]))
     out.update(zip(RAW_FIELDS, (float(v) for v in stats)))
     return out
@@ -168,11 +152,12 @@ def joint_counts(a, b, ea, eb):
     """(counts int64 (bins_a, bins_b), outside, n_nan) of a checked pair for checked edges."""
     na, nb = int(ea.size - 1), int(eb.size - 1)
     check_bins(na, nb)
-    call = _Call(a, b, na, nb)
+    call = _call(a, b, na, nb)
     counts = np.zeros(na * nb + 2, dtype=np.int64)
     with _torch().cuda.device(a.device):
-        _lib.check(call.entry("histogram")(*call.head, ea.ctypes.data_as(C.c_void_p), na, eb.ctypes.data_as(C.c_void_p), nb,
-                                           counts.ctypes.data_as(_lib.p_i64), *call.tail()))
+        _lib.check(call.entry("pairstat_histogram")(*call.head(), ea.ctypes.data_as(C.c_void_p), na,
+                                                    eb.ctypes.data_as(C.c_void_p), nb, counts.ctypes.data_as(_lib.p_i64),
+                                                    *call.tail()))
     return counts[:na * nb].reshape(na, nb).copy(), int(counts[na * nb]), int(counts[na * nb + 1])
 
 

@@ -44,23 +44,29 @@ def workspace_bytes(chain, n_bins=0):
 
 
 class _Call:
-    """The arguments every entry shares, and a workspace with room for ``n_bins`` bins."""
+    """The arguments every entry of the statistics family shares (core/valstat.py, axisext.py, labelstat.py,
+    pairstat.py): one chain, or two of one shape (``other``: the pair entries), and the workspace -- the caller's
+    (``ws``), or a new one of ``ws_bytes`` bytes, or one with room for ``n_bins`` histogram bins."""
 
-    def __init__(self, chain, n_bins=0):
+    def __init__(self, chain, n_bins=0, other=None, ws=None, ws_bytes=None):
         torch = _torch()
         self.np_type, self.suffix = _element(chain)
         self.lib = _lib.load()
-        self.L = chain.L
-        self.dims, self.bonds = _lib.i64_array(chain.dims), _lib.i64_array(chain.bonds)
-        self.ptrs = chain._core_ptrs()
-        self.ws_bytes = workspace_bytes(chain, n_bins)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=chain.device)
+        chains = (chain,) if other is None else (chain, other)
+        self._head = (chain.L, _lib.i64_array(chain.dims), *[_lib.i64_array(c.bonds) for c in chains],
+                      *[c._core_ptrs() for c in chains])
+        if ws is None:
+            ws_bytes = workspace_bytes(chain, n_bins) if ws_bytes is None else ws_bytes
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=chain.device)
+        self.ws, self.ws_bytes = ws, ws.numel()
 
     def entry(self, name):
-        return getattr(self.lib, f"ndmps_valstat_{name}_{self.suffix}")
+        """``ndmps_<name>_f32`` or ``_f64``, by the chain's element type."""
+        return getattr(self.lib, f"ndmps_{name}_{self.suffix}")
 
     def head(self):
-        return self.L, self.dims, self.bonds, self.ptrs
+        """L, dims, the bonds of each chain, the core pointers of each chain."""
+        return self._head
 
     def tail(self):
         return self.ws.data_ptr(), self.ws_bytes, _lib.stream_ptr()
@@ -73,7 +79,7 @@ def moments(chain, clip=None):
     lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
     stats, counts = (C.c_double * 4)(), (C.c_int64 * 3)()
     with _torch().cuda.device(chain.device):
-        _lib.check(call.entry("moments")(*call.head(), lo, hi, stats, counts, *call.tail()))
+        _lib.check(call.entry("valstat_moments")(*call.head(), lo, hi, stats, counts, *call.tail()))
     return dict(count=int(counts[0]), n_nan=int(counts[1]), taken=int(counts[2]), min=float(stats[0]), max=float(stats[1]),
                 sum=float(stats[2]), sumsq=float(stats[3]))
 
@@ -113,8 +119,8 @@ def bin_counts(chain, edges):
     call = _Call(chain, n_bins)
     counts = np.zeros(n_bins + 3, dtype=np.int64)
     with _torch().cuda.device(chain.device):
-        _lib.check(call.entry("histogram")(*call.head(), edges.ctypes.data_as(C.c_void_p), n_bins,
-                                           counts.ctypes.data_as(_lib.p_i64), *call.tail()))
+        _lib.check(call.entry("valstat_histogram")(*call.head(), edges.ctypes.data_as(C.c_void_p), n_bins,
+                                                   counts.ctypes.data_as(_lib.p_i64), *call.tail()))
     return counts[:n_bins].copy(), int(counts[n_bins]), int(counts[n_bins + 1]), int(counts[n_bins + 2])
 
 
@@ -222,8 +228,8 @@ def error_to(chain, plan, x):
         row_off, col_off, col_perm = plan.split_tables(n_cols, device)
         call = _Call(chain)
         stats, counts = (C.c_double * 4)(), (C.c_int64 * 3)()
-        _lib.check(call.entry("error")(*call.head(), ref.data_ptr(), row_off.data_ptr(), col_off.data_ptr(),
-                                       col_perm.data_ptr(), n_cols, stats, counts, *call.tail()))
+        _lib.check(call.entry("valstat_error")(*call.head(), ref.data_ptr(), row_off.data_ptr(), col_off.data_ptr(),
+                                               col_perm.data_ptr(), n_cols, stats, counts, *call.tail()))
     n = int(counts[0]) - int(counts[1])
     sse, max_abs, ref_sumsq, ref_max = (float(v) for v in stats)
     return dict(sse=sse, mse=sse / n if n else math.nan, max_abs=max_abs, ref_sumsq=ref_sumsq, ref_max=ref_max,

@@ -20,14 +20,11 @@
 //               the LDS atomic a wavefront folds the lanes that share the first lane's cell into one add (the
 //               background of two medical volumes is one cell).
 //
-// A voxel's value is computed by the instruction sequence of valstat_product_kernel, in its k order with its zero
-// padding (pair_accumulate below is that kernel's k-loop), so the marginals of the joint histogram are the
-// single-chain histograms bit for bit.  Determinism as there: tile t goes to workgroup t mod grid, a fixed shuffle
-// tree, one partial record per workgroup folded in index order, and only integers are added atomically.
-#include <math.h>
-
+// A voxel's value is computed by the one text valstat_product_kernel computes it by (stat_tile_accumulate,
+// valstat_device.h: its k order, its zero padding), so the marginals of the joint histogram are the single-chain
+// histograms bit for bit.  Determinism as there: tile t goes to workgroup t mod grid, a fixed shuffle tree, one
+// partial record per workgroup folded in index order, and only integers are added atomically.
 #include <mutex>
-#include <type_traits>
 
 #include "common.h"
 #include "pairstat_plan.h"
@@ -43,60 +40,37 @@ struct PairRecord {
   double sum_a, sum_b, sumsq_a, sumsq_b, sum_ab, sse;
   double min_a, max_a, min_b, max_b, max_abs_diff;
   long long count, n_nan;  // voxels where neither value is NaN / where either is
+
+  __device__ __forceinline__ void clear() {
+    sum_a = sum_b = sumsq_a = sumsq_b = sum_ab = sse = 0.0;
+    min_a = min_b = INFINITY;
+    max_a = max_b = max_abs_diff = -INFINITY;
+    count = n_nan = 0;
+  }
+  __device__ __forceinline__ void fold(const PairRecord& b) {
+    sum_a += b.sum_a;
+    sum_b += b.sum_b;
+    sumsq_a += b.sumsq_a;
+    sumsq_b += b.sumsq_b;
+    sum_ab += b.sum_ab;
+    sse += b.sse;
+    min_a = fmin(min_a, b.min_a);
+    max_a = fmax(max_a, b.max_a);
+    min_b = fmin(min_b, b.min_b);
+    max_b = fmax(max_b, b.max_b);
+    max_abs_diff = fmax(max_abs_diff, b.max_abs_diff);
+    count += b.count;
+    n_nan += b.n_nan;
+  }
 };
 // a partial or the result in the workspace (ndmps::kPairstatRecordBytes): the thirteen fields and three spare slots
-struct PairSlot {
-  PairRecord r;
+struct PairSlot : PairRecord {
   long long unused[3];
 };
 static_assert(sizeof(PairSlot) == ndmps::kPairstatRecordBytes, "record layout");
 
-__device__ __forceinline__ void pair_clear(PairRecord& r) {
-  r.sum_a = r.sum_b = r.sumsq_a = r.sumsq_b = r.sum_ab = r.sse = 0.0;
-  r.min_a = r.min_b = INFINITY;
-  r.max_a = r.max_b = r.max_abs_diff = -INFINITY;
-  r.count = r.n_nan = 0;
-}
-__device__ __forceinline__ void pair_fold(PairRecord& a, const PairRecord& b) {
-  a.sum_a += b.sum_a;
-  a.sum_b += b.sum_b;
-  a.sumsq_a += b.sumsq_a;
-  a.sumsq_b += b.sumsq_b;
-  a.sum_ab += b.sum_ab;
-  a.sse += b.sse;
-  a.min_a = fmin(a.min_a, b.min_a);
-  a.max_a = fmax(a.max_a, b.max_a);
-  a.min_b = fmin(a.min_b, b.min_b);
-  a.max_b = fmax(a.max_b, b.max_b);
-  a.max_abs_diff = fmax(a.max_abs_diff, b.max_abs_diff);
-  a.count += b.count;
-  a.n_nan += b.n_nan;
-}
-// lane 0 <- the wavefront's 64 records, folded by a fixed tree
-__device__ __forceinline__ void pair_fold_wave(PairRecord& r) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    PairRecord o;
-    o.sum_a = __shfl_down(r.sum_a, off);
-    o.sum_b = __shfl_down(r.sum_b, off);
-    o.sumsq_a = __shfl_down(r.sumsq_a, off);
-    o.sumsq_b = __shfl_down(r.sumsq_b, off);
-    o.sum_ab = __shfl_down(r.sum_ab, off);
-    o.sse = __shfl_down(r.sse, off);
-    o.min_a = __shfl_down(r.min_a, off);
-    o.max_a = __shfl_down(r.max_a, off);
-    o.min_b = __shfl_down(r.min_b, off);
-    o.max_b = __shfl_down(r.max_b, off);
-    o.max_abs_diff = __shfl_down(r.max_abs_diff, off);
-    o.count = __shfl_down(r.count, off);
-    o.n_nan = __shfl_down(r.n_nan, off);
-    pair_fold(r, o);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ epilogues
-// take() is called by every lane of every wavefront the same number of times (valid == false: a padded row or
-// column, which contributes nothing); finish() once per workgroup.
+// (the contract: valstat_device.h; take() gets the pair of one accumulator slot)
 struct PairRecordArgs {
   PairSlot* partials;  // one per workgroup
 };
@@ -105,7 +79,7 @@ template <typename T>
 struct PairRecordEpi {
   typedef PairRecordArgs Args;
   PairRecord r;
-  __device__ __forceinline__ void begin(const Args&) { pair_clear(r); }
+  __device__ __forceinline__ void begin(const Args&) { r.clear(); }
   __device__ __forceinline__ void take(const Args&, bool valid, int64_t, int64_t, T va, T vb) {
     if (!valid) return;
     if (va != va || vb != vb) {
@@ -126,17 +100,7 @@ struct PairRecordEpi {
     r.sse += d * d;
     r.max_abs_diff = fmax(r.max_abs_diff, fabs(d));
   }
-  __device__ __forceinline__ void finish(const Args& a) {
-    __shared__ PairRecord waves[4];
-    pair_fold_wave(r);
-    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      PairRecord t = waves[0];
-      for (int w = 1; w < 4; ++w) pair_fold(t, waves[w]);
-      a.partials[blockIdx.x].r = t;
-    }
-  }
+  __device__ __forceinline__ void finish(const Args& a) { stat_fold_group<PairRecord>(r, &a.partials[blockIdx.x]); }
 };
 
 struct JointHistArgs {
@@ -195,63 +159,6 @@ struct JointHistEpi {
 };
 
 // ------------------------------------------------------------------------------------------------ the product
-constexpr int kPad = 4;
-template <typename T>
-struct PairTile {
-  static constexpr int BK = sizeof(T) == 4 ? 16 : 8;
-  typedef typename std::conditional<sizeof(T) == 4, f32x16, f64x4>::type Frag;
-  static constexpr int kFrags = sizeof(T) == 4 ? 1 : 4, kPerFrag = sizeof(T) == 4 ? 16 : 4;
-};
-
-// acc <- the tile (m0, n0) of A (m x k) B (k x n): the k-loop of valstat_product_kernel without a column order,
-// instruction by instruction (the staging with its zero padding, the MFMA order), through the caller's LDS buffers
-template <typename T>
-__device__ __forceinline__ void pair_accumulate(const T* __restrict__ A, const T* __restrict__ B, int64_t m, int64_t n,
-                                                int64_t k, int64_t m0, int64_t n0,
-                                                T (&As)[PairTile<T>::BK][kBM + kPad], T (&Bs)[PairTile<T>::BK][kBN + kPad],
-                                                typename PairTile<T>::Frag (&acc)[PairTile<T>::kFrags]) {
-  constexpr int BK = PairTile<T>::BK;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-  for (auto& a : acc)
-    for (int r = 0; r < PairTile<T>::kPerFrag; ++r) a[r] = (T)0;
-
-  for (int64_t k0 = 0; k0 < k; k0 += BK) {
-    for (int e = tid; e < kBM * BK; e += 256) {
-      const int r = e / BK, kk = e % BK;
-      const int64_t gr = m0 + r, gk = k0 + kk;
-      As[kk][r] = (gr < m && gk < k) ? A[gr * k + gk] : (T)0;
-    }
-    for (int e = tid; e < BK * kBN; e += 256) {
-      const int kk = e / kBN, c = e % kBN;
-      const int64_t gk = k0 + kk, gc = n0 + c;
-      Bs[kk][c] = (gc < n && gk < k) ? B[gk * n + gc] : (T)0;
-    }
-    __syncthreads();
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 2)
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + (lane >> 5)][wm + (lane & 31)],
-                                                      Bs[kk + (lane >> 5)][wn + (lane & 31)], acc[0], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 4) {
-        double a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          a[i] = As[kk + (lane >> 4)][wm + 16 * i + (lane & 15)];
-          b[i] = Bs[kk + (lane >> 4)][wn + 16 * i + (lane & 15)];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[2 * i + j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[2 * i + j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // Ca = Aa (m x ka) Ba (ka x n) and Cb = Ab (m x kb) Bb (kb x n), dense row-major, tile by tile on a persistent grid:
 // both accumulator tiles of a tile index, one after the other through the same staging buffers, then the pairs
 // (valid, row, col, Ca[row, col], Cb[row, col]) to the epilogue.  Rows and columns beyond m and n are staged as zeros
@@ -260,53 +167,31 @@ template <typename T, typename Epi>
 __global__ void __launch_bounds__(256)
 pairstat_product_kernel(const T* __restrict__ Aa, const T* __restrict__ Ba, int64_t ka, const T* __restrict__ Ab,
                         const T* __restrict__ Bb, int64_t kb, int64_t m, int64_t n, const typename Epi::Args args) {
-  constexpr int BK = PairTile<T>::BK;
-  __shared__ T As[BK][kBM + kPad];  // k-major, as gemm.hip stages them: a fragment read is consecutive words
-  __shared__ T Bs[BK][kBN + kPad];
+  __shared__ typename StatTile<T>::StageA As;
+  __shared__ typename StatTile<T>::StageB Bs;
 
   Epi epi;
   epi.begin(args);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int64_t tiles_n = (n + kBN - 1) / kBN, tiles = (m + kBM - 1) / kBM * tiles_n;
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t m0 = (t / tiles_n) * kBM, n0 = (t % tiles_n) * kBN;
-    typename PairTile<T>::Frag acc_a[PairTile<T>::kFrags], acc_b[PairTile<T>::kFrags];
-    pair_accumulate<T>(Aa, Ba, m, n, ka, m0, n0, As, Bs, acc_a);
-    pair_accumulate<T>(Ab, Bb, m, n, kb, m0, n0, As, Bs, acc_b);
-
-    if constexpr (sizeof(T) == 4) {
-      const int64_t col = n0 + wn + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        epi.take(args, row < m && col < n, row, col, acc_a[0][r], acc_b[0][r]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t col = n0 + wn + 16 * j + (lane & 15);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int64_t row = m0 + wm + 16 * i + (lane >> 4) + 4 * r;
-            epi.take(args, row < m && col < n, row, col, acc_a[2 * i + j][r], acc_b[2 * i + j][r]);
-          }
-        }
-    }
+    typename StatTile<T>::Frag acc_a[StatTile<T>::kFrags], acc_b[StatTile<T>::kFrags];
+    stat_tile_accumulate<T>(Aa, Ba, nullptr, m, n, ka, m0, n0, As, Bs, acc_a);
+    stat_tile_accumulate<T>(Ab, Bb, nullptr, m, n, kb, m0, n0, As, Bs, acc_b);
+    stat_tile_for_each<T>(m0, n0, m, n, [&](bool valid, int64_t row, int64_t col, int i, int r) {
+      epi.take(args, valid, row, col, acc_a[i][r], acc_b[i][r]);
+    });
   }
   epi.finish(args);
 }
 
-// result <- the partial records folded in index order (one wavefront)
-__global__ void __launch_bounds__(64) pairstat_fold_kernel(const PairSlot* __restrict__ partials, int count, PairSlot* result) {
-  PairRecord r;
-  pair_clear(r);
-  for (int i = threadIdx.x; i < count; i += 64) pair_fold(r, partials[i].r);
-  pair_fold_wave(r);
-  if (threadIdx.x == 0) result->r = r;
+template <typename T, typename Epi>
+int pairstat_launch(const StatCall<T>& a, const StatCall<T>& b, const typename Epi::Args& args, int grid, size_t lds) {
+  hipLaunchKernelGGL((pairstat_product_kernel<T, Epi>), dim3(grid), dim3(256), lds, a.s, (const T*)a.ops.A, (const T*)a.ops.B,
+                     a.q.k, (const T*)b.ops.A, (const T*)b.ops.B, b.q.k, a.q.m, a.q.n, args);
+  NDMPS_LAUNCH_CHECK();
+  return NDMPS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -329,10 +214,10 @@ int pairstat_opt_in() {
 // The argument check of both entries, before the first launch: each chain as the single-chain entries check it, on its
 // own part of the workspace, then the pair.
 template <typename T>
-int pairstat_check(const ChainPairPlan& pp, const int64_t* dims, const int64_t* bonds_a, const int64_t* bonds_b,
-                   const T* const* cores_a, const T* const* cores_b, void* d_ws, int64_t ws_bytes) {
-  NDMPS_TRY(valstat_check(pp.a, dims, bonds_a, cores_a, d_ws, ws_bytes, nullptr));
-  NDMPS_TRY(valstat_check(pp.b, dims, bonds_b, cores_b, (char*)d_ws + pp.off_b, ws_bytes - pp.off_b, nullptr));
+int pairstat_check(const ChainPairPlan& pp, const StatCall<T>& a, const StatCall<T>& b, const int64_t* dims,
+                   const int64_t* bonds_a, const int64_t* bonds_b, int64_t ws_bytes) {
+  NDMPS_TRY(a.check(dims, bonds_a, ws_bytes, nullptr));
+  NDMPS_TRY(b.check(dims, bonds_b, ws_bytes - pp.off_b, nullptr));
   NDMPS_REQUIRE(!pp.error, "pairstat: %s", pp.error ? pp.error : "");
   if (ws_bytes < pp.total_bytes) {
     ndmps::set_error("pairstat workspace too small: %lld < %lld", (long long)ws_bytes, (long long)pp.total_bytes);
@@ -349,37 +234,20 @@ int pairstat_moments(int L, const int64_t* h_dims, const int64_t* h_bonds_a, con
                      int64_t ws_bytes, ndmps_stream_t stream) {
   NDMPS_REQUIRE(L >= 1 && h_dims && h_bonds_a && h_bonds_b && h_stats && h_counts, "bad pairstat argument");
   const ChainPairPlan pp = ndmps::chain_pair_plan(L, h_dims, h_bonds_a, h_bonds_b, sizeof(T));
-  NDMPS_TRY(pairstat_check(pp, h_dims, h_bonds_a, h_bonds_b, h_cores_a, h_cores_b, d_ws, ws_bytes));
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)d_ws;
-  Operands oa, ob;
-  NDMPS_TRY(valstat_run_chain(pp.a, h_cores_a, ws, nullptr, s, &oa));
-  NDMPS_TRY(valstat_run_chain(pp.b, h_cores_b, ws + pp.off_b, nullptr, s, &ob));
-  const ChainProduct &qa = pp.a.reduced, &qb = pp.b.reduced;
-  const int grid = valstat_grid(qa);
-  PairSlot* partials = (PairSlot*)(ws + pp.off_partials);
-  PairSlot* result = (PairSlot*)(ws + pp.off_result);
+  StatCall<T> a(pp.a, h_cores_a, d_ws, stream), b(pp.b, h_cores_b, (char*)d_ws + pp.off_b, stream);
+  NDMPS_TRY(pairstat_check(pp, a, b, h_dims, h_bonds_a, h_bonds_b, ws_bytes));
+  NDMPS_TRY(a.run(nullptr));
+  NDMPS_TRY(b.run(nullptr));
+  PairSlot* partials = (PairSlot*)(a.ws + pp.off_partials);
+  PairSlot* result = (PairSlot*)(a.ws + pp.off_result);
   const PairRecordArgs args{partials};
-  hipLaunchKernelGGL((pairstat_product_kernel<T, PairRecordEpi<T>>), dim3(grid), dim3(256), 0, s, (const T*)oa.A,
-                     (const T*)oa.B, qa.k, (const T*)ob.A, (const T*)ob.B, qb.k, qa.m, qa.n, args);
-  NDMPS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pairstat_fold_kernel, dim3(1), dim3(64), 0, s, partials, grid, result);
-  NDMPS_LAUNCH_CHECK();
+  NDMPS_TRY((pairstat_launch<T, PairRecordEpi<T>>(a, b, args, a.grid, 0)));
   PairRecord host;
-  NDMPS_CHECK_HIP(hipMemcpyAsync(&host, &result->r, sizeof(PairRecord), hipMemcpyDeviceToHost, s));
-  NDMPS_CHECK_HIP(hipStreamSynchronize(s));
+  NDMPS_TRY((stat_fetch_record<PairRecord>(partials, a.grid, result, &host, a.s)));
   const double stats[11] = {host.sum_a, host.sum_b, host.sumsq_a, host.sumsq_b, host.sum_ab, host.sse,
                             host.min_a, host.max_a, host.min_b, host.max_b, host.max_abs_diff};
   std::copy(stats, stats + 11, h_stats);
   h_counts[0] = host.count, h_counts[1] = host.n_nan;
-  return NDMPS_OK;
-}
-
-template <typename T>
-int pairstat_edges_ok(const T* e, int bins, const char* which) {
-  for (int i = 0; i <= bins; ++i)
-    NDMPS_REQUIRE(e[i] == e[i] && (i == 0 || e[i] >= e[i - 1]), "joint histogram: edges of %s must be ascending and not NaN (edge %d)",
-                  which, i);
   return NDMPS_OK;
 }
 
@@ -393,25 +261,22 @@ int pairstat_histogram(int L, const int64_t* h_dims, const int64_t* h_bonds_a, c
                 "joint histogram: %d x %d bins, an axis takes 1 to %d", bins_a, bins_b, ndmps::kPairstatMaxAxisBins);
   NDMPS_REQUIRE((int64_t)bins_a * bins_b <= ndmps::kPairstatMaxCells, "joint histogram: %d x %d bins are more than %d cells",
                 bins_a, bins_b, ndmps::kPairstatMaxCells);
-  NDMPS_TRY(pairstat_edges_ok(h_edges_a, bins_a, "a"));
-  NDMPS_TRY(pairstat_edges_ok(h_edges_b, bins_b, "b"));
+  NDMPS_TRY(stat_edges_ok(h_edges_a, bins_a, "joint histogram: edges of a"));
+  NDMPS_TRY(stat_edges_ok(h_edges_b, bins_b, "joint histogram: edges of b"));
   const int cells = bins_a * bins_b;
   const ChainPairPlan pp = ndmps::chain_pair_plan(L, h_dims, h_bonds_a, h_bonds_b, sizeof(T), cells, bins_a, bins_b);
-  NDMPS_TRY(pairstat_check(pp, h_dims, h_bonds_a, h_bonds_b, h_cores_a, h_cores_b, d_ws, ws_bytes));
-  const ChainProduct &qa = pp.a.reduced, &qb = pp.b.reduced;
+  StatCall<T> a(pp.a, h_cores_a, d_ws, stream), b(pp.b, h_cores_b, (char*)d_ws + pp.off_b, stream);
+  NDMPS_TRY(pairstat_check(pp, a, b, h_dims, h_bonds_a, h_bonds_b, ws_bytes));
   const size_t lds = joint_hist_lds(bins_a, bins_b, sizeof(T));
-  const int64_t tiles = ceil_div(qa.m, kBM) * ceil_div(qa.n, kBN);
+  const int64_t tiles = stat_tiles(a.q);
   // above 64 KB of counters and edges a CU holds one workgroup
   const int grid = (int)std::min<int64_t>(tiles, lds > 65536 ? ndmps::kNumCU : ndmps::kValstatMaxGroups);
-  // a workgroup counts in 32 bits until its one flush
-  NDMPS_REQUIRE(ceil_div(tiles, grid) * kBM * kBN < (int64_t)UINT32_MAX,
-                "joint histogram: volume too large for 32-bit counters per workgroup");
+  NDMPS_TRY(stat_counters_fit(tiles, grid, "joint histogram"));
   NDMPS_TRY(pairstat_opt_in());
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)d_ws;
-  Operands oa, ob;
-  NDMPS_TRY(valstat_run_chain(pp.a, h_cores_a, ws, nullptr, s, &oa));
-  NDMPS_TRY(valstat_run_chain(pp.b, h_cores_b, ws + pp.off_b, nullptr, s, &ob));
+  NDMPS_TRY(a.run(nullptr));
+  NDMPS_TRY(b.run(nullptr));
+  hipStream_t s = a.s;
+  char* ws = a.ws;
   unsigned long long* counts = (unsigned long long*)(ws + pp.off_counts);
   T* edges_a = (T*)(ws + pp.off_edges_a);
   T* edges_b = (T*)(ws + pp.off_edges_b);
@@ -419,9 +284,7 @@ int pairstat_histogram(int L, const int64_t* h_dims, const int64_t* h_bonds_a, c
   NDMPS_CHECK_HIP(hipMemcpyAsync(edges_a, h_edges_a, (size_t)(bins_a + 1) * sizeof(T), hipMemcpyHostToDevice, s));
   NDMPS_CHECK_HIP(hipMemcpyAsync(edges_b, h_edges_b, (size_t)(bins_b + 1) * sizeof(T), hipMemcpyHostToDevice, s));
   const JointHistArgs args{edges_a, edges_b, counts, bins_a, bins_b};
-  hipLaunchKernelGGL((pairstat_product_kernel<T, JointHistEpi<T>>), dim3(grid), dim3(256), lds, s, (const T*)oa.A,
-                     (const T*)oa.B, qa.k, (const T*)ob.A, (const T*)ob.B, qb.k, qa.m, qa.n, args);
-  NDMPS_LAUNCH_CHECK();
+  NDMPS_TRY((pairstat_launch<T, JointHistEpi<T>>(a, b, args, grid, lds)));
   static_assert(sizeof(int64_t) == sizeof(unsigned long long), "counter width");
   NDMPS_CHECK_HIP(hipMemcpyAsync(h_counts, counts, (size_t)(cells + 2) * 8, hipMemcpyDeviceToHost, s));
   NDMPS_CHECK_HIP(hipStreamSynchronize(s));

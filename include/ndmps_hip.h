@@ -571,7 +571,7 @@ int ndmps_chain_contract_scatter_batched_f32(int batch, int L, const int64_t* h_
 int ndmps_chain_plan_query(int elem, int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t* h_out);
 /* Value statistics of the volume a chain decodes to, and its error against an original, WITHOUT the volume: the chain
  * is contracted as ndmps_chain_contract_* contracts it, but the last product -- the only one that touches N
- * elements -- hands its accumulator tiles to a reducing epilogue instead of storing them (csrc/valstat.hip).  fp32
+ * elements -- hands its accumulator tiles to a reducing epilogue instead of storing them (csrc/valstat.hip; the product kernel: csrc/valstat_device.h).  fp32
  * cores on the fp32 MFMA, fp64 cores on the fp64 MFMA.  Every call checks its arguments before its first launch,
  * reads its small result record back once and returns with the stream synchronised.  The same inputs give the same
  * bits: sums are fp64, folded in a fixed order, and only integers are added atomically.
@@ -629,7 +629,7 @@ int ndmps_valstat_error_f64(int L, const int64_t* h_dims, const int64_t* h_bonds
                             const double* d_ref, const int64_t* d_row_off, const int64_t* d_col_off,
                             const int32_t* d_col_perm, int64_t n_cols, double* h_stats, int64_t* h_counts, void* d_ws,
                             int64_t ws_bytes, ndmps_stream_t stream);
-/* ---- Extremes along axes and the place of the global extreme, from the cores (csrc/valstat.hip, core/axisext.py).
+/* ---- Extremes along axes and the place of the global extreme, from the cores (csrc/axisext.hip, core/axisext.py).
  * The same chain contraction and the same workspace as the value statistics (ndmps_valstat_workspace_bytes with
  * n_bins = 0); the last product's epilogue turns every voxel into an unsigned key whose integer order is the order of
  * the values and combines the keys of one output cell with integer atomic maxima, so the same inputs give the same
@@ -659,7 +659,7 @@ int ndmps_argext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const
 int ndmps_argext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
                      const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
                      double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
-/* ---- Statistics per label of an atlas, from the cores (csrc/valstat.hip, core/labelstat.py).
+/* ---- Statistics per label of an atlas, from the cores (csrc/labelstat.hip, core/labelstat.py).
  * The chain contraction of the value statistics; the last product runs twice over the same operands.  The first run is
  * the moments pass, whose minimum and maximum fix on the device the two power-of-two scales s and s2; the second hands
  * every voxel v with its label d_labels[d_row_off[r] + d_col_off[c]] (the tables of the error entry; an offset outside

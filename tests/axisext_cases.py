@@ -1,4 +1,4 @@
-"""Cases, references and bars of the extremes along axes from the cores (csrc/valstat.hip, core/axisext.py).
+"""Cases, references and bars of the extremes along axes from the cores (csrc/axisext.hip, core/axisext.py).
 
 Nothing here touches a GPU: tests/test_axisext_host.py runs the planner and the bars on the reference and on modelled
 faults, tests/test_gpu_axisext.py on what the kernels return.

@@ -1,4 +1,4 @@
-"""Cases, references and bars of the statistics per label from the cores (LabelEpi in csrc/valstat.hip,
+"""Cases, references and bars of the statistics per label from the cores (LabelEpi in csrc/labelstat.hip,
 core/labelstat.py).
 
 The chains, their fp64 references and their element bounds are those of tests/valstat_cases.py (``vc.Case``, imported

@@ -1,4 +1,4 @@
-"""Extremes along axes and the place of the global extreme from the cores (csrc/valstat.hip, core/axisext.py), on the
+"""Extremes along axes and the place of the global extreme from the cores (csrc/axisext.hip, core/axisext.py), on the
 GPU, against the fp64 contraction of oracle/mps.py through the bars of tests/axisext_cases.py (which
 tests/test_axisext_host.py shows to accept the reference and to reject a tile left out, padding counted, the last
 occurrence, a dropped column index, unpermuted columns and a NaN that wins).

@@ -1,4 +1,4 @@
-"""Statistics per label from the cores (LabelEpi in csrc/valstat.hip, core/labelstat.py), on the GPU, against NumPy on
+"""Statistics per label from the cores (LabelEpi in csrc/labelstat.hip, core/labelstat.py), on the GPU, against NumPy on
 the fp64 contraction of oracle/mps.py through the bars of tests/labelstat_cases.py (which tests/test_labelstat_host.py
 shows to accept the reference and to reject labels read in site order, a tile left out, padding counted, a run never
 flushed, folded windows, NaN counted and outside voxels added to a label).

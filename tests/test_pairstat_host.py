@@ -6,6 +6,7 @@
   single-chain entries on either chain, with pointers that are never dereferenced.  The C entries take ONE dims array,
   and chain_plan splits by the dims alone, so two last products that differ in rows or columns cannot be handed to
   them; that refusal is made where two chains meet, in core/pairstat.py, and tested there.
+* pinned answers: code and whole message of every such refusal, and the workspace and plan of every pair, as literals.
 * mutual information from planted count tables.
 * the preconditions of the NDMPS methods, on objects built without a device.
 """
@@ -146,6 +147,277 @@ def test_refusals_before_any_launch(lib):
     assert lib.ndmps_pairstat_plan_query(0, L, d, ba, bb, 1024, 17, out) == _lib.EINVAL and b"16384" in lib.ndmps_last_error()
     assert lib.ndmps_pairstat_plan_query(1, L, d, ba, bb, 0, 0, out) == _lib.EINVAL  # bf16 has no statistics entry
     assert lib.ndmps_pairstat_plan_query(0, L, d, ba, bb, 0, 0, None) == _lib.EINVAL
+
+
+# ------------------------------------------------------------------------------------------------ pinned answers
+# What the two pair entries answer before their first HIP call, as literals (return code and the whole message, in the
+# order the checks are made), and the workspace and the plan of every pair.  Taken from the build before the
+# statistics family got its shared host prologue; a change of any of them is a change of behaviour.
+def refusal_calls(lib, suffix):
+    """name -> call, each refused before the first HIP call (the pointers are fakes)."""
+    dims, bonds_a = vc.ALL_CHAINS["L4_tail_last"]
+    L, d, ba, bb = len(dims), _lib.i64_array(dims), _lib.i64_array(bonds_a), _lib.i64_array(pc.REAL_PAIRS["L4_tail_last"])
+    eb, arr = (4, C.c_float) if suffix == "f32" else (8, C.c_double)
+    fake = (C.c_void_p * L)(*[256] * L)
+    hole = (C.c_void_p * L)(256, None, 256, 256)
+    p, big = 256, 1 << 40
+    stats, counts = (C.c_double * 11)(), (C.c_int64 * 16386)()
+    need = lib.ndmps_pairstat_workspace_bytes(L, d, ba, bb, eb, 0, 0)
+    need_a = lib.ndmps_valstat_workspace_bytes(L, d, ba, eb, 0)
+    up = _lib.i64_array([1, 4, 13, 13, 1])
+    e4, e2, wide = (arr * 5)(0, 1, 2, 3, 4), (arr * 3)(0, 1, 2), (arr * 1026)(*range(1026))
+    down, hurt = (arr * 5)(0, 1, 3, 2, 4), (arr * 3)(0, float("nan"), 2)
+
+    def mom(L=L, d=d, a=ba, b=bb, cores_a=fake, cores_b=fake, stats=stats, ws=p, nbytes=big):
+        return getattr(lib, f"ndmps_pairstat_moments_{suffix}")(L, d, a, b, cores_a, cores_b, stats, counts, ws, nbytes, None)
+
+    def hist(L=L, d=d, a=ba, b=bb, cores_a=fake, cores_b=fake, ea=e4, na=4, eb_=e2, nb=2, ws=p, nbytes=big):
+        return getattr(lib, f"ndmps_pairstat_histogram_{suffix}")(L, d, a, b, cores_a, cores_b, ea, na, eb_, nb, counts, ws,
+                                                                 nbytes, None)
+
+    calls = {}
+    for name, f in (("moments", mom), ("histogram", hist)):
+        calls.update({
+            f"{name}/no_sites": lambda f=f: f(L=0),
+            f"{name}/no_dims": lambda f=f: f(d=None),
+            f"{name}/no_bonds_of_b": lambda f=f: f(b=None),
+            f"{name}/no_cores_of_a": lambda f=f: f(cores_a=None),
+            f"{name}/no_cores_of_b": lambda f=f: f(cores_b=None),
+            f"{name}/core_1_of_b_null": lambda f=f: f(cores_b=hole),
+            f"{name}/boundary_of_b": lambda f=f: f(b=_lib.i64_array([2, 3, 13, 13, 1])),
+            f"{name}/bond_of_a_exceeds": lambda f=f: f(a=up),
+            f"{name}/bond_of_b_exceeds": lambda f=f: f(b=up),
+            f"{name}/both_bonds_exceed": lambda f=f: f(a=up, b=_lib.i64_array([1, 3, 28, 13, 1])),
+            f"{name}/workspace_null": lambda f=f: f(ws=None),
+            f"{name}/workspace_short_for_a": lambda f=f: f(nbytes=need_a - 1),
+            f"{name}/workspace_short_for_b": lambda f=f: f(nbytes=need_a + 256),
+            f"{name}/workspace_short_for_the_pair": lambda f=f: f(nbytes=need - 1),
+            f"{name}/workspace_misaligned": lambda f=f: f(ws=264),
+            f"{name}/bond_of_b_exceeds_and_workspace_short_for_a": lambda f=f: f(b=up, nbytes=1),
+        })
+    calls.update({
+        "moments/no_result": lambda: mom(stats=None),
+        "histogram/no_edges_of_b": lambda: hist(eb_=None),
+        "histogram/axis_a_too_wide": lambda: hist(ea=wide, na=1025, nb=1),
+        "histogram/axis_b_too_wide": lambda: hist(na=1, eb_=wide, nb=1025),
+        "histogram/no_bins_on_a": lambda: hist(na=0),
+        "histogram/too_many_cells": lambda: hist(ea=wide, na=1024, eb_=wide, nb=17),
+        "histogram/edges_of_a_descend": lambda: hist(ea=down),
+        "histogram/edge_of_b_nan": lambda: hist(eb_=hurt),
+        "histogram/both_edge_tables_bad": lambda: hist(ea=down, eb_=hurt),
+        "histogram/too_many_cells_and_edges_descend": lambda: hist(ea=down, na=1024, eb_=wide, nb=17),
+        "histogram/edges_descend_and_bond_exceeds": lambda: hist(ea=down, a=up),
+        "histogram/edge_nan_and_workspace_short": lambda: hist(eb_=hurt, nbytes=1),
+        "histogram/workspace_short_for_the_cells": lambda: hist(nbytes=need),
+        "histogram/the_limit_itself_with_no_room": lambda: hist(ea=wide, na=1024, eb_=wide, nb=16, nbytes=1),
+    })
+    return calls
+
+
+def refusals(lib):
+    out = {}
+    for suffix in ("f32", "f64"):
+        for name, call in refusal_calls(lib, suffix).items():
+            rc = call()
+            out[f"{name}/{suffix}"] = (rc, lib.ndmps_last_error().decode() if rc != _lib.OK else "")
+    out["query/axis"] = (lib.ndmps_pairstat_plan_query(0, 2, _lib.i64_array([4, 4]), _lib.i64_array([1, 2, 1]),
+                                                       _lib.i64_array([1, 3, 1]), 1025, 1, (C.c_int64 * len(SLOTS))()),
+                         lib.ndmps_last_error().decode())
+    out["query/cells"] = (lib.ndmps_pairstat_plan_query(2, 2, _lib.i64_array([4, 4]), _lib.i64_array([1, 2, 1]),
+                                                        _lib.i64_array([1, 3, 1]), 1024, 17, (C.c_int64 * len(SLOTS))()),
+                          lib.ndmps_last_error().decode())
+    out["query/one_axis_without_bins"] = (lib.ndmps_pairstat_plan_query(0, 2, _lib.i64_array([4, 4]), _lib.i64_array([1, 2, 1]),
+                                                                        _lib.i64_array([1, 3, 1]), 4, 0, (C.c_int64 * len(SLOTS))()),
+                                          lib.ndmps_last_error().decode())
+    out["query/element"] = (lib.ndmps_pairstat_plan_query(1, 2, _lib.i64_array([4, 4]), _lib.i64_array([1, 2, 1]),
+                                                          _lib.i64_array([1, 3, 1]), 0, 0, (C.c_int64 * len(SLOTS))()),
+                            lib.ndmps_last_error().decode())
+    return out
+
+
+def sizes(lib):
+    """name -> per element type: the workspace of the moments and of 128 x 128 cells, then the plan query's fourteen
+    slots at 64 x 16 bins."""
+    out = {}
+    for name in sorted(ALL_PAIRS):
+        dims, bonds_a = pc.CHAINS[name]
+        L, d, ba, bb = len(dims), _lib.i64_array(dims), _lib.i64_array(bonds_a), _lib.i64_array(ALL_PAIRS[name])
+        row = []
+        for elem, eb in (("f32", 4), ("f64", 8)):
+            row += [lib.ndmps_pairstat_workspace_bytes(L, d, ba, bb, eb, 0, 0),
+                    lib.ndmps_pairstat_workspace_bytes(L, d, ba, bb, eb, 128, 128)]
+            row.append(tuple(_plan(lib, dims, bonds_a, ALL_PAIRS[name], elem, 64, 16)[k] for k in SLOTS))
+        out[name] = tuple(row)
+    return out
+
+
+REFUSED = {'moments/no_sites/f32': (-1, 'bad pairstat argument'),
+ 'moments/no_dims/f32': (-1, 'bad pairstat argument'),
+ 'moments/no_bonds_of_b/f32': (-1, 'bad pairstat argument'),
+ 'moments/no_cores_of_a/f32': (-1, 'bad valstat argument'),
+ 'moments/no_cores_of_b/f32': (-1, 'bad valstat argument'),
+ 'moments/core_1_of_b_null/f32': (-1, 'dims[1] must be positive and core 1 non-NULL'),
+ 'moments/boundary_of_b/f32': (-1, 'open boundary bonds must be 1'),
+ 'moments/bond_of_a_exceeds/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/bond_of_b_exceeds/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/both_bonds_exceed/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/workspace_null/f32': (-4, 'valstat workspace too small: 1099511627776 < 246272'),
+ 'moments/workspace_short_for_a/f32': (-4, 'valstat workspace too small: 246271 < 246272'),
+ 'moments/workspace_short_for_b/f32': (-4, 'valstat workspace too small: 256 < 684800'),
+ 'moments/workspace_short_for_the_pair/f32': (-4, 'pairstat workspace too small: 996863 < 996864'),
+ 'moments/workspace_misaligned/f32': (-1, 'valstat workspace must be 256-byte aligned'),
+ 'moments/bond_of_b_exceeds_and_workspace_short_for_a/f32': (-4, 'valstat workspace too small: 1 < 246272'),
+ 'histogram/no_sites/f32': (-1, 'bad pairstat argument'),
+ 'histogram/no_dims/f32': (-1, 'bad pairstat argument'),
+ 'histogram/no_bonds_of_b/f32': (-1, 'bad pairstat argument'),
+ 'histogram/no_cores_of_a/f32': (-1, 'bad valstat argument'),
+ 'histogram/no_cores_of_b/f32': (-1, 'bad valstat argument'),
+ 'histogram/core_1_of_b_null/f32': (-1, 'dims[1] must be positive and core 1 non-NULL'),
+ 'histogram/boundary_of_b/f32': (-1, 'open boundary bonds must be 1'),
+ 'histogram/bond_of_a_exceeds/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/bond_of_b_exceeds/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/both_bonds_exceed/f32': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/workspace_null/f32': (-4, 'valstat workspace too small: 1099511627776 < 246272'),
+ 'histogram/workspace_short_for_a/f32': (-4, 'valstat workspace too small: 246271 < 246272'),
+ 'histogram/workspace_short_for_b/f32': (-4, 'valstat workspace too small: 256 < 684800'),
+ 'histogram/workspace_short_for_the_pair/f32': (-4, 'pairstat workspace too small: 996863 < 997632'),
+ 'histogram/workspace_misaligned/f32': (-1, 'valstat workspace must be 256-byte aligned'),
+ 'histogram/bond_of_b_exceeds_and_workspace_short_for_a/f32': (-4, 'valstat workspace too small: 1 < 246272'),
+ 'moments/no_result/f32': (-1, 'bad pairstat argument'),
+ 'histogram/no_edges_of_b/f32': (-1, 'bad pairstat argument'),
+ 'histogram/axis_a_too_wide/f32': (-1, 'joint histogram: 1025 x 1 bins, an axis takes 1 to 1024'),
+ 'histogram/axis_b_too_wide/f32': (-1, 'joint histogram: 1 x 1025 bins, an axis takes 1 to 1024'),
+ 'histogram/no_bins_on_a/f32': (-1, 'joint histogram: 0 x 2 bins, an axis takes 1 to 1024'),
+ 'histogram/too_many_cells/f32': (-1, 'joint histogram: 1024 x 17 bins are more than 16384 cells'),
+ 'histogram/edges_of_a_descend/f32': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/edge_of_b_nan/f32': (-1, 'joint histogram: edges of b must be ascending and not NaN (edge 1)'),
+ 'histogram/both_edge_tables_bad/f32': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/too_many_cells_and_edges_descend/f32': (-1, 'joint histogram: 1024 x 17 bins are more than 16384 cells'),
+ 'histogram/edges_descend_and_bond_exceeds/f32': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/edge_nan_and_workspace_short/f32': (-1, 'joint histogram: edges of b must be ascending and not NaN (edge 1)'),
+ 'histogram/workspace_short_for_the_cells/f32': (-4, 'pairstat workspace too small: 996864 < 997632'),
+ 'histogram/the_limit_itself_with_no_room/f32': (-4, 'valstat workspace too small: 1 < 246272'),
+ 'moments/no_sites/f64': (-1, 'bad pairstat argument'),
+ 'moments/no_dims/f64': (-1, 'bad pairstat argument'),
+ 'moments/no_bonds_of_b/f64': (-1, 'bad pairstat argument'),
+ 'moments/no_cores_of_a/f64': (-1, 'bad valstat argument'),
+ 'moments/no_cores_of_b/f64': (-1, 'bad valstat argument'),
+ 'moments/core_1_of_b_null/f64': (-1, 'dims[1] must be positive and core 1 non-NULL'),
+ 'moments/boundary_of_b/f64': (-1, 'open boundary bonds must be 1'),
+ 'moments/bond_of_a_exceeds/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/bond_of_b_exceeds/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/both_bonds_exceed/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'moments/workspace_null/f64': (-4, 'valstat workspace too small: 1099511627776 < 435712'),
+ 'moments/workspace_short_for_a/f64': (-4, 'valstat workspace too small: 435711 < 435712'),
+ 'moments/workspace_short_for_b/f64': (-4, 'valstat workspace too small: 256 < 1266944'),
+ 'moments/workspace_short_for_the_pair/f64': (-4, 'pairstat workspace too small: 1768447 < 1768448'),
+ 'moments/workspace_misaligned/f64': (-1, 'valstat workspace must be 256-byte aligned'),
+ 'moments/bond_of_b_exceeds_and_workspace_short_for_a/f64': (-4, 'valstat workspace too small: 1 < 435712'),
+ 'histogram/no_sites/f64': (-1, 'bad pairstat argument'),
+ 'histogram/no_dims/f64': (-1, 'bad pairstat argument'),
+ 'histogram/no_bonds_of_b/f64': (-1, 'bad pairstat argument'),
+ 'histogram/no_cores_of_a/f64': (-1, 'bad valstat argument'),
+ 'histogram/no_cores_of_b/f64': (-1, 'bad valstat argument'),
+ 'histogram/core_1_of_b_null/f64': (-1, 'dims[1] must be positive and core 1 non-NULL'),
+ 'histogram/boundary_of_b/f64': (-1, 'open boundary bonds must be 1'),
+ 'histogram/bond_of_a_exceeds/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/bond_of_b_exceeds/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/both_bonds_exceed/f64': (-1, 'bond 1 = 4 exceeds min(3, 37440), the rank any unfolding can have'),
+ 'histogram/workspace_null/f64': (-4, 'valstat workspace too small: 1099511627776 < 435712'),
+ 'histogram/workspace_short_for_a/f64': (-4, 'valstat workspace too small: 435711 < 435712'),
+ 'histogram/workspace_short_for_b/f64': (-4, 'valstat workspace too small: 256 < 1266944'),
+ 'histogram/workspace_short_for_the_pair/f64': (-4, 'pairstat workspace too small: 1768447 < 1769216'),
+ 'histogram/workspace_misaligned/f64': (-1, 'valstat workspace must be 256-byte aligned'),
+ 'histogram/bond_of_b_exceeds_and_workspace_short_for_a/f64': (-4, 'valstat workspace too small: 1 < 435712'),
+ 'moments/no_result/f64': (-1, 'bad pairstat argument'),
+ 'histogram/no_edges_of_b/f64': (-1, 'bad pairstat argument'),
+ 'histogram/axis_a_too_wide/f64': (-1, 'joint histogram: 1025 x 1 bins, an axis takes 1 to 1024'),
+ 'histogram/axis_b_too_wide/f64': (-1, 'joint histogram: 1 x 1025 bins, an axis takes 1 to 1024'),
+ 'histogram/no_bins_on_a/f64': (-1, 'joint histogram: 0 x 2 bins, an axis takes 1 to 1024'),
+ 'histogram/too_many_cells/f64': (-1, 'joint histogram: 1024 x 17 bins are more than 16384 cells'),
+ 'histogram/edges_of_a_descend/f64': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/edge_of_b_nan/f64': (-1, 'joint histogram: edges of b must be ascending and not NaN (edge 1)'),
+ 'histogram/both_edge_tables_bad/f64': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/too_many_cells_and_edges_descend/f64': (-1, 'joint histogram: 1024 x 17 bins are more than 16384 cells'),
+ 'histogram/edges_descend_and_bond_exceeds/f64': (-1, 'joint histogram: edges of a must be ascending and not NaN (edge 3)'),
+ 'histogram/edge_nan_and_workspace_short/f64': (-1, 'joint histogram: edges of b must be ascending and not NaN (edge 1)'),
+ 'histogram/workspace_short_for_the_cells/f64': (-4, 'pairstat workspace too small: 1768448 < 1769216'),
+ 'histogram/the_limit_itself_with_no_room/f64': (-4, 'valstat workspace too small: 1 < 435712'),
+ 'query/axis': (-1, 'joint histogram: 1025 x 1 bins, an axis takes 1 to 1024'),
+ 'query/cells': (-1, 'joint histogram: 1024 x 17 bins are more than 16384 cells'),
+ 'query/one_axis_without_bins': (-1, 'joint histogram: 4 x 0 bins: both at least 1, or both 0 for the moments'),
+ 'query/element': (-1, 'bad pairstat plan query (elem=1)')}
+SIZES = {'L1': (136960, 269824, (1, 37, 1, 1, 35584, 35584, 35584, 71168, 136704, 136960, 145408, 145920, 75008, 146176), 137984,
+        271872, (1, 37, 1, 1, 36096, 36096, 36096, 72192, 137728, 137984, 146432, 147200, 75264, 147456)),
+ 'L2_maxbond': (171776, 304640, (33, 65, 33, 5, 65792, 40192, 65792, 105984, 171520, 171776, 180224, 180736, 75008, 180992),
+                203008, 336896,
+                (33, 65, 33, 5, 92416, 44800, 92416, 137216, 202752, 203008, 211456, 212224, 75264, 212480)),
+ 'L4_no_tail': (2019584, 2152448,
+                (12, 8192, 7, 12, 935936, 1017856, 935936, 1953792, 2019328, 2019584, 2028032, 2028544, 75008, 2028800),
+                3592448, 3726336,
+                (12, 8192, 7, 12, 1722368, 1804288, 1722368, 3526656, 3592192, 3592448, 3600896, 3601664, 75264, 3601920)),
+ 'L4_tail_4096': (1163008, 1295872,
+                  (16, 4096, 16, 9, 692224, 404992, 692224, 1097216, 1162752, 1163008, 1171456, 1171968, 75008, 1172224),
+                  1985792, 2119680,
+                  (16, 4096, 16, 9, 1218560, 701440, 1218560, 1920000, 1985536, 1985792, 1994240, 1995008, 75264, 1995264)),
+ 'L4_tail_last': (996864, 1129728,
+                  (1755, 64, 13, 40, 246272, 684800, 246272, 931072, 996608, 996864, 1005312, 1005824, 75008, 1006080),
+                  1768448, 1902336,
+                  (1755, 64, 13, 40, 435712, 1266944, 435712, 1702656, 1768192, 1768448, 1776896, 1777664, 75264, 1777920)),
+ 'L5_mid_tail_65': (2014208, 2147072,
+                    (90, 1716, 65, 40, 1197568, 750848, 1197568, 1948416, 2013952, 2014208, 2022656, 2023168, 75008,
+                     2023424),
+                    3532288, 3666176,
+                    (90, 1716, 65, 40, 2137088, 1329408, 2137088, 3466496, 3532032, 3532288, 3540736, 3541504, 75264,
+                     3541760)),
+ 'L5_ragged': (295936, 428800,
+               (7, 1320, 7, 5, 128256, 101888, 128256, 230144, 295680, 295936, 304384, 304896, 75008, 305152), 424448,
+               558336, (7, 1320, 7, 5, 203008, 155648, 203008, 358656, 424192, 424448, 432896, 433664, 75264, 433920)),
+ 'L5_tail_last': (1734144, 1867008,
+                  (3900, 64, 33, 16, 1111552, 556800, 1111552, 1668352, 1733888, 1734144, 1742592, 1743104, 75008, 1743360),
+                  3288064, 3421952,
+                  (3900, 64, 33, 16, 2158080, 1064192, 2158080, 3222272, 3287808, 3288064, 3296512, 3297280, 75264,
+                   3297536)),
+ 'L6_tail_all': (274688, 407552,
+                 (4, 3456, 3, 1, 139008, 69888, 139008, 208896, 274432, 274688, 283136, 283648, 75008, 283904), 386304,
+                 520192, (4, 3456, 3, 1, 222464, 98048, 222464, 320512, 386048, 386304, 394752, 395520, 75264, 395776)),
+ 'int_8x7': (1216768, 1349632,
+             (512, 4096, 16, 8, 755712, 395264, 755712, 1150976, 1216512, 1216768, 1225216, 1225728, 75008, 1225984),
+             2101504, 2235392,
+             (512, 4096, 16, 8, 1345536, 690176, 1345536, 2035712, 2101248, 2101504, 2109952, 2110720, 75264, 2110976)),
+ 'int_many_tiles': (1736960, 1869824,
+                    (2, 40010, 2, 2, 835584, 835584, 835584, 1671168, 1736704, 1736960, 1745408, 1745920, 75008, 1746176),
+                    3017984, 3151872,
+                    (2, 40010, 2, 2, 1476096, 1476096, 1476096, 2952192, 3017728, 3017984, 3026432, 3027200, 75264,
+                     3027456)),
+ 'int_no_tail': (1806592, 1939456,
+                 (12, 8192, 2, 4, 854016, 886784, 854016, 1740800, 1806336, 1806592, 1815040, 1815552, 75008, 1815808),
+                 3379456, 3513344,
+                 (12, 8192, 2, 4, 1640448, 1673216, 1640448, 3313664, 3379200, 3379456, 3387904, 3388672, 75264, 3388928)),
+ 'int_tail_all': (162048, 294912, (5, 504, 2, 3, 45568, 50688, 45568, 96256, 161792, 162048, 170496, 171008, 75008, 171264),
+                  183552, 317440,
+                  (5, 504, 2, 3, 54272, 63488, 54272, 117760, 183296, 183552, 192000, 192768, 75264, 193024)),
+ 'int_tail_last': (177408, 310272,
+                   (600, 41, 5, 2, 64000, 47616, 64000, 111616, 177152, 177408, 185856, 186368, 75008, 186624), 214272,
+                   348160, (600, 41, 5, 2, 90112, 58368, 90112, 148480, 214016, 214272, 222720, 223488, 75264, 223744)),
+ 'int_wide': (309248, 442112, (8, 1440, 8, 4, 150528, 92928, 150528, 243456, 308992, 309248, 317696, 318208, 75008, 318464),
+              448512, 582400,
+              (8, 1440, 8, 4, 243200, 139520, 243200, 382720, 448256, 448512, 456960, 457728, 75264, 457984))}
+
+
+def test_every_refusal_is_pinned(lib):
+    got = refusals(lib)
+    assert sorted(got) == sorted(REFUSED)
+    for name, answer in got.items():
+        assert answer[0] < 0, f"{name} was not refused"
+        assert answer == REFUSED[name], (name, answer, REFUSED[name])
+
+
+def test_sizes_and_plans_are_pinned(lib):
+    got = sizes(lib)
+    assert sorted(got) == sorted(SIZES)
+    for name, answer in got.items():
+        assert answer == SIZES[name], (name, answer, SIZES[name])
 
 
 # ------------------------------------------------------------------------------------------------ mutual information
