@@ -141,6 +141,10 @@ SIGNATURES = {
                                     vp]),
     "ndmps_argext_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
     "ndmps_argext_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, vp, vp, vp, i64, p_f64, p_i64, vp, i64, vp]),
+    "ndmps_select_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, C.c_double, C.c_double, vp, vp, vp, i64, i64,
+                                   vp, vp, p_i64, vp, i64, vp]),
+    "ndmps_select_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), C.c_int, C.c_double, C.c_double, vp, vp, vp, i64, i64,
+                                   vp, vp, p_i64, vp, i64, vp]),
     "ndmps_labelstat_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, i64, i64]),
     "ndmps_labelstat_scales": (C.c_int, [C.c_double, i64, p_int, p_int]),
     "ndmps_labelstat_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, vp, vp, vp,

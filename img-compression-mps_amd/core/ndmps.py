@@ -1458,6 +1458,55 @@ class NDMPS:
         chain, plan = self._valstat_chain("argmin", with_plan=True)
         return _ax.reduce_index(chain, plan, "min", axis, keepdims, as_torch, return_values)
 
+    def count_between(self, lo=None, hi=None, invert: bool = False) -> int:
+        """The number of non-NaN voxels of ``to_tensor()`` with ``lo <= v <= hi`` (None: unbounded; ``invert``: the
+        non-NaN voxels outside the interval), from the cores: the clipped moments pass of ``value_stats``.  The bounds
+        are cast to the cores' element type and compared with the computed voxel in that type, so the count equals
+        ``len(find(lo, hi)[0])`` and the one bin of ``histogram(bins=[lo, hi])``.  ValueError for a NaN bound,
+        ``lo > hi`` and what ``value_stats`` refuses."""
+        from . import select as _sel
+
+        chain = self._valstat_chain("count_between")
+        return _sel.count_between(chain, lo, hi, invert)
+
+    def find(self, lo=None, hi=None, *, invert: bool = False, max_count: int = 1 << 20, coords: bool = False,
+             as_torch: bool = False):
+        """``(index, values)`` of the voxels of ``to_tensor()`` with ``lo <= v <= hi``, without the volume
+        (core/select.py, csrc/select.hip): ``index`` is ``np.flatnonzero((v >= lo) & (v <= hi))``, int64 flat C-order
+        indices ascending, or with ``coords`` their ``np.unravel_index`` as a (K, ndim) int64 array, and ``values`` the
+        voxels there in the cores' element type.  ``invert`` selects the non-NaN voxels outside the interval; NaN voxels
+        are never selected (``find_nan`` lists them).  The call counts first and allocates exactly the K slots; more
+        than ``max_count`` matches raise ValueError naming the count, nothing is truncated.  NumPy arrays, or device
+        tensors with ``as_torch``; the same object gives the same bytes.  ValueError for a NaN bound, ``lo > hi``, a
+        negative ``max_count`` and what ``value_stats`` refuses."""
+        from . import select as _sel
+
+        _sel.check_find(self._valstat_chain("find"), lo, hi, max_count)  # the refusals that need no device, first
+        chain, plan = self._valstat_chain("find", with_plan=True)
+        return _sel.find(chain, plan, lo, hi, invert, max_count, coords, as_torch)
+
+    def find_nan(self, max_count: int = 1 << 20, coords: bool = False):
+        """The flat C-order indices (``coords``: the (K, ndim) coordinates) of the NaN voxels of ``to_tensor()``,
+        ascending, from the cores; as ``find``."""
+        from . import select as _sel
+
+        _sel.check_find(self._valstat_chain("find_nan"), None, None, max_count)
+        chain, plan = self._valstat_chain("find_nan", with_plan=True)
+        return _sel.find_nan(chain, plan, max_count, coords)
+
+    def topk(self, k, largest: bool = True, *, max_count: int = 1 << 20, coords: bool = False, as_torch: bool = False):
+        """``(index, values)`` of the ``k`` largest (``largest=False``: smallest) non-NaN voxels of ``to_tensor()``, from
+        the cores: ordered by value and among equal values by ascending flat index, ``np.lexsort((flat_index, -v))[:k]``;
+        all of them where fewer than ``k`` are not NaN.  Histogram passes bracket the k-th value as ``quantile``'s do,
+        until one ``find`` of at most ``max_count`` voxels holds the answer; where more than that tie at the k-th value
+        ``t`` the strictly better voxels come first and the first ties in C order fill up.  ValueError for ``k < 1``, for
+        ``k`` or the ties at ``t`` beyond ``max_count``, and what ``find`` refuses."""
+        from . import select as _sel
+
+        _sel.check_topk(self._valstat_chain("topk"), k, max_count)
+        chain, plan = self._valstat_chain("topk", with_plan=True)
+        return _sel.topk(chain, plan, k, largest, max_count, coords, as_torch)
+
     def histogram(self, bins=256, range=None, outliers: bool = False):
         """``numpy.histogram(to_tensor(), bins, range)`` from the cores: ``(counts int64, edges)``.  ``bins`` is an int
         or an explicit ascending edge array (at most 4096 bins; the edges are cast to the cores' element type and

@@ -659,6 +659,24 @@ int ndmps_argext_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const
 int ndmps_argext_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int op,
                      const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols,
                      double* h_value, int64_t* h_flat_index, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+/* ---- The voxels inside or outside an interval, or NaN, as a list, from the cores (csrc/select.hip, core/select.py).
+ * The chain contraction and the workspace of the value statistics (ndmps_valstat_workspace_bytes with n_bins = 0) and
+ * the tables of the error entry.  mode 0: lo <= v <= hi; 1: v is not NaN and not inside; 2: v is NaN (lo and hi are
+ * not read).  lo and hi are cast to the element type and compared with the computed voxel in that type, as the
+ * clipped moments pass compares, so its count is the length of the list.  A match takes the next free slot s of a
+ * 64-bit cursor and writes d_index[s] = d_row_off[r] + d_col_off[c] (the flat C-order index; an offset outside the
+ * volume matches nothing) and d_values[s] = v when s < capacity; matches at and beyond capacity are counted and not
+ * written, so nothing outside the first `capacity` slots is touched (capacity 0: d_index and d_values may be NULL).
+ * *h_total receives the number of matches.  The slots are in order of arrival: sort by index for a fixed result.
+ * Every argument check returns before the first launch; returns with the stream synchronised. */
+int ndmps_select_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores, int mode,
+                     double lo, double hi, const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                     int64_t n_cols, int64_t capacity, int64_t* d_index, float* d_values, int64_t* h_total, void* d_ws,
+                     int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_select_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores, int mode,
+                     double lo, double hi, const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                     int64_t n_cols, int64_t capacity, int64_t* d_index, double* d_values, int64_t* h_total, void* d_ws,
+                     int64_t ws_bytes, ndmps_stream_t stream);
 /* ---- Statistics per label of an atlas, from the cores (csrc/labelstat.hip, core/labelstat.py).
  * The chain contraction of the value statistics; the last product runs twice over the same operands.  The first run is
  * the moments pass, whose minimum and maximum fix on the device the two power-of-two scales s and s2; the second hands
