@@ -151,6 +151,12 @@ SIGNATURES = {
                                       vp, vp, i64, vp]),
     "ndmps_labelstat_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, vp, vp, vp,
                                       vp, vp, i64, vp]),
+    "ndmps_labelhist_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, i64, i64, i64, C.c_int]),
+    "ndmps_labelhist_plan_query": (C.c_int, [i64, i64, i64, C.c_int, p_i64]),
+    "ndmps_labelhist_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, C.c_int,
+                                      C.c_int, vp, vp, vp, vp, i64, vp]),
+    "ndmps_labelhist_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, C.c_int,
+                                      C.c_int, vp, vp, vp, vp, i64, vp]),
     "ndmps_pairstat_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, p_i64, i64, i64, i64]),
     "ndmps_pairstat_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64, i64, i64, p_i64]),
     "ndmps_pairstat_moments_f32": (C.c_int, [C.c_int, p_i64, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), p_f64, p_i64, vp, i64, vp]),

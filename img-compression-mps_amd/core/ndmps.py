@@ -1507,31 +1507,52 @@ class NDMPS:
         chain, plan = self._valstat_chain("topk", with_plan=True)
         return _sel.topk(chain, plan, k, largest, max_count, coords, as_torch)
 
-    def histogram(self, bins=256, range=None, outliers: bool = False):
+    def histogram(self, bins=256, range=None, outliers: bool = False, mask=None):
         """``numpy.histogram(to_tensor(), bins, range)`` from the cores: ``(counts int64, edges)``.  ``bins`` is an int
         or an explicit ascending edge array (at most 4096 bins; the edges are cast to the cores' element type and
         returned as used); bin b holds ``edges[b] <= v < edges[b + 1]`` and the last bin its right edge too, exactly,
         for the voxel values the chain computes.  ``range=None`` with an int runs the moments pass first for min and
         max.  ``outliers=True`` adds ``(n_below, n_above, n_nan)``; bins and outliers always sum to the voxel count.
 
+        ``mask`` (a bool or integer volume of the object's shape, non-zero meaning inside) bins only the voxels inside
+        it, through ``label_histogram`` with two labels; the edges are the same (an int ``bins`` with ``range=None``
+        spans the whole volume's min and max) and bins and outliers sum to the voxels inside the mask.
+
         Raises ValueError for more than 4096 bins, edges that are not ascending, a range that is not finite, and what
-        ``value_stats`` refuses."""
+        ``value_stats`` refuses; with a mask TypeError for one that is not bool or integer and ValueError for another
+        shape."""
         from . import valstat as _vs
 
+        if mask is not None:
+            from . import labelhist as _lh
+
+            chain, plan = self._valstat_chain("histogram", with_plan=True)
+            return _lh.masked_histogram(chain, plan, mask, bins, range, outliers)
         chain = self._valstat_chain("histogram")
         return _vs.histogram(chain, bins, range, outliers)
 
-    def quantile(self, q, passes: int = 2, bins: int = 4096):
+    def quantile(self, q, passes: int = 2, bins: int = 4096, mask=None):
         """The ``q``-quantile of the voxels (rank ``ceil(q N)``, numpy's ``method="inverted_cdf"``) by repeated
         histograms from the cores: ``(value, (lo, hi))``.  After each of up to ``passes`` histograms the bracket is the
         one bin that holds the rank, and the next pass bins inside it; the search stops early once the bracket is one
         number.  A last pass looks inside the bracket: one distinct value there is returned exactly, otherwise
-        ``value`` is the midpoint of the bracket ``(lo, hi)``, its smallest and largest voxel.  ValueError for ``q``
-        outside [0, 1], ``bins`` outside [1, 4096] and what ``value_stats`` refuses."""
+        ``value`` is the midpoint of the bracket ``(lo, hi)``, its smallest and largest voxel.  ``mask`` (as
+        ``histogram`` takes it) gives the quantile of the voxels inside it, through ``label_quantile`` with two labels.
+        ValueError for ``q`` outside [0, 1], ``bins`` outside [1, 4096] and what ``value_stats`` refuses."""
         from . import valstat as _vs
 
+        if mask is not None:
+            from . import labelhist as _lh
+
+            chain, plan = self._valstat_chain("quantile", with_plan=True)
+            return _lh.masked_quantile(chain, plan, mask, q, passes, bins)
         chain = self._valstat_chain("quantile")
         return _vs.quantile(chain, q, passes, bins)
+
+    def median(self, mask=None) -> float:
+        """The median of the voxels (``quantile(0.5, mask=mask)[0]``: numpy's ``method="inverted_cdf"``), of the whole
+        volume or of the voxels inside ``mask``; NaN where there is no non-NaN voxel."""
+        return self.quantile(0.5, mask=mask)[0]
 
     def error_to(self, x) -> dict:
         """The error of ``to_tensor()`` against ``x`` (NumPy array or device tensor of the object's shape, cast to the
@@ -1578,6 +1599,53 @@ class NDMPS:
         objs = NDMPS._region_series_objs(objs)
         pairs = [o._valstat_chain("label_stats_many", with_plan=True) for o in objs]
         return _ls.label_stats_many([chain for chain, _ in pairs], pairs[0][1], labels, n_labels)
+
+    def label_histogram(self, labels, n_labels=None, bins=64, range=None, outliers: bool = False):
+        """``numpy.histogram(to_tensor()[labels == l], bins, range)`` for every label l of an atlas, without decoding:
+        ``(counts (n_labels, bins) int64, edges)`` (core/labelhist.py, csrc/labelhist.hip).  ``labels`` and ``n_labels``
+        are ``label_stats``'s; ``bins`` and ``range`` are ``histogram``'s and give the edges it uses (an int ``bins``
+        with ``range=None`` spans the whole volume's min and max).  ``outliers=True`` adds a dict of ``below``,
+        ``above``, ``n_nan`` (int64 per label) and ``outside``: every voxel is in exactly one of the five.  Only
+        integers are added: the same inputs give the same bits.
+
+        Raises what ``label_stats`` and ``histogram`` raise, except that an infinite voxel is binned and not refused, and
+        ValueError for a call whose labels and bins need more than 64 launches (fewer bins, or split the atlas)."""
+        from . import labelhist as _lh
+
+        chain, plan = self._valstat_chain("label_histogram", with_plan=True)
+        return _lh.label_histogram(chain, plan, labels, n_labels, bins, range, outliers)
+
+    @staticmethod
+    def label_histogram_many(objs, labels, n_labels=None, bins=64, range=None, outliers: bool = False):
+        """``label_histogram`` of every frame of a series against one atlas and one edge table: counts of shape
+        ``(T, n_labels, bins)``.  With an int ``bins`` and ``range=None`` the range is the minimum and maximum over all
+        frames.  The atlas and the offset tables go to the device once and one workspace serves every frame; row t
+        equals ``objs[t].label_histogram(labels, n_labels, edges)`` bit for bit.  The list checks are those of
+        ``label_stats_many``."""
+        from . import labelhist as _lh
+
+        objs = NDMPS._region_series_objs(objs)
+        pairs = [o._valstat_chain("label_histogram_many", with_plan=True) for o in objs]
+        return _lh.label_histogram_many([chain for chain, _ in pairs], pairs[0][1], labels, n_labels, bins, range, outliers)
+
+    def label_quantile(self, labels, q, n_labels=None, passes: int = 2, bins: int = 64) -> dict:
+        """The ``q``-quantile (numpy's ``method="inverted_cdf"``; ``q`` a number or a 1-D sequence) of the voxels under
+        each label, without decoding: a dict of ``value``, ``lo``, ``hi`` (float64, ``(n_labels,)`` or ``(n_labels, Q)``),
+        ``count``, ``n_nan`` and ``outside``.  Histograms with one edge row per label narrow every label's bracket
+        ``passes`` times by ``bins``; a last launch finds the smallest and largest voxel inside each bracket, so
+        ``value`` is exact where they coincide and their midpoint otherwise, and ``lo <= true quantile <= hi``.  NaN for
+        a label without a non-NaN voxel.  The refusals of ``label_histogram``."""
+        from . import labelhist as _lh
+
+        chain, plan = self._valstat_chain("label_quantile", with_plan=True)
+        return _lh.label_quantile(chain, plan, labels, q, n_labels, passes, bins)
+
+    def label_median(self, labels, n_labels=None, passes: int = 2, bins: int = 64):
+        """``label_quantile(labels, 0.5, ...)["value"]``: the median of the voxels under each label."""
+        from . import labelhist as _lh
+
+        chain, plan = self._valstat_chain("label_median", with_plan=True)
+        return _lh.label_median(chain, plan, labels, n_labels, passes, bins)
 
     # ---------------------------------------------------- statistics of two objects on the cores (core/pairstat.py)
     def _pairstat_chains(self, other, what):

@@ -712,6 +712,41 @@ int ndmps_labelstat_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, co
                         const int32_t* d_col_perm, int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq,
                         int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws, int64_t ws_bytes,
                         ndmps_stream_t stream);
+/* ---- Histograms per label of an atlas, from the cores (csrc/labelhist.hip, core/labelhist.py): the labelled reading
+ * of ndmps_labelstat_* (d_labels, label_elem_bytes and the tables of the error entry; a label outside [0, n_labels)
+ * is counted in `outside`) with the exact bin search of ndmps_valstat_histogram_*.  A voxel is binned against the
+ * edge row of its label.  h_edges (HOST, element type): per_label == 0 one row of n_bins + 1 edges for every label,
+ * per_label != 0 n_labels rows of n_bins + 1.  A row is ascending and not NaN; it need not be strictly ascending, so
+ * a short row may repeat its last edge (a voxel equal to that edge lands in the last bin, which is closed on the
+ * right), and -inf / +inf are legal edges.  Only integers are added atomically: the same inputs give the same bits.
+ * NaN voxels are counted per label; an infinite voxel is binned like any other.
+ *
+ * One launch takes a window of labels whose edge rows, keys and 32-bit counters fit in 64 KiB of dynamic LDS:
+ *   lds(w) = elem_bytes * ((per_label ? w : 1) * (n_bins + 1) + 2 w) + 4 w (n_bins + 3),
+ * window = the largest w <= n_labels with lds(w) <= 65536 (at least 1 for n_bins <= 4096), launches =
+ * ceil(n_labels / window).  More than 64 launches are refused with NDMPS_EINVAL ("use fewer bins or split the
+ * atlas").  ndmps_labelhist_plan_query (host arithmetic only) writes h_out = {window, launches, lds(window), table
+ * bytes} or returns that refusal; the table is 8 * (n_labels * (n_bins + 5) + 1) bytes rounded up to 256.
+ *
+ * Workspace: ndmps_valstat_workspace_bytes(..., n_bins = 0) + the table + the edge rows rounded up to 256; 0 for bad
+ * arguments and for a call that would be refused.  1 <= n_labels <= 4096, 1 <= n_bins <= 4096.
+ * Results (HOST): h_counts[n_labels * (n_bins + 3)], per label the bins, then below, above and the NaN count;
+ * h_minmax[2 n_labels] the smallest and then the largest voxel inside [e[0], e[n_bins]] of each label as doubles (NaN
+ * where there is none); h_info = {outside, voxels}.  Every argument check returns before the first launch; returns
+ * with the stream synchronised. */
+int64_t ndmps_labelhist_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds, int64_t elem_bytes,
+                                        int64_t n_labels, int64_t n_bins, int per_label);
+int ndmps_labelhist_plan_query(int64_t elem_bytes, int64_t n_labels, int64_t n_bins, int per_label, int64_t* h_out);
+int ndmps_labelhist_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                        const void* d_labels, int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off,
+                        const int32_t* d_col_perm, int64_t n_cols, int n_labels, const float* h_edges, int n_bins,
+                        int per_label, int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws,
+                        int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_labelhist_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                        const void* d_labels, int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off,
+                        const int32_t* d_col_perm, int64_t n_cols, int n_labels, const double* h_edges, int n_bins,
+                        int per_label, int64_t* h_counts, double* h_minmax, int64_t* h_info, void* d_ws,
+                        int64_t ws_bytes, ndmps_stream_t stream);
 /* ---- Statistics of TWO chains of one shape and one factorisation, from the cores (csrc/pairstat.hip,
  * core/pairstat.py): the pair moments and the joint histogram of the two volumes, with neither written.  Both chains
  * have the site dims h_dims, so their last products have the same rows and columns (the split depends on the dims
