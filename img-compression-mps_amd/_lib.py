@@ -157,6 +157,16 @@ SIGNATURES = {
                                       C.c_int, vp, vp, vp, vp, i64, vp]),
     "ndmps_labelhist_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, C.c_int,
                                       C.c_int, vp, vp, vp, vp, i64, vp]),
+    "ndmps_labelpair_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, p_i64, i64, i64]),
+    "ndmps_labelpair_scales": (C.c_int, [C.c_double, C.c_double, C.c_double, i64, p_int]),
+    "ndmps_labelpair_f32": (C.c_int, [C.c_int, p_i64, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64,
+                                      C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ndmps_labelpair_f64": (C.c_int, [C.c_int, p_i64, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), vp, C.c_int, vp, vp, vp, i64,
+                                      C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ndmps_labelpair_original_f32": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, C.c_int, vp, vp, vp, i64, C.c_int,
+                                               vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ndmps_labelpair_original_f64": (C.c_int, [C.c_int, p_i64, p_i64, C.POINTER(vp), vp, vp, C.c_int, vp, vp, vp, i64, C.c_int,
+                                               vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "ndmps_pairstat_workspace_bytes": (i64, [C.c_int, p_i64, p_i64, p_i64, i64, i64, i64]),
     "ndmps_pairstat_plan_query": (C.c_int, [C.c_int, C.c_int, p_i64, p_i64, p_i64, i64, i64, p_i64]),
     "ndmps_pairstat_moments_f32": (C.c_int, [C.c_int, p_i64, p_i64, p_i64, C.POINTER(vp), C.POINTER(vp), p_f64, p_i64, vp, i64, vp]),

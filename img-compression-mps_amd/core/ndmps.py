@@ -1702,6 +1702,51 @@ class NDMPS:
         pairs = [o._pairstat_chains(ref, "mutual_information_many") for o in objs]
         return _ps.mutual_information_many([a for a, _ in pairs], pairs[0][1] if pairs else None, bins, range, normalized)
 
+    # ---------------------------------------------------- two values per voxel under an atlas (core/labelpair.py)
+    def label_pair_stats(self, other, labels, n_labels=None) -> dict:
+        """``pair_stats`` of this volume (a) and ``other`` (b) under each label of an atlas, from the cores of both with
+        neither decoded (csrc/labelpair.hip).  ``labels`` and ``n_labels`` are ``label_stats``'s.  A dict of arrays of
+        length ``n_labels`` over the voxels of each label where neither value is NaN: ``count``, ``n_nan`` (voxels
+        where either is), ``sum_a, sum_b, sumsq_a, sumsq_b, sum_ab, sse, max_abs_diff, min_a, max_a, min_b, max_b``, the
+        derived ``mean_a, mean_b, cov, pearson, mse, rel_frob`` (NaN for a label without a counted voxel, whose sums
+        are 0), the scalar ``outside`` and ``scales``, a dict of the six exponents of the 64-bit fixed-point sums.
+        Only integers are added: the same inputs give the same bits, and where neither volume has a NaN the fields of
+        a and of b are those of ``label_stats`` bit for bit.  One fp32 and one fp64 object make the call fp64.
+
+        Raises what ``pair_stats`` and ``label_stats`` raise, an infinite voxel in either volume included."""
+        from . import labelpair as _lp
+
+        a, b = self._pairstat_chains(other, "label_pair_stats")
+        _, plan = self._valstat_chain("label_pair_stats", with_plan=True)
+        return _lp.label_pair_stats(a, b, plan, labels, n_labels)
+
+    @staticmethod
+    def label_pair_stats_many(objs, ref, labels, n_labels=None) -> dict:
+        """``objs[t].label_pair_stats(ref, labels, n_labels)`` for every frame of a series against one reference
+        object: the same dict with arrays of shape ``(T, n_labels)``; ``outside`` and each entry of ``scales`` have
+        length T.  The atlas and the offset tables go to the device once and one workspace serves every frame; row t
+        equals the single call bit for bit.  The list checks are those of ``label_stats_many``."""
+        from . import labelpair as _lp
+
+        objs = NDMPS._region_series_objs(objs)
+        pairs = [o._pairstat_chains(ref, "label_pair_stats_many") for o in objs]
+        _, plan = objs[0]._valstat_chain("label_pair_stats_many", with_plan=True)
+        return _lp.label_pair_stats_many([a for a, _ in pairs], pairs[0][1], plan, labels, n_labels)
+
+    def label_error_to(self, x, labels, n_labels=None) -> dict:
+        """``error_to(x)`` under each label of an atlas, without decoding: the error of the encoding in the lesion, the
+        hippocampus or the cortex ribbon and not in the air around the head.  ``x`` is the original (cast to the
+        cores' element type), read at the address where the label is read.  A dict of arrays of length ``n_labels``:
+        ``count, n_nan, sse, mse, max_abs, ref_sumsq, ref_max, rel_frob, psnr``, and the scalars ``outside`` and
+        ``peak``, the maximum of ``x`` that ``psnr_to`` uses (``error_to(x)["ref_max"]``); ``psnr[l]`` is
+        ``10 log10(peak^2 / mse[l])``, comparable with ``psnr_to(x)``.  The same computation as ``label_pair_stats``
+        with ``b := x``.  Raises what ``error_to`` and ``label_stats`` raise, and ValueError for an infinite element
+        of ``x``."""
+        from . import labelpair as _lp
+
+        chain, plan = self._valstat_chain("label_error_to", with_plan=True)
+        return _lp.label_error_to(chain, plan, x, labels, n_labels)
+
     # ---------------------------------------------------- quantise / on-disk size
     def compress_to_dtype(self, dtype=np.uint16, replace: bool = False):
         """Integer-truncate each MPS tensor to the given unsigned dtype (ndmps.py:182-207)."""

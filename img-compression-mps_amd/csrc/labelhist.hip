@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "labelstat_device.h"
 #include "typed.h"
 #include "valstat_device.h"
 #include "valstat_plan.h"
@@ -109,12 +110,7 @@ struct LabelHistEpi {
     if (valid) {
       const int64_t at = a.row_off[row] + a.col_off[col];
       if (at >= 0 && at < a.numel) {  // the tables are not trusted: nothing is read outside lab
-        int label;
-        switch (a.lab_bytes) {  // uniform over the launch
-          case 1: label = static_cast<const uint8_t*>(a.lab)[at]; break;
-          case 2: label = static_cast<const int16_t*>(a.lab)[at]; break;
-          default: label = static_cast<const int32_t*>(a.lab)[at]; break;
-        }
+        int label = label_read(a.lab, a.lab_bytes, at);
         if (label < 0 || label >= a.n_labels) {
           if (a.label_base == 0) ++outside;
         } else {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "labelstat_device.h"
 #include "typed.h"
 #include "valstat_device.h"
 #include "valstat_plan.h"
@@ -15,33 +16,11 @@ namespace {
 // Which threads meet which label depends on the data, so no fixed tree folds the sums.  They are 64-bit fixed-point
 // integers instead: q = llrint(v 2^s) into a signed sum, q2 = llrint(v v 2^s2) into an unsigned one, and integer
 // addition gives the same bits in any order.  The scales follow from the extremes of the moments pass over the same
-// operands (labelstat_scale_kernel), by the one rule below.
+// operands (labelstat_scale_kernel), by the one rule of labelstat_device.h.
 constexpr int kLabelWindow = 1024;  // labels of one launch: their LDS table (40 B each in fp64) fits beside the tiles
-constexpr int kLabelMax = 4096;
 constexpr int kLabelSlots = 6;      // global table: sum, sum of squares, count, NaN count, min key, max key (n_labels each)
 constexpr int kLabelTail = 5;       // then: outside, overflow, s, s2, non-finite flag
 enum { kTailOutside = 0, kTailOverflow = 1, kTailS = 2, kTailS2 = 3, kTailFlag = 4 };
-
-// nb = ceil(log2 numel)
-__host__ __device__ inline int labelstat_bits(int64_t numel) {
-  int nb = 0;
-  while (nb < 62 && ((int64_t)1 << nb) < numel) ++nb;
-  return nb;
-}
-// maxabs < 2^e (frexp), s = 61 - nb - e, so that numel * |v| 2^s <= 2^61; s2 likewise from the fp64 product
-// maxabs * maxabs, which bounds every fl(v * v) (2 e where the product leaves the fp64 range)
-__host__ __device__ inline void labelstat_scale_rule(double maxabs, int64_t numel, int* s, int* s2) {
-  *s = *s2 = 0;
-  if (!(maxabs > 0.0)) return;
-  const int nb = labelstat_bits(numel);
-  int e = 0, e2 = 0;
-  frexp(maxabs, &e);
-  const double sq = maxabs * maxabs;
-  if (sq > 0.0 && sq <= 1.7976931348623157e308) frexp(sq, &e2); else e2 = 2 * e;
-  const int a = 61 - nb - e, b = 61 - nb - e2;
-  *s = a < -1000 ? -1000 : (a > 1000 ? 1000 : a);
-  *s2 = b < -1000 ? -1000 : (b > 1000 ? 1000 : b);
-}
 
 // the folded record of the moments pass -> s, s2 and the non-finite flag in the table's tail (one thread)
 __global__ void labelstat_scale_kernel(const Record* __restrict__ result, int64_t numel, long long* __restrict__ tail) {
@@ -130,12 +109,7 @@ struct LabelEpi {
     if (!valid || dead) return;
     const int64_t at = a.row_off[row] + a.col_off[col];
     if (at < 0 || at >= a.numel) return;  // the tables are not trusted: nothing is read outside lab
-    int label;
-    switch (a.lab_bytes) {  // uniform over the launch
-      case 1: label = static_cast<const uint8_t*>(a.lab)[at]; break;
-      case 2: label = static_cast<const int16_t*>(a.lab)[at]; break;
-      default: label = static_cast<const int32_t*>(a.lab)[at]; break;
-    }
+    int label = label_read(a.lab, a.lab_bytes, at);
     if (label < 0 || label >= a.n_labels) {
       if (a.label_base == 0) ++outside;
       return;

@@ -1,6 +1,8 @@
 // The device layer and the host prologue of the statistics family: valstat.hip (moments, histogram, error),
 // axisext.hip (extremes along axes, the place of the global extreme), labelstat.hip (statistics per label), each one
-// chain reduced, and pairstat.hip (two chains reduced together).  One text each of
+// chain reduced, pairstat.hip (two chains reduced together) and labelpair.hip (two values per voxel under a label; the
+// pair layer on top of this one is pairstat_device.h, the label read and the scale rule labelstat_device.h).  One text
+// each of
 //
 //   the tile       StatTile, stat_tile_accumulate (staging and MFMA k-loop), stat_tile_for_each (the walk over a
 //                  wavefront's accumulator slots), and valstat_product_kernel, the single-chain product on them

@@ -793,6 +793,61 @@ int ndmps_pairstat_histogram_f64(int L, const int64_t* h_dims, const int64_t* h_
                                  const double* const* h_cores_a, const double* const* h_cores_b, const double* h_edges_a,
                                  int bins_a, const double* h_edges_b, int bins_b, int64_t* h_counts, void* d_ws,
                                  int64_t ws_bytes, ndmps_stream_t stream);
+/* ---- Pair statistics per label of an atlas, from the cores (csrc/labelpair.hip, core/labelpair.py): two values per
+ * voxel under the label d_labels[d_row_off[r] + d_col_off[c]].  ndmps_labelpair_*: the voxels of two chains of one
+ * shape and one factorisation (as ndmps_pairstat_*; both run in the column order d_col_perm).  ndmps_labelpair_original_*:
+ * the voxel of one chain and the element of d_ref (device, C order, element type) at the voxel's address, which is
+ * also where the label is read.  A call is the moments pass of ndmps_pairstat_moments_* over the same operands, whose
+ * extremes fix six exponents on the device, then one labelled launch per window of 512 labels.  Per voxel where
+ * neither value is NaN, with d = (double)a - (double)b and the products formed in fp64, llrint(. 2^scale) of a, b,
+ * a b (signed) and a a, b b, d d (unsigned) is added into 64-bit integers, and integer maxima of order-preserving
+ * keys give min a, max a, min b, max b and max |d| (the last an fp64 key in either element type).  Only integers are
+ * added atomically: the same inputs give the same bits.  A voxel with either value NaN is counted in n_nan of its
+ * label; an infinite voxel or element of d_ref (or an fp64 difference that overflows) is refused with NDMPS_EINVAL
+ * ("label pair statistics need finite voxels").  A label outside [0, n_labels) is counted in `outside`.
+ *
+ * The exponents (ndmps_labelpair_scales, host arithmetic only; the device applies the same function), h_scales[6] =
+ * {s_a, s2_a, s_b, s2_b, s_ab, s2_d}: (s_a, s2_a) = ndmps_labelstat_scales(max |a|), (s_b, s2_b) likewise from max |b|,
+ * s2_d the second exponent of ndmps_labelstat_scales(max |a - b|), and s_ab = 61 - nb - e with
+ * fl(max |a| max |b|) < 2^e by frexp (e_a + e_b where that product is 0 or infinite), clamped to [-1000, 1000]; 0 when
+ * either maximum is 0.  The maxima are taken over the voxels where neither value is NaN.
+ *
+ * Workspace: ndmps_labelpair_workspace_bytes(L, dims, bonds_a, bonds_b, elem_bytes, n_labels) =
+ * ndmps_pairstat_workspace_bytes(.., 0, 0), or with h_bonds_b == NULL (the original)
+ * ndmps_valstat_workspace_bytes(.., n_bins = 0), + the table, 8 * (13 * n_labels + 14) bytes rounded up to 256:
+ * thirteen 64-bit slots per label (sum a, sum b, sum a b, sum a^2, sum b^2, sum d^2, count, NaN count, and the keys of
+ * min a, max a, min b, max b, max |d|), then outside, overflow, the six exponents, the non-finite flag and the five
+ * extremes of the whole volume.  0 for bad arguments.  1 <= n_labels <= 4096; d_labels as ndmps_labelstat_*.
+ * Results (HOST): h_sums[3 n_labels] the signed integers of a, b, a b (value = integer 2^-s_a, 2^-s_b, 2^-s_ab);
+ * h_sumsq[3 n_labels] the unsigned ones of a a, b b, d d (2^-s2_a, 2^-s2_b, 2^-s2_d); h_counts[2 n_labels] the counted
+ * voxels then the NaN counts; h_ext[5 n_labels] min a, max a, min b, max b, max |d| as doubles (NaN where the count
+ * is 0); h_info[NDMPS_LABELPAIR_INFO_SLOTS] = {outside, s_a, s2_a, s_b, s2_b, s_ab, s2_d, voxels}; h_whole[5] the
+ * same five extremes over every counted voxel of the volume, labelled or not (+-inf where none is counted).
+ * Every argument check returns before the first launch; one copy to the host; returns with the stream synchronised. */
+#define NDMPS_LABELPAIR_INFO_SLOTS 8
+int64_t ndmps_labelpair_workspace_bytes(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                                        int64_t elem_bytes, int64_t n_labels);
+int ndmps_labelpair_scales(double maxabs_a, double maxabs_b, double max_abs_diff, int64_t numel, int* h_scales);
+int ndmps_labelpair_f32(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                        const float* const* h_cores_a, const float* const* h_cores_b, const void* d_labels,
+                        int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                        int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq, int64_t* h_counts, double* h_ext,
+                        int64_t* h_info, double* h_whole, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_labelpair_f64(int L, const int64_t* h_dims, const int64_t* h_bonds_a, const int64_t* h_bonds_b,
+                        const double* const* h_cores_a, const double* const* h_cores_b, const void* d_labels,
+                        int label_elem_bytes, const int64_t* d_row_off, const int64_t* d_col_off, const int32_t* d_col_perm,
+                        int64_t n_cols, int n_labels, int64_t* h_sums, uint64_t* h_sumsq, int64_t* h_counts, double* h_ext,
+                        int64_t* h_info, double* h_whole, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_labelpair_original_f32(int L, const int64_t* h_dims, const int64_t* h_bonds, const float* const* h_cores,
+                                 const float* d_ref, const void* d_labels, int label_elem_bytes, const int64_t* d_row_off,
+                                 const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols, int n_labels,
+                                 int64_t* h_sums, uint64_t* h_sumsq, int64_t* h_counts, double* h_ext, int64_t* h_info,
+                                 double* h_whole, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
+int ndmps_labelpair_original_f64(int L, const int64_t* h_dims, const int64_t* h_bonds, const double* const* h_cores,
+                                 const double* d_ref, const void* d_labels, int label_elem_bytes, const int64_t* d_row_off,
+                                 const int64_t* d_col_off, const int32_t* d_col_perm, int64_t n_cols, int n_labels,
+                                 int64_t* h_sums, uint64_t* h_sumsq, int64_t* h_counts, double* h_ext, int64_t* h_info,
+                                 double* h_whole, void* d_ws, int64_t ws_bytes, ndmps_stream_t stream);
 /* C = A B with table-driven addressing of A and / or C: element (m, k) of A at d_A[d_a_row[m] + d_a_col[k]],
  * element (m, n) of C at d_C[d_c_row[m] + d_c_col[n]] (NULL pair: dense row-major).  a_vec4: d_a_col comes in
  * aligned runs of four consecutive offsets. */
